@@ -8,7 +8,7 @@ factorises and scores W/2 = 128 kernel matrices; K steps = 256*K
 Inputs (X, y, walker positions) are resident / tiny; only (128, 18) doubles of proposals go up and
 128 log-likelihoods come back per half-step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -808,6 +808,10 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="form the process group, report it (backend, ranks RCCL counts, device of every rank) and exit "
                     "without device work: the launch path alone (the CPU tests run it over gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (the ensemble's "
+                    "walker positions and log-probabilities, float64) as DIR/<name>.npy, on rank 0; the inputs are seeded, "
+                    "so two builds run with the same arguments can be compared output for output")
     ap.add_argument("--launch-free-only", action="store_true", help="(internal) the launch_free section alone, as one JSON line")
     ap.add_argument("--device", type=int, default=0, help="(internal) device of --launch-free-only")
     ap.add_argument("--peak", type=float, default=0.0, help="(internal) fp64 MFMA peak the fractions are quoted against")
@@ -827,7 +831,9 @@ def main():
     from bayes_skopt_amd import _lib, distributed
     from bayes_skopt_amd.bayesgpr import _AsyncLogProb, _ShardedLogProb
 
-    ndev = _lib.device_count()
+    # a rendezvous over gloo does no device work: its ranks do not open the GPU at all (eight of them would be eight GPU users)
+    gloo_rendezvous = args.rendezvous_only and os.environ.get("BGP_DIST_BACKEND") == "gloo"
+    ndev = 0 if gloo_rendezvous else _lib.device_count()
     if ndev < 1 and not args.rendezvous_only:
         raise SystemExit("bench.py needs an MI355X (no CPU fallback)")
     rank, local_rank, ws = distributed.world()
@@ -885,6 +891,10 @@ def main():
     dt = float(np.median(passes))
     resident_runs = int(getattr(sampler, "resident_runs", 0))
     pos, lp = state.coords, state.log_prob
+    if args.dump_outputs and rank == 0:  # the State the last timed step returned: (W, d + 2) + (W,) doubles, 37 KB
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "coords.npy"), np.ascontiguousarray(pos, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "log_prob.npy"), np.ascontiguousarray(lp, dtype=np.float64))
 
     # final posterior-sample gather (RCCL over xGMI when N > 1; the shared ensemble's chain is on every rank already)
     tg = time.perf_counter()

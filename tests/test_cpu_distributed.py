@@ -321,12 +321,16 @@ def test_a_rank_that_fails_inside_the_sharded_evaluation_stops_every_rank(tmp_pa
 
 
 def test_bench_rendezvous_at_world_size_eight():
+    """Eight ranks over gloo: the launch path alone, with no rank opening a GPU (on a GPU node too -- eight processes on one
+    device is more than it may serve at once)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["BGP_DIST_BACKEND"] = "gloo"
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rendezvous-only"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][-1])
     assert d["n_gpus"] == 8 and d["ranks_seen"] == [float(r) for r in range(8)] and len(d["rank_devices"]) == 8
+    assert d["dist_backend"] == "gloo" and d["rccl_nranks"] is None and d["rank_devices"] == [-1] * 8
 
 
 def test_rendezvous_ignores_a_consistent_set_of_stale_files(tmp_path):

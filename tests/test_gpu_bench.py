@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -155,3 +156,22 @@ def test_bench_two_ranks_on_one_gpu(shard):
         assert d["weak_chains_evals_per_s"] > 0
         assert abs(d["value"] - 256 * 2 / (d["ms_per_step"] * 2 * 1e-3)) / d["value"] < 1e-9
 
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs DIR: the State the last timed step returned (walker positions and log-probabilities, float64), written
+    after exactly `steps` timed steps; the inputs are seeded, so two runs with the same arguments write the same arrays."""
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-extras",
+                              "--no-cpu-baseline", "--no-live-pmc", "--dump-outputs", str(out)],
+                             capture_output=True, text=True, timeout=900)
+        d = _line(res)
+        assert d["steps"] == 3 and d["warmup"] == 1
+        assert sorted(os.listdir(out)) == ["coords.npy", "log_prob.npy"]
+        dumps.append({k: np.load(out / (k + ".npy")) for k in ("coords", "log_prob")})
+    a, b = dumps
+    assert a["coords"].shape == (256, 18) and a["log_prob"].shape == (256,)
+    assert a["coords"].dtype == np.float64 and a["log_prob"].dtype == np.float64
+    assert np.all(np.isfinite(a["coords"])) and np.all(np.isfinite(a["log_prob"]))
+    assert np.array_equal(a["coords"], b["coords"]) and np.array_equal(a["log_prob"], b["log_prob"])
