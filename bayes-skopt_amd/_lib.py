@@ -82,6 +82,12 @@ SIGNATURES = {
     "bgp_acq_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, _dp]),
     "bgp_pvrs": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "bgp_pvrs_prepare": (C.c_int, [_vp, _dp, C.c_int, _ip]),
+    "bgp_fantasy_begin": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, C.c_int,
+                                    C.c_int]),
+    "bgp_fantasy_step": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _ip, _dp]),
+    "bgp_fantasy_moments": (C.c_int, [_vp, _dp, _dp]),
+    "bgp_fantasy_end": (C.c_int, [_vp]),
+    "bgp_fantasy_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -177,6 +183,7 @@ def device_identity(device=0):
 
 ACQ_EI, ACQ_MEAN, ACQ_LCB, ACQ_STD = 0, 1, 2, 3  # include/bgp.h BGP_ACQ_*
 ACQ_MAX = 8
+BGP_LIE_VALUE, BGP_LIE_KB = 0, 1  # include/bgp.h BGP_LIE_* (bgp_fantasy_step)
 
 
 _live_contexts = weakref.WeakSet()
@@ -527,6 +534,45 @@ class Context:
         covs = np.empty(Xc.shape[0])
         _check(self._lib.bgp_pvrs(self._h, _p(H), Xc.shape[0], _p(Xc), Xt.shape[0], _p(Xt), _p(covs)), "bgp_pvrs")
         return covs
+
+    # ---- batch proposals by fantasy conditioning (bgp_fantasy_*)
+    def fantasy_begin(self, H_kernel, noise, Xcand, y_mean, y_std, kinds, params, n_samples, qmax):
+        """Start a batch over the resident posteriors (built with the draws' h): H_kernel with the white level at -inf,
+        ``noise`` (B,) the variance of a fantasy observation per draw."""
+        H = self._H(H_kernel)
+        noise = _c(np.asarray(noise, dtype=np.float64).reshape(H.shape[0]))
+        Xc = _c(np.atleast_2d(Xcand))
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        params = _c(np.asarray(params, dtype=np.float64))
+        self._fantasy_shape = (H.shape[0], Xc.shape[0], len(kinds))
+        _check(self._lib.bgp_fantasy_begin(self._h, H.shape[0], _p(H), _p(noise), Xc.shape[0], _p(Xc), float(y_mean),
+                                           float(y_std), len(kinds), _p(kinds), _p(params), int(n_samples), int(qmax)),
+               "bgp_fantasy_begin")
+
+    def fantasy_step(self, p, lie, want_values=False):
+        """Condition on candidate ``p`` with ``lie`` (a normalised value, or None for the kriging believer); returns
+        (next index, averaged values (n_acq, m) or None)."""
+        _B, m, n_acq = self._fantasy_shape
+        nxt = np.zeros(1, dtype=np.int32)
+        vals = np.empty((n_acq, m)) if want_values else None
+        kind = BGP_LIE_KB if lie is None else BGP_LIE_VALUE
+        _check(self._lib.bgp_fantasy_step(self._h, int(p), kind, 0.0 if lie is None else float(lie), _p(nxt),
+                                          _p(vals) if want_values else C.cast(None, _dp)), "bgp_fantasy_step")
+        return int(nxt[0]), vals
+
+    def fantasy_moments(self):
+        B, m, _ = self._fantasy_shape
+        mean, var = np.empty((B, m)), np.empty((B, m))
+        _check(self._lib.bgp_fantasy_moments(self._h, _p(mean), _p(var)), "bgp_fantasy_moments")
+        return mean, var
+
+    def fantasy_end(self):
+        _check(self._lib.bgp_fantasy_end(self._h), "bgp_fantasy_end")
+
+    def fantasy_stats(self):
+        out = (C.c_longlong * 2)()
+        _check(self._lib.bgp_fantasy_stats(self._h, out), "bgp_fantasy_stats")
+        return {"begins": int(out[0]), "steps": int(out[1])}
 
     def sample_y(self, b, h_kernel, Xq, z, jitter=0.0):
         H = self._H(h_kernel)

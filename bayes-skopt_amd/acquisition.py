@@ -86,7 +86,7 @@ def _device_acq_spec(acq, kwargs):
 
 
 def evaluate_acquisitions(X, gpr, acquisition_functions=None, n_samples=10, progress=False, random_state=None,
-                          **kwargs):
+                          _record=None, **kwargs):
     """Evaluate a set of acquisition functions on candidate points X (m, d).
 
     Same arguments, RNG consumption and averaging as ``bask/acquisition.py:48-147``:
@@ -95,6 +95,11 @@ def evaluate_acquisitions(X, gpr, acquisition_functions=None, n_samples=10, prog
     the noise switched off (``noise_set_to_zero``); an output that is not all finite contributes
     zeros; ``gpr.theta`` is restored at the end.
     Returns (len(acquisition_functions), m).
+
+    ``_record`` (private, never forwarded to the acquisitions): a dict that receives what a batch proposal needs to
+    condition this evaluation on fantasy points (``Optimizer.ask(n_points > 1)``) -- the chain rows drawn (``rows``),
+    ``n_samples``, per PVRS position its Thompson points (``thompson``) and, per other whole-GP acquisition, the
+    generator state it was handed (``replay``).  The generator is consumed as without it.
     """
     X = np.atleast_2d(np.asarray(X, dtype=np.float64))
     n_cand = len(X)
@@ -106,13 +111,21 @@ def evaluate_acquisitions(X, gpr, acquisition_functions=None, n_samples=10, prog
 
     for i_acq, acq in enumerate(acqs):
         if isinstance(acq, FullGPAcquisition):
-            vals = acq(X, gpr, random_state=random_state, **kwargs)
+            if _record is not None and type(acq) is PVRS:
+                vals, thompson = acq._evaluate(X, gpr, random_state=random_state, **kwargs)
+                _record.setdefault("thompson", {})[i_acq] = thompson
+            else:
+                if _record is not None:  # (a batch replays the acquisition itself with the same generator state)
+                    _record.setdefault("replay", {})[i_acq] = random_state.get_state()
+                vals = acq(X, gpr, random_state=random_state, **kwargs)
             if np.all(np.isfinite(vals)):
                 out[i_acq] = vals
 
     has_unc = any(isinstance(a, UncertaintyAcquisition) for a in acqs)
     has_smp = any(isinstance(a, SampleAcquisition) for a in acqs)
     rows = gpr.chain_[trace_i]
+    if _record is not None:
+        _record.update(rows=rows, n_samples=n_samples)
     on_device = {}
     if len(trace_i) > 0 and has_unc:
         specs = [(j, _device_acq_spec(a, kwargs)) for j, a in enumerate(acqs) if isinstance(a, UncertaintyAcquisition)]
@@ -147,6 +160,21 @@ def evaluate_acquisitions(X, gpr, acquisition_functions=None, n_samples=10, prog
                 out[j] += tmp / n_samples
     if not np.array_equal(gpr.theta, theta_backup):
         gpr.theta = theta_backup
+    return out
+
+
+def _average_uncertainty(gpr, acq, mus, stds, n_samples, kwargs):
+    """One uncertainty acquisition averaged over the rows' (mu, std) as ``evaluate_acquisitions`` averages it: the
+    device closed forms (bgp_acq_values) where the acquisition has one, else the host callable one row at a time; a row
+    whose values are not all finite contributes zeros."""
+    spec = _device_acq_spec(acq, kwargs)
+    if DEVICE_ACQUISITIONS and spec is not None:
+        return gpr._ctx.acq_values(mus, stds, [spec[0]], [spec[1]], n_samples)[0]
+    out = np.zeros(mus.shape[1])
+    for pos in range(mus.shape[0]):
+        tmp = acq(mus[pos], stds[pos], **kwargs)
+        if np.all(np.isfinite(tmp)):
+            out += tmp / n_samples
     return out
 
 
@@ -255,7 +283,11 @@ class PVRS(FullGPAcquisition):
     score each candidate by how much observing it reduces the predictive variance at those points."""
 
     def __call__(self, X, gp, *args, n_thompson=10, random_state=None, **kwargs):
+        return self._evaluate(X, gp, n_thompson=n_thompson, random_state=random_state)[0]
+
+    def _evaluate(self, X, gp, *args, n_thompson=10, random_state=None, **kwargs):
+        """(values, Thompson points): the batch proposal conditions on fantasy points with the same Thompson points."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         thompson_sample = gp.sample_y(X, sample_mean=True, n_samples=n_thompson, random_state=random_state)
         thompson_points = X[np.argmin(thompson_sample, axis=0)]
-        return _device_pvrs(gp, X, thompson_points)
+        return _device_pvrs(gp, X, thompson_points), thompson_points

@@ -16,6 +16,7 @@ Where the reference relies on inherited third-party code, the behaviour restated
     (``sklearn/_gpr.py:296-341``) -- objective and gradient are evaluated on the device;
   * skopt's predict: ``var = diag - einsum(K*, K*, K_inv_)`` clipped at 0.
 """
+import sys
 import warnings
 from contextlib import contextmanager, nullcontext
 
@@ -935,6 +936,141 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             covs[lo : lo + step] = tt.sum() + np.sum(cross * cross / cii[None, :], axis=0)
         return covs
 
+    # ---- batch proposals (Optimizer.ask(n_points > 1))
+    def _fantasy_batch(self, X, first, q, acq, rows, n_samples, acq_kwargs, lie, thompson=None, replay=None, path="auto",
+                       want_moments=False):
+        """Greedy batch over the candidates ``X`` of a proposal whose argmax was ``first``: point j + 1 maximises ``acq``
+        for the GPs of the same chain ``rows`` (PVRS / VR and other whole-GP acquisitions: the median GP; PVRS with the
+        same ``thompson`` points) conditioned on the j points chosen so far with their fantasy observations.  ``lie``:
+        the fantasy value in y units, or None for the kriging believer (every GP's own posterior mean).
+        Hyper-parameters, warps and the y normalisation stay fixed; a fantasy point carries the noise a ``tell`` with
+        noise 0 would give it (the scalar alpha + the row's white level; for PVRS / VR alpha enters only as a vector,
+        with 0 appended, as the reference does for the candidate row).  A whole-GP acquisition other than PVRS / VR is
+        called itself on the conditioned median GP with ``replay``, the generator state the proposal handed it.
+        Returns (q indices into X, the (q - 1, m) step values, "fast" | "fallback", info) with info["step_ms"] the
+        wall time of every step; on the fast path also info["begin_ms"] / ["end_ms"], info["device"] (its counters)
+        and, with ``want_moments``, info["moments"] (the conditioned latent means, variances)."""
+        from . import acquisition as A
+
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if not 1 <= q <= X.shape[0]:
+            raise ValueError(f"a batch of {q} points from {X.shape[0]} candidates")
+        lie_n = None if lie is None else (float(lie) - float(np.ravel(self.y_train_mean_)[0])) / float(np.ravel(self.y_train_std_)[0])
+        spec = A._device_acq_spec(acq, acq_kwargs) if isinstance(acq, A.UncertaintyAcquisition) else None
+        fast = (path != "fallback" and spec is not None and A.DEVICE_ACQUISITIONS and not self.warp_inputs and not self._generic
+                and X.shape[1] <= 32)
+        if isinstance(acq, A.UncertaintyAcquisition) and (rows is None or len(rows) == 0):
+            # no hyper-posterior draws (n_samples=0): every value is 0, np.argmax takes the lowest index left
+            rest = [i for i in range(X.shape[0]) if i != first][: q - 1]
+            return [int(first)] + rest, np.zeros((q - 1, X.shape[0])), "fallback", {"step_ms": []}
+        if fast:
+            return self._fantasy_fast(X, first, q, spec, rows, n_samples, lie_n, want_moments)
+        _fantasy_tell_once()
+        return self._fantasy_fallback(X, first, q, acq, rows, n_samples, acq_kwargs, lie_n, thompson, replay)
+
+    def _fantasy_base_alpha(self):
+        return float(self.alpha if not np.iterable(self.alpha) else self._alpha)
+
+    def _fantasy_fast(self, X, first, q, spec, rows, n_samples, lie_n, want_moments):
+        """The uncertainty family on the device (bgp_fantasy_*), on a context of its own: the estimator's context and its
+        resident posteriors are left as they are."""
+        import time
+
+        Xt, n = self._X_train_, self._X_train_.shape[0]
+        alpha_diag = np.broadcast_to(np.asarray(self.alpha, dtype=np.float64), (n,)) if not np.iterable(self.alpha) \
+            else np.asarray(self.alpha, dtype=np.float64)
+        H = self._canonical(np.atleast_2d(rows))
+        ctx = _lib.Context(Xt, self.y_train_, alpha_diag, form=self._plan.form, stationary=self._plan.stationary,
+                           max_batch=self._ctx.max_batch, device=self.device)
+        info = {"step_ms": []}
+        try:
+            self._raise_if_not_pd(ctx.posterior(H, want_alpha=False)["status"])
+            Hk = H.copy()
+            Hk[:, -1] = -np.inf
+            noise = self._fantasy_base_alpha() + np.exp(H[:, -1])
+            y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+            t0 = time.perf_counter()
+            ctx.fantasy_begin(Hk, noise, X, y_mean, y_std, [spec[0]], [spec[1]], n_samples, max(q - 1, 1))
+            info["begin_ms"] = (time.perf_counter() - t0) * 1e3
+            picks, values = [int(first)], []
+            for _ in range(q - 1):
+                t0 = time.perf_counter()
+                nxt, vals = ctx.fantasy_step(picks[-1], lie_n, want_values=True)
+                info["step_ms"].append((time.perf_counter() - t0) * 1e3)
+                picks.append(nxt)
+                values.append(vals[0])
+            if want_moments:
+                info["moments"] = ctx.fantasy_moments()
+            info["device"] = ctx.fantasy_stats()
+            t0 = time.perf_counter()
+            ctx.fantasy_end()
+            info["end_ms"] = (time.perf_counter() - t0) * 1e3
+        finally:
+            ctx.close()
+        return picks, np.array(values).reshape(q - 1, X.shape[0]), "fast", info
+
+    def _fantasy_fallback(self, X, first, q, acq, rows, n_samples, acq_kwargs, lie_n, thompson, replay):
+        """Any kernel, warp and acquisition: a scratch copy of the estimator holds the training set plus the chosen
+        points and their lies on a context of its own, and the existing device calls evaluate every step."""
+        import copy
+        import time
+
+        from . import acquisition as A
+
+        scratch = copy.copy(self)  # (__getstate__: no context, no sampler travel)
+        scratch._needs_rebuild = False
+        scratch.kernel_ = copy.deepcopy(self.kernel_)
+        full = isinstance(acq, A.FullGPAcquisition)
+        own = full and type(acq) not in (A.PVRS, A.VarianceReduction)  # a whole-GP acquisition evaluated as itself
+        X0, y0 = self._X_train_, self.y_train_
+        alpha0 = np.asarray(self.alpha, dtype=np.float64) if np.iterable(self.alpha) else None
+        picks, values, info = [int(first)], [], {"step_ms": []}
+        try:
+            mus0 = None
+            if lie_n is None and not (full and not own):
+                # kriging believer: the lie is each GP's own mean, so the conditioned means ARE the unconditioned ones
+                scratch._ensure_context()
+                if own:
+                    scratch.theta = scratch.theta
+                    mus0 = scratch.predict(X)[None, :]
+                else:
+                    mus0, _ = scratch._predict_hyper_samples(rows, X, noise_zero=True)
+            for j in range(1, q):
+                t0 = time.perf_counter()
+                scratch._X_train_ = np.vstack([X0, X[picks]])
+                if own and lie_n is None:  # the median GP's own means at the chosen points, normalised
+                    lies = (mus0[0, picks] - np.ravel(self.y_train_mean_)[0]) / np.ravel(self.y_train_std_)[0]
+                else:  # (PVRS / VR and the variances do not read y)
+                    lies = np.full(j, 0.0 if lie_n is None else lie_n)
+                scratch.y_train_ = np.concatenate([y0, lies])
+                if alpha0 is not None:
+                    extra = np.zeros(j) if full and not own else np.full(j, self._fantasy_base_alpha())
+                    scratch.alpha = np.concatenate([alpha0, extra])
+                scratch._ensure_context()
+                if own:
+                    scratch.theta = scratch.theta  # the median GP's posterior on the augmented set
+                    rng = np.random.RandomState()
+                    rng.set_state(replay)
+                    vals = np.asarray(acq(X, scratch, random_state=rng, **acq_kwargs), dtype=np.float64)
+                    vals = vals if np.all(np.isfinite(vals)) else np.zeros(X.shape[0])
+                elif full:
+                    vals = scratch._pvrs(X, X if thompson is None else thompson, alpha0 is not None)
+                    vals = vals if np.all(np.isfinite(vals)) else np.zeros_like(vals)
+                else:
+                    mus, stds = scratch._predict_hyper_samples(rows, X, noise_zero=True)
+                    vals = A._average_uncertainty(scratch, acq, mus if mus0 is None else mus0, stds, n_samples,
+                                                  acq_kwargs)
+                values.append(vals)
+                v = np.array(vals, copy=True)
+                v[picks] = -np.inf
+                picks.append(int(np.argmax(v)))
+                info["step_ms"].append((time.perf_counter() - t0) * 1e3)
+        finally:
+            if scratch._ctx_obj is not None:
+                scratch._ctx_obj.close()
+                scratch._ctx_obj = None
+        return picks, np.array(values).reshape(q - 1, X.shape[0]), "fallback", info
+
     def _mvn_mode(self, m, mvn=None):
         """'reference' (numpy's SVD draw on the host from the device-built mean / covariance) or 'cholesky' (device)."""
         mode = self.__dict__.get("mvn", "auto") if mvn is None else mvn
@@ -1107,6 +1243,17 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                 ctx.close()
             except Exception:
                 pass
+
+
+_fantasy_told = []
+
+
+def _fantasy_tell_once():
+    """One line on stderr, once per process: a batch proposal conditioned through whole device passes per point."""
+    if not _fantasy_told:
+        _fantasy_told.append(True)
+        print("[bayes_skopt_amd] ask(n_points > 1): fantasy points through the fallback path (one posterior build + "
+              "evaluation per point on an augmented training set)", file=sys.stderr, flush=True)
 
 
 def _with_white_zeroed(kernel):

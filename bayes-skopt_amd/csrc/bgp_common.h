@@ -169,6 +169,7 @@ struct bgp_ctx {
   size_t cap_alpha = 0;
   // resident posterior state
   int post_B = 0;            // number of resident posteriors (0 = none)
+  int post_gen = 0;          // bumped by every posterior build (a fantasy state checks that its posteriors are still there)
   std::vector<double> post_h;
   // scratch for predict / pvrs (grown on demand)
   double* dscratch = nullptr;
@@ -198,6 +199,8 @@ struct bgp_ctx {
   long long ps_calls = 0;       // launch-free calls enqueued by this context (bgp_persist_stats)
   long long ps_timeouts = 0;    // ... of which timed out and were redone by launches
   int pending_warped = 0;       // the pending batch carries per-walker warps (redo path of bgp_lml_batch_wait)
+  struct bgp_fantasy_state* fantasy = nullptr;  // an open batch proposal (bgp_fantasy_begin .. bgp_fantasy_end; bgp_fantasy.hip)
+  long long fant_stats[2] = {0, 0};             // fantasy begins / steps run on this context (bgp_fantasy_stats)
   struct bgp_mcmc_state* mcmc = nullptr;  // an open device-resident sampler run (bgp_mcmc_begin .. bgp_mcmc_end; bgp_mcmc.hip)
   int ps_forbid = 0;            // the device-resident sampler redoes a run after a time-out: launches only, on every rank
   int ps_resident = 0;          // the device-resident sampler is enqueuing: no per-call copy of the error word (its kernels read it)
@@ -367,6 +370,7 @@ int bgp_launch_cholesky_persist(bgp_ctx* ctx, int B, int build_gram);
 int bgp_lml_redo_if_abandoned(bgp_ctx* ctx, int B);
 int bgp_lml_enqueue_dev(bgp_ctx* ctx, int nb, int warped);  // bgp_api.hip: Gram build + factorisation + LML of c->dh[0 .. nb), on the device only
 int bgp_ensure_warp_buffers(bgp_ctx* ctx);                  // bgp_api.hip: the per-walker warp buffers of a warped LML batch exist
+void bgp_fantasy_abandon(bgp_ctx* ctx);  // bgp_fantasy.hip: drop an open batch proposal (context teardown)
 void bgp_mcmc_abandon(bgp_ctx* ctx);  // bgp_mcmc.hip: drop an open sampler run (context teardown, failed calls)
 // the launch-free call of a batch whose results are discarded anyway: forget it (no time-out is counted, nothing is redone)
 static inline void bgp_ps_clear_inflight(bgp_ctx* c) {

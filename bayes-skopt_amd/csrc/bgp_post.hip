@@ -223,6 +223,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
     BGP_HIP(bgp_stream_sync(c->stream));
   }
   c->post_B = B;
+  c->post_gen++;
   return BGP_OK;
 }
 

@@ -32,6 +32,7 @@ ACQUISITION_FUNC = {
 }
 
 _INT32_MAX = np.iinfo(np.int32).max
+BATCH_STRATEGIES = ("cl_min", "cl_mean", "cl_max", "kb")
 
 
 class Optimizer:
@@ -39,6 +40,9 @@ class Optimizer:
     noisei, n_points, n_initial_points_, init_strategy, acq_func, acq_func_kwargs``) and defaults of
     ``bask/optimizer.py:120-175``.  The generator ``rng`` is consumed in the reference's order (initial-design seed,
     surrogate seed; per tell: candidate draw, acquisition seed), so a seeded run visits the same points."""
+
+    _batch_path = "auto"  # "fallback": batch proposals always through the host-driven path (tests compare the two)
+    _batch_moments = False  # True: _last_batch_info carries the fast path's conditioned latent moments (tests)
 
     def __init__(self, dimensions, n_points=500, n_initial_points=10, init_strategy="sb", gp_kernel=None,
                  gp_kwargs=None, gp_priors=None, acq_func="pvrs", acq_func_kwargs=None, random_state=None, **kwargs):
@@ -54,6 +58,8 @@ class Optimizer:
         self._next_x = None
         self._last_candidates = None  # transformed candidates / acquisition values of the latest proposal (tests, plots)
         self._last_acq_values = None
+        self._last_batch_state = None  # what the latest proposal drew (chain rows, Thompson points) for ask(n_points > 1)
+        self._last_batch_info = None   # path taken / step values / device counters of the latest batch (tests, probes)
 
     # ---- construction helpers ------------------------------------------------------------------------------
     def _plan_initial_design(self, n_initial_points, init_strategy):
@@ -78,11 +84,37 @@ class Optimizer:
         return create_result(self.Xi, self.yi, self.space, self.rng, models=[self.gp])
 
     # ---- ask ---------------------------------------------------------------------------------------------------
-    def ask(self, n_points=1):
+    def ask(self, n_points=1, strategy="cl_min"):
         """Next point to evaluate (``bask/optimizer.py:177-226``): a point of the initial design while it lasts, then
-        the maximiser of the acquisition function found by the last ``tell``."""
+        the maximiser of the acquisition function found by the last ``tell``.
+
+        ``n_points > 1`` returns a list of ``n_points`` distinct points (``n_points == 1``: the single point, and
+        ``strategy`` is not looked at):
+
+        * while the initial design lasts, or before any model has been fit, the next ``n_points`` points of the design --
+          "r2": the following design points in the order single ask / tell rounds hand them out; "sb": the sequential
+          Steinerberger extension of the points seen so far; otherwise ``space.rvs(n_points)``.  Slots the design has no
+          points left for are filled with ``space.rvs`` points;
+        * once a model exists, a greedy batch over the candidates of the last proposal: point 1 is ``ask()``; point
+          j + 1 maximises the same acquisition on the same candidates, with the same hyper-posterior rows (PVRS: the same
+          Thompson points), for the GPs conditioned on the training data plus the j chosen points with a fantasy
+          observation ("lie"); points already chosen are excluded.  Hyper-parameters and the y normalisation stay fixed;
+          a fantasy point has the noise a ``tell`` with noise 0 would give it (scalar alpha + the row's white level).
+          ``strategy``: the lie is min / mean / max of ``yi`` ("cl_min" / "cl_mean" / "cl_max"), or each row's own
+          posterior mean ("kb", kriging believer: the means stay, only the variances shrink).  PVRS / VR do not read y,
+          so the strategy does not change their batches.  The averages follow ``evaluate_acquisitions``.  Any other
+          whole-GP acquisition (``FullGPAcquisition``) is called itself on the conditioned median GP, with the
+          generator state the proposal handed it.  ``n_points`` may not exceed the number of candidates.  This does not
+          consume ``rng`` and changes nothing on the optimizer: asking twice gives the same list, and telling the first
+          point alone continues exactly as after ``ask()``.  Sample acquisitions (Thompson sampling, "ts") have no
+          batch form.
+        """
+        if n_points > 1 and strategy not in BATCH_STRATEGIES:
+            raise ValueError(f"strategy must be one of {BATCH_STRATEGIES}, got {strategy!r}")
         if n_points > 1:
-            raise NotImplementedError("Returning multiple points is not implemented yet.")
+            if self._n_initial_points > 0 or not self.gp.kernel_:
+                return self._ask_design(n_points)
+            return self._ask_batch(n_points, strategy)
         if self._n_initial_points <= 0:
             if not self.gp.kernel_:
                 raise RuntimeError("Initialization is finished, but no model has been fit.")
@@ -96,6 +128,44 @@ class Optimizer:
                              existing_points=self.space.transform(self.Xi) if seen else None,
                              random_state=self._init_rng.randint(2**31))
         return self.space.inverse_transform(np.atleast_2d(design[seen]))[0]
+
+    def _ask_design(self, n_points):
+        """The next ``n_points`` points of the initial design, topped up with ``space.rvs`` points."""
+        k = min(max(self._n_initial_points, 0), n_points)
+        points = []
+        if k and self.init_strategy == "r2":
+            points = [self._initial_points[self._n_initial_points - 1 - i] for i in range(k)]
+        elif k and self.init_strategy == "sb":
+            seen = len(self.Xi)
+            design = sb_sequence(n=seen + k, d=self.space.transformed_n_dims,
+                                 existing_points=self.space.transform(self.Xi) if seen else None,
+                                 random_state=self._init_rng.randint(2**31))
+            points = list(self.space.inverse_transform(np.atleast_2d(design[seen:])))
+        elif k:
+            points = list(self.space.rvs(n_samples=k))
+        if len(points) < n_points:
+            points += list(self.space.rvs(n_samples=n_points - len(points)))
+        return points
+
+    def _ask_batch(self, n_points, strategy):
+        """Greedy fantasy batch over the last proposal (``BayesGPR._fantasy_batch``)."""
+        if isinstance(self.acq_func, acquisition.SampleAcquisition):
+            raise NotImplementedError("Batch proposals (n_points > 1) are not implemented for Thompson sampling "
+                                      "or other sample acquisitions.")
+        state = self._last_batch_state
+        if self._last_candidates is None or state is None:
+            raise RuntimeError("No proposal to extend: tell() has not fit a model and proposed a point yet.")
+        cand, values = self._last_candidates, self._last_acq_values
+        if n_points > len(cand):
+            raise ValueError(f"n_points={n_points} exceeds the {len(cand)} candidates of a proposal (Optimizer.n_points)")
+        lie = {"cl_min": np.min, "cl_mean": np.mean, "cl_max": np.max}.get(strategy)
+        lie = None if lie is None else float(lie(self.yi))
+        picks, step_values, path, info = self.gp._fantasy_batch(
+            cand, int(np.argmax(values)), n_points, self.acq_func, state.get("rows"), state.get("n_samples", 0),
+            self.acq_func_kwargs, lie, thompson=state.get("thompson", {}).get(0), replay=state.get("replay", {}).get(0),
+            path=self._batch_path, want_moments=self._batch_moments)
+        self._last_batch_info = dict(info, picks=picks, values=step_values, path=path)
+        return [self.space.inverse_transform(cand[i].reshape((1, -1)))[0] for i in picks]
 
     # ---- tell --------------------------------------------------------------------------------------------------
     def _record(self, x, y, noise_vector):
@@ -137,10 +207,11 @@ class Optimizer:
             cand = self.gp.unwarp(self.rng.uniform(size=(self.n_points, self.space.transformed_n_dims)))
         else:
             cand = self.space.rvs_transformed(n_samples=self.n_points, random_state=self.rng)
+        record = {}
         values = evaluate_acquisitions(X=cand, gpr=self.gp, acquisition_functions=(self.acq_func,), n_samples=n_samples,
-                                       progress=False, random_state=self.rng.randint(0, _INT32_MAX),
+                                       progress=False, random_state=self.rng.randint(0, _INT32_MAX), _record=record,
                                        **self.acq_func_kwargs).ravel()
-        self._last_candidates, self._last_acq_values = cand, values
+        self._last_candidates, self._last_acq_values, self._last_batch_state = cand, values, record
         return self.space.inverse_transform(cand[np.argmax(values)].reshape((1, -1)))[0]
 
     def tell(self, x, y, noise_vector=None, fit=True, replace=False, n_samples=0, gp_samples=100, gp_burnin=10,

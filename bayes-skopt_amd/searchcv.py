@@ -4,7 +4,7 @@
 The reference subclasses ``skopt.BayesSearchCV`` and swaps in its own optimizer (``bask/searchcv.py:292-354``);
 skopt is not part of this image, so the thin layer skopt adds on scikit-learn's ``BaseSearchCV`` is restated
 here: the search spaces are normalised to ``(dict, n_iter)`` pairs, one ``Optimizer`` is made per space
-(dimensions in sorted key order, ``acq_func="pvrs"`` unless given), and every iteration asks one point, lets
+(dimensions in sorted key order, ``acq_func="pvrs"`` unless given), and every iteration asks ``n_points`` points, lets
 scikit-learn cross-validate it (``evaluate_candidates``) and tells the optimizer the negative mean test score
 -- which is where the device hot path runs (``Optimizer.tell`` -> BayesGPR MCMC + acquisition)."""
 import numpy as np
@@ -30,9 +30,10 @@ def point_asdict(search_space, point_as_list):
 class BayesSearchCV(BaseSearchCV):
     """Same constructor as ``bask/searchcv.py:245-290``.  ``search_spaces``: a dict ``{param: dimension}``, a
     list of such dicts, or a list of ``(dict, n_iter)`` pairs; a dimension is a ``space.Real`` / ``Integer`` /
-    ``Categorical`` or anything ``Optimizer(dimensions=...)`` accepts.  ``n_points`` other than 1 and
-    ``return_policy="best_mean"`` behave as in the reference (the former is refused by ``Optimizer.ask``, the
-    latter is stored but the best observed setting is what ``best_params_`` reports)."""
+    ``Categorical`` or anything ``Optimizer(dimensions=...)`` accepts.  ``n_points > 1`` asks that
+    many settings per round (``Optimizer.ask(n_points)``: a fantasy batch) and cross-validates them
+    together, e.g. over ``n_jobs`` workers.  ``return_policy="best_mean"`` is stored but the best observed setting is
+    what ``best_params_`` reports."""
 
     def __init__(self, estimator, search_spaces, optimizer_kwargs=None, n_iter=50, return_policy="best_setting",
                  scoring=None, fit_params=None, n_jobs=1, n_points=1, iid=True, refit=True, cv=None, verbose=0,
@@ -88,7 +89,7 @@ class BayesSearchCV(BaseSearchCV):
 
     def _step(self, search_space, optimizer, evaluate_candidates, n_points=1):
         """One ask / cross-validate / tell round (``bask/searchcv.py:320-354``)."""
-        params = [optimizer.ask(n_points=n_points)]
+        params = optimizer.ask(n_points=n_points) if n_points > 1 else [optimizer.ask(n_points=n_points)]
         params = [[np.array(v).item() for v in p] for p in params]
         params_dict = [point_asdict(search_space, p) for p in params]
         all_results = evaluate_candidates(params_dict)

@@ -195,6 +195,36 @@ int bgp_pvrs(bgp_ctx* ctx, const double* h_kernel, int m, const double* Xcand, i
 int bgp_pvrs_prepare(bgp_ctx* ctx, const double* h_kernel, int has_alpha_vec, int* status);
 
 /*
+ * Batch proposals by fantasy conditioning: Optimizer.ask(n_points > 1) (skopt's "constant liar" / kriging-believer
+ * batches; bask/optimizer.py:177 has the signature and refuses).  The B resident posteriors of the proposal
+ * (bgp_posterior_batch with the draws' h, built first) are conditioned one chosen candidate p at a time on a fantasy
+ * observation, with the hyper-parameters and the y normalisation fixed:
+ *   w_b = K_b^-1 k_b(X, x_p) ;  c_b(i) = k_b(x_i, x_p) - k_b(X, x_i)^T w_b - sum_{l<j} u_{b,l}(i) u_{b,l}(p)
+ *   s_b = c_b(p) + noise[b] ;  u_{b,j} = c_b / sqrt(s_b) ;  var_b -= u_{b,j}^2 ;  mu_b += u_{b,j} (lie_b - mu_b(p)) / sqrt(s_b)
+ * -- the latent predictive moments of the GP whose training set is X plus the chosen points with their lies (each with
+ * noise variance noise[b]: the constructor's scalar alpha + the draw's white level), i.e. what
+ * evaluate_acquisitions (bask/acquisition.py:112-139) would see after tell(chosen, lies) without a refit.
+ * bgp_fantasy_begin: h_kernel (B*(d+2)) as in bgp_acq_batch (white level -inf), noise (B), the m candidates, the
+ *   acquisitions (kinds / params / n_samples as bgp_acq_batch) and qmax < m, the largest number of steps; the starting
+ *   moments are bgp_predict_batch's.  Needs d <= 32 and no context-level warp.
+ * bgp_fantasy_step: condition on candidate p with lie_kind BGP_LIE_VALUE (every draw's lie is lie_value, normalised-y
+ *   units: cl_min / cl_mean / cl_max) or BGP_LIE_KB (each draw's own mean at p: means unchanged); then the closed forms
+ *   and the average over the draws exactly as bgp_acq_batch, and *next = the argmax of acquisition 0 over the candidates
+ *   not chosen so far (np.argmax order).  values (n_acq*m, may be NULL): the averaged values.  BGP_ERR_STATE when the
+ *   resident posteriors have been rebuilt since begin.
+ * bgp_fantasy_moments: the current latent means / variances (B*m each, normalised units).
+ * bgp_fantasy_end: drop the state (bgp_ctx_destroy drops it too).
+ * bgp_fantasy_stats: out[0] = begins, out[1] = steps run on this context.
+ */
+enum { BGP_LIE_VALUE = 0, BGP_LIE_KB = 1 };
+int bgp_fantasy_begin(bgp_ctx* ctx, int B, const double* h_kernel, const double* noise, int m, const double* Xcand,
+                      double y_mean, double y_std, int n_acq, const int* kinds, const double* params, int n_samples, int qmax);
+int bgp_fantasy_step(bgp_ctx* ctx, int p, int lie_kind, double lie_value, int* next, double* values);
+int bgp_fantasy_moments(bgp_ctx* ctx, double* mean, double* var);
+int bgp_fantasy_end(bgp_ctx* ctx);
+int bgp_fantasy_stats(bgp_ctx* ctx, long long* out);
+
+/*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
  * the host (z: n_draws*m), via a Cholesky factor of cov (+jitter) instead of numpy's SVD.
  * Replaces: sklearn sample_y (sklearn/_gpr.py:522-526) reached from BayesGPR.sample_y
