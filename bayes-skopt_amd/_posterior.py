@@ -1,0 +1,260 @@
+"""The two posterior backends of ``BayesGPR``.  ``CanonicalPosterior`` (``kernels.KernelPlan``): the device builds every
+matrix from the canonical vector ``H``.  ``GramPosterior`` (``kernels.GramPlan``): the host evaluates the kernel object, as
+the reference does for every kernel (``sklearn/_gpr.py:582``), and the device factorises, solves, inverts and forms the
+predictive products (``ctx.*_gram``).  Every method takes the estimator and reads ``gp._ctx`` at the call: a backend holds no
+context.  What only the canonical form has -- the resident sampler, the device acquisitions, the fantasy fast path, the
+device ``mvn`` draw, the sharded asynchronous gather -- is behind ``canonical``.  Predictions: normalised-target units."""
+import numpy as np
+from sklearn.base import clone
+
+from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
+
+_PD_MESSAGE = (
+    "The kernel, %s, is not returning a positive definite matrix. Try gradually increasing the "
+    "'alpha' parameter of your GaussianProcessRegressor estimator."
+)
+
+
+def raise_if_not_pd(status, kernel=None):
+    """LinAlgError for the first failed factorisation of a batch of ``status`` words (scikit-learn's message, naming
+    ``kernel``; without it only the leading-minor line, the message PVRS raises)."""
+    status = np.atleast_1d(status)
+    if np.any(status != 0):
+        minor = "%d-th leading minor of the array is not positive definite" % status[np.flatnonzero(status)[0]]
+        raise np.linalg.LinAlgError(*((minor,) if kernel is None else (_PD_MESSAGE % kernel, minor)))
+
+
+def noise_off(H):
+    """A copy of canonical vectors with the white level at -inf: the predictive kernel of ``noise_set_to_zero``."""
+    Hk = H.copy()
+    Hk[:, -1] = -np.inf
+    return Hk
+
+
+class PendingLml:
+    """A block's LML between ``lml_begin`` and ``lml_finish``; ``submitted``: the device is already working on it."""
+
+    def __init__(self, args, submitted=False):
+        self.args, self.submitted = args, submitted
+
+
+class CanonicalPosterior:
+    canonical = True
+
+    def lml(self, gp, T, eval_gradient):
+        """(LML, gradient | None) of every row of the (B, p) block ``T``."""
+        H = gp._canonical(T)
+        if eval_gradient:
+            lml, gh, _ = gp._ctx.lml_grad(H)
+            return lml, gp._plan.grad_to_theta(gh, gp._X_train_.shape[1])
+        return gp._ctx.lml(H), None
+
+    def lml_begin(self, gp, T, W):
+        """Put the block's LML batch on the device (``W``: per-row input warps) and return at once."""
+        H = gp._canonical(T)
+        if W is None:
+            return PendingLml((H, None), gp._ctx.lml_submit(H))
+        W = np.ascontiguousarray(W)
+        return PendingLml((H, W), gp._ctx.lml_warped_submit(H, W))
+
+    def lml_finish(self, gp, pending):
+        if pending.submitted:
+            return gp._ctx.lml_wait()
+        H, W = pending.args
+        return gp._ctx.lml(H) if W is None else gp._ctx.lml_warped(H, W)
+
+    def posterior(self, gp, theta):
+        """Build the resident posterior at ``theta``; returns alpha."""
+        res = gp._ctx.posterior(gp._canonical(theta), want_L=False, want_alpha=True, want_K_inv=False)
+        raise_if_not_pd(res["status"], gp.kernel_)
+        return res["alpha"][0]
+
+    def factor(self, gp, which):
+        """``L`` or ``K_inv`` of the posterior at ``gp._post_theta``."""
+        res = gp._ctx.posterior(gp._canonical(gp._post_theta), want_L=(which == "L"), want_alpha=False,
+                                want_K_inv=(which == "K_inv"))
+        return res[which][0]
+
+    def make_resident(self, gp):
+        H = gp._canonical(gp._post_theta)
+        res = gp._ctx.resident_H
+        if res is None or res.shape[0] < 1 or not np.array_equal(res[0], H[0]):
+            gp._ctx.posterior(H, want_alpha=False)
+
+    def build_rows(self, gp, thetas):
+        """One batched posterior build for a set of chain rows (every row, repeated ones too); returns their H."""
+        H = gp._canonical(np.atleast_2d(thetas))
+        raise_if_not_pd(gp._ctx.posterior(H, want_alpha=False)["status"], gp.kernel_)
+        return H
+
+    def predict(self, gp, X, return_cov):
+        """(mean, var, cov | None) of the resident posterior, with the kernel parameters currently in ``kernel_``."""
+        self.make_resident(gp)
+        out = gp._ctx.predict(gp._canonical(gp._kernel_theta_for_predict()), X, return_cov=return_cov)
+        return out if return_cov else (*out, None)
+
+    def rows_predict(self, gp, thetas, X, noise_zero, return_cov=False):
+        """One batched build over the distinct rows of ``thetas`` + one batched predict, scattered back to the rows."""
+        uniq, inverse = np.unique(gp._canonical(thetas), axis=0, return_inverse=True)
+        raise_if_not_pd(gp._ctx.posterior(uniq, want_alpha=False)["status"], gp.kernel_)
+        out = gp._ctx.predict(noise_off(uniq) if noise_zero else uniq, X, return_cov=return_cov)
+        inverse = np.asarray(inverse).ravel()
+        return out[0][inverse], out[1][inverse], (out[2][inverse] if return_cov else None)
+
+    def hyper_predict(self, gp, thetas, X, noise_zero):
+        """(mean, var) of every hyper-posterior draw: one build over all rows, one predict."""
+        H = self.build_rows(gp, thetas)
+        return gp._ctx.predict(noise_off(H) if noise_zero else H, X)
+
+    def grad_x(self, gp, x, Xt):
+        """(d k(x, X_i) / dx as (n, d), k(x, X_i)) at one (warped) query point, in closed form from H."""
+        hk = gp._canonical(gp._kernel_theta_for_predict())[0]
+        d = Xt.shape[1]
+        ell2 = np.exp(2.0 * hk[1 : d + 1])
+        diff = x[None, :] - Xt                       # (n, d)
+        r = np.sqrt(np.sum(diff * diff / ell2, axis=1))
+        stat = gp._plan.stationary
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if stat == "rbf":
+                S = np.exp(-0.5 * r * r)
+                fac = -S
+            elif stat == "matern12":
+                S = np.exp(-r)
+                fac = np.where(r > 0, -S / r, 0.0)
+            elif stat == "matern32":
+                e = np.exp(-np.sqrt(3.0) * r)
+                S = (1.0 + np.sqrt(3.0) * r) * e
+                fac = -3.0 * e
+            else:
+                e = np.exp(-np.sqrt(5.0) * r)
+                S = (1.0 + np.sqrt(5.0) * r + 5.0 / 3.0 * r * r) * e
+                fac = -(5.0 / 3.0) * (1.0 + np.sqrt(5.0) * r) * e
+        cst = np.exp(hk[0])
+        product = gp._plan.form == "product"
+        grad = (cst if product else 1.0) * fac[:, None] * diff / ell2  # (Constant / White terms: zero)
+        return grad, (cst * S if product else cst + S)
+
+    def pvrs(self, gp, X, T, has_alpha_vec):
+        Hk = gp._canonical(gp._kernel_theta_for_predict())
+        raise_if_not_pd(gp._ctx.pvrs_prepare(Hk, has_alpha_vec))
+        return gp._ctx.pvrs(Hk, X, T)
+
+
+class GramPosterior:
+    canonical = False
+
+    def __init__(self):
+        self._resident = None  # theta whose posterior the device holds (every posterior_gram overwrites it)
+
+    def _posterior_gram(self, gp, K, theta=None, **want):
+        self._resident = None
+        res = gp._ctx.posterior_gram(K, **want)
+        self._resident = None if theta is None else np.array(theta, copy=True)
+        return res
+
+    def lml(self, gp, T, eval_gradient):
+        """``sklearn/_gpr.py:579-647``: ``K, K_gradient = kernel(X, eval_gradient=True)`` on the host; factorisation, alpha,
+        K^-1 and the LML on the device; the contraction ``1/2 sum_ij (alpha_i alpha_j - K^-1_ij) dK_ij/dtheta_k`` of the
+        host-evaluated gradient tensor with them (``:615-647``)."""
+        if not eval_gradient:
+            return gp._gram_lml(T), None
+        vals, grads = np.empty(len(T)), np.empty(T.shape)
+        for i, t in enumerate(T):
+            K, Kg = gp._kernel_at(t)(gp.X_train_, eval_gradient=True)
+            res = self._posterior_gram(gp, K, want_alpha=True, want_K_inv=True)
+            if res["status"][0] != 0:
+                vals[i], grads[i] = -np.inf, 0.0
+                continue
+            a, Ki = res["alpha"][0], res["K_inv"][0]
+            vals[i] = res["lml"][0]
+            grads[i] = 0.5 * (np.einsum("i,ijk,j->k", a, Kg, a) - np.einsum("ij,ijk->k", Ki, Kg))
+        return vals, grads
+
+    def lml_begin(self, gp, T, W):
+        return PendingLml((T, W))  # host kernel matrices: nothing to overlap the priors with
+
+    def lml_finish(self, gp, pending):
+        return gp._gram_lml(*pending.args)
+
+    def posterior(self, gp, theta):
+        res = self._posterior_gram(gp, gp._gram_stack(theta), theta, want_alpha=True)
+        raise_if_not_pd(res["status"], gp.kernel_)
+        return res["alpha"][0]
+
+    def factor(self, gp, which):
+        res = self._posterior_gram(gp, gp._gram_stack(gp._post_theta), gp._post_theta, want_L=(which == "L"),
+                                   want_alpha=False, want_K_inv=(which == "K_inv"))
+        return res[which][0]
+
+    def make_resident(self, gp):
+        if self._resident is None or not np.array_equal(self._resident, gp._post_theta):
+            self._posterior_gram(gp, gp._gram_stack(gp._post_theta), gp._post_theta, want_alpha=False)
+
+    def predict(self, gp, X, return_cov):
+        return self.rows_predict(gp, None, X, noise_zero=False, return_cov=return_cov)
+
+    def rows_predict(self, gp, thetas, X, noise_zero, return_cov=False):
+        """The kernel object on the host (training matrix, cross covariances, prior variances), the rest on the device.
+        ``thetas=None``: the resident posterior with ``kernel_`` as it is."""
+        Xw = gp.warp(X) if gp.warp_inputs else X  # BayesGPR.predict warps the query points (bask/bayesgpr.py:630-632)
+        Xt = gp.X_train_
+        if thetas is None:
+            self.make_resident(gp)
+            kernels = [gp.kernel_]
+        else:
+            thetas = np.atleast_2d(thetas)
+            res = self._posterior_gram(gp, gp._gram_stack(thetas, Xt), want_alpha=False)
+            raise_if_not_pd(res["status"], gp.kernel_)
+            kernels = [gp._kernel_at(t) for t in thetas]
+        if noise_zero:
+            kernels = [_with_white_zeroed(k) for k in kernels]
+        Ks = np.stack([k(Xw, Xt) for k in kernels])
+        kss = np.stack([k.diag(Xw) for k in kernels])
+        Kss = np.stack([k(Xw) for k in kernels]) if return_cov else None
+        out = gp._ctx.predict_gram(Ks, kss, Kss)
+        return out[0], out[1], (out[2] if return_cov else None)
+
+    def hyper_predict(self, gp, thetas, X, noise_zero):
+        return self.rows_predict(gp, thetas, X, noise_zero)[:2]
+
+    def grad_x(self, gp, x, Xt):
+        """``kernel_.gradient_x`` is ``kernels.gradient_x`` (skopt's method restated for scikit-learn kernel objects)."""
+        return gradient_x(gp.kernel_, x, Xt), gp.kernel_(x[None, :], Xt)[0]
+
+    def pvrs(self, gp, X, T, has_alpha_vec):
+        """PVRS through the bordered-inverse identity of ``bgp_pvrs``,
+        ``covs_i = sum_t [k_t^T K^-1 k_t + (k(x_t, x_i) - k_i^T K^-1 k_t)^2 / (kappa_i - k_i^T K^-1 k_i)]``, every term read off
+        ONE device predictive covariance ``C = K_** - K_* K^-1 K_*^T`` over [Thompson points; candidates] per candidate chunk:
+        ``C_ti``, ``C_ii`` and ``k_t^T K^-1 k_t = kappa_t - C_tt``.  K carries alpha only when it is a vector (reference quirk,
+        ``bask/acquisition.py:332-333``); the kernel matrices come from the host-evaluated ``kernel_``."""
+        k = gp.kernel_
+        Xt = gp.X_train_
+        res = self._posterior_gram(gp, k(Xt)[None], use_alpha=bool(has_alpha_vec), want_alpha=False)
+        raise_if_not_pd(res["status"], k)
+        if gp.warp_inputs:
+            X, T = gp.warp(X), gp.warp(T)
+        nt = T.shape[0]
+        covs = np.empty(X.shape[0])
+        step = max(1, 2048 - nt)
+        for lo in range(0, X.shape[0], step):
+            Q = np.vstack([T, X[lo : lo + step]])
+            kss = k.diag(Q)
+            C = gp._ctx.predict_gram(k(Q, Xt)[None], kss[None], k(Q)[None])[2][0]
+            tt = kss[:nt] - np.diag(C)[:nt]
+            cross = C[:nt, nt:]
+            cii = np.diag(C)[nt:]
+            covs[lo : lo + step] = tt.sum() + np.sum(cross * cross / cii[None, :], axis=0)
+        return covs
+
+
+def _with_white_zeroed(kernel):
+    """A copy of ``kernel`` with its WhiteKernel (inside nested sums) at level 0: what ``noise_set_to_zero`` does to
+    ``kernel_`` (``bask/bayesgpr.py:327-333``)."""
+    k = clone(kernel)
+    if isinstance(k, WhiteKernel):
+        k.set_params(noise_level=0.0)
+        return k
+    present, white_param = param_for_white_kernel_in_sum(k)
+    if present:
+        k.set_params(**{white_param: WhiteKernel(noise_level=0.0)})
+    return k

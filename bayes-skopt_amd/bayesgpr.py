@@ -26,17 +26,13 @@ from sklearn.base import BaseEstimator, RegressorMixin, clone
 from sklearn.utils import check_random_state
 
 from . import _lib, distributed
+from ._posterior import CanonicalPosterior, GramPosterior, noise_off, raise_if_not_pd
 from .kernels import ConstantKernel, WhiteKernel, analyse_kernel, param_for_white_kernel_in_sum
 from .kernels import RBF as _RBF
 from .sampler import EnsembleSampler
 from .utils import geometric_median, guess_priors, validate_zeroone
 
 __all__ = ["BayesGPR"]
-
-_PD_MESSAGE = (
-    "The kernel, %s, is not returning a positive definite matrix. Try gradually increasing the "
-    "'alpha' parameter of your GaussianProcessRegressor estimator."
-)
 
 
 class BayesGPR(RegressorMixin, BaseEstimator):
@@ -114,6 +110,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         self._ctx_obj = None  # device context (ctypes handle; never pickled, rebuilt on demand)
         self._needs_rebuild = False
         self._plan = None
+        self._backend = None  # _posterior.CanonicalPosterior | GramPosterior, chosen with the context
         self._post_theta = None  # theta the resident posterior (L_, alpha_, K_inv_) was built with
         self._L = self._K_inv = None
         self.alpha_ = None
@@ -138,6 +135,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         state = dict(self.__dict__)
         state["_ctx_obj"] = None
         state["_sampler"] = None  # holds the bound (possibly rank-sharded) log-probability
+        state["_backend"] = None  # (what it knows of the device does not travel: rebuilt with the context)
         state["_needs_rebuild"] = getattr(self, "_X_train_", None) is not None and self.kernel_ is not None
         return state
 
@@ -147,12 +145,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
     def _ensure_context(self, batch_hint=None):
         """(Re)create / update the device context for the current training set."""
         X, y = self._X_train_, self.y_train_
-        n = X.shape[0]
-        alpha_diag = np.broadcast_to(np.asarray(self.alpha, dtype=np.float64), (n,)) if not np.iterable(self.alpha) \
-            else np.asarray(self.alpha, dtype=np.float64)
-        if alpha_diag.shape[0] != n:
-            raise ValueError(f"alpha must be a scalar or an array with same number of entries as y. "
-                             f"({alpha_diag.shape[0]} != {n})")
+        alpha_diag = self._alpha_diag()
         plan = analyse_kernel(self.kernel_)
         want_batch = int(self.max_batch or batch_hint or getattr(self, "_batch_wish", None) or 64)
         ctx = self._ctx_obj
@@ -165,10 +158,26 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         else:
             ctx.update_data(X, y, alpha_diag)
         self._ctx, self._plan = ctx, plan
+        self._backend = GramPosterior() if plan.generic else CanonicalPosterior()
         self._post_theta = None
         self._L = self._K_inv = None
         self._install_warp()
         return ctx
+
+    def _alpha_diag(self):
+        """The diagonal the device adds to K: ``alpha`` broadcast over the training points."""
+        n = self._X_train_.shape[0]
+        a = np.asarray(self.alpha, dtype=np.float64)
+        a = a if np.iterable(self.alpha) else np.broadcast_to(a, (n,))
+        if a.shape[0] != n:
+            raise ValueError(f"alpha must be a scalar or an array with same number of entries as y. ({a.shape[0]} != {n})")
+        return a
+
+    @property
+    def _post(self):
+        """The posterior backend of the kernel (after an unpickle: rebuilt with the context first)."""
+        self._ctx  # noqa: B018
+        return self._backend
 
     def _warp_vector(self):
         """[wa_1..wa_d, wb_1..wb_d] of the current warpers, or None (identity)."""
@@ -187,8 +196,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
     def _canonical(self, theta):
         return self._plan.canonical(theta, self._X_train_.shape[1])
 
-    # ---- generic kernel expression trees (kernels.GramPlan): the host evaluates the kernel object, as the reference does for
-    # every kernel (sklearn/_gpr.py:582); the device factorises, solves, inverts and forms the predictive products
+    # ---- generic kernel expression trees (kernels.GramPlan; _posterior.GramPosterior): the kernel object on the host
     @property
     def _generic(self):
         return self._plan is not None and self._plan.generic
@@ -219,39 +227,10 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                 raise ValueError("Gradient can only be evaluated for theta!=None")
             return self.log_marginal_likelihood_value_
         theta = np.asarray(theta, dtype=np.float64)
-        single = theta.ndim == 1
-        if self._generic:
-            return self._gram_lml_and_grad(theta, eval_gradient)
-        H = self._canonical(theta)
-        if eval_gradient:
-            lml, gh, _ = self._ctx.lml_grad(H)
-            g = self._plan.grad_to_theta(gh, self._X_train_.shape[1])
-            return (float(lml[0]), g[0]) if single else (lml, g)
-        lml = self._ctx.lml(H)
-        return float(lml[0]) if single else lml
-
-    def _gram_lml_and_grad(self, theta, eval_gradient):
-        """``sklearn/_gpr.py:579-647`` for a generic tree: ``K, K_gradient = kernel(X, eval_gradient=True)`` on the host;
-        factorisation, alpha, K^-1 and the LML on the device; the contraction ``1/2 sum_ij (alpha_i alpha_j - K^-1_ij)
-        dK_ij/dtheta_k`` of the host-evaluated gradient tensor with them (``:615-647``)."""
-        single = theta.ndim == 1
-        T = np.atleast_2d(theta)
-        if not eval_gradient:
-            lml = self._gram_lml(T)
-            return float(lml[0]) if single else lml
-        X = self.X_train_
-        vals, grads = np.empty(len(T)), np.empty((len(T), T.shape[1]))
-        self._gram_resident = None  # (posterior_gram below overwrites the device-resident K^-1 / alpha of theta)
-        for i, t in enumerate(T):
-            K, Kg = self._kernel_at(t)(X, eval_gradient=True)
-            res = self._ctx.posterior_gram(K, want_alpha=True, want_K_inv=True)
-            if res["status"][0] != 0:
-                vals[i], grads[i] = -np.inf, 0.0
-                continue
-            a, Ki = res["alpha"][0], res["K_inv"][0]
-            vals[i] = res["lml"][0]
-            grads[i] = 0.5 * (np.einsum("i,ijk,j->k", a, Kg, a) - np.einsum("ij,ijk->k", Ki, Kg))
-        return (float(vals[0]), grads[0]) if single else (vals, grads)
+        lml, grad = self._post.lml(self, np.atleast_2d(theta), eval_gradient)
+        if theta.ndim == 1:
+            return (float(lml[0]), grad[0]) if eval_gradient else float(lml[0])
+        return (lml, grad) if eval_gradient else lml
 
     # ------------------------------------------------------------------ theta / posterior
     @property
@@ -271,31 +250,14 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         self._build_posterior(theta)
 
     def _build_posterior(self, theta):
-        if self._generic:
-            res = self._ctx.posterior_gram(self._gram_stack(theta), want_alpha=True)
-        else:
-            res = self._ctx.posterior(self._canonical(theta), want_L=False, want_alpha=True, want_K_inv=False)
-        if res["status"][0] != 0:
-            raise np.linalg.LinAlgError(
-                _PD_MESSAGE % self.kernel_,
-                "%d-th leading minor of the array is not positive definite" % res["status"][0],
-            )
-        self.alpha_ = res["alpha"][0]
+        self.alpha_ = self._post.posterior(self, theta)
         self._post_theta = np.array(theta, copy=True)
-        self._gram_resident = np.array(theta, copy=True) if self._generic else None
         self._L = self._K_inv = None
 
     def _fetch_factor(self, which):
         if self._post_theta is None:
             raise AttributeError("no posterior has been built yet")
-        if self._generic:
-            res = self._ctx.posterior_gram(self._gram_stack(self._post_theta), want_L=(which == "L"), want_alpha=False,
-                                           want_K_inv=(which == "K_inv"))
-            self._gram_resident = np.array(self._post_theta, copy=True)
-            return res[which][0]
-        res = self._ctx.posterior(self._canonical(self._post_theta), want_L=(which == "L"), want_alpha=False,
-                                  want_K_inv=(which == "K_inv"))
-        return res[which][0]
+        return self._post.factor(self, which)
 
     @property
     def L_(self):
@@ -406,42 +368,22 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         """First half of ``_log_prob_batch``: put the block's LML batch on the device and return at once with the
         priors of the same block (evaluated while the device factorises)."""
         Theta = np.atleast_2d(Theta)
-        if self._generic:  # host kernel matrices: nothing to overlap the priors with
-            d = self._X_train_.shape[1] if self.warp_inputs else 0
-            Tgp, W = (Theta[:, : Theta.shape[1] - 2 * d], Theta[:, Theta.shape[1] - 2 * d :]) if d else (Theta, None)
-            lp = _eval_priors(priors, Tgp)
-            if W is not None:
-                lp = lp + _eval_warp_priors(warp_priors, W, d)
-            return lp, ("gram", Tgp, W), False
-        if self.warp_inputs:
-            d = self._X_train_.shape[1]
-            Tgp, W = Theta[:, : Theta.shape[1] - 2 * d], Theta[:, Theta.shape[1] - 2 * d :]
-            H = (self._canonical(Tgp), np.ascontiguousarray(W))
-            submitted = self._ctx.lml_warped_submit(*H)
-        else:
-            Tgp, W, d = Theta, None, 0
-            H = self._canonical(Theta)
-            submitted = self._ctx.lml_submit(H)
+        d = self._X_train_.shape[1] if self.warp_inputs else 0
+        Tgp, W = (Theta[:, : Theta.shape[1] - 2 * d], Theta[:, Theta.shape[1] - 2 * d :]) if d else (Theta, None)
+        pending = self._post.lml_begin(self, Tgp, W)
         try:
             lp = _eval_priors(priors, Tgp)
             if W is not None:
                 lp = lp + _eval_warp_priors(warp_priors, W, d)
         except BaseException:
-            if submitted:
+            if pending.submitted:
                 self._ctx.lml_wait()
             raise
-        return lp, H, submitted
+        return lp, pending
 
     def _log_prob_finish(self, token):
-        lp, H, submitted = token
-        if submitted:
-            lml = self._ctx.lml_wait()
-        elif isinstance(H, tuple) and len(H) == 3 and isinstance(H[0], str):
-            lml = self._gram_lml(H[1], H[2])
-        elif self.warp_inputs:
-            lml = self._ctx.lml_warped(*H)
-        else:
-            lml = self._ctx.lml(H)
+        lp, pending = token
+        lml = self._post.lml_finish(self, pending)
         with np.errstate(invalid="ignore"):
             lp = lp + lml
         lp[~np.isfinite(lp)] = -np.inf
@@ -693,37 +635,19 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             validate_zeroone(X)  # the device warps the query points with the context-level warp
         if self._post_theta is None or getattr(self, "_X_train_", None) is None:
             raise RuntimeError("predict before fit is not supported on the MI355X path")
-        if self._generic:
-            mean, var, cov = self._rows_predict(None, X, noise_zero=False, return_cov=return_cov)
-            y_mean = self.y_train_std_ * mean[0] + self.y_train_mean_
-            if return_cov:
-                return y_mean, cov[0] * self.y_train_std_**2
-            y_std = np.sqrt(var[0] * self.y_train_std_**2)
-            if return_mean_grad:
-                grad_mean, grad_std = self._predict_gradients_generic(X[0], y_std, return_std_grad)
-                if return_std_grad:
-                    return y_mean, y_std, grad_mean, grad_std
-                return (y_mean, y_std, grad_mean) if return_std else (y_mean, grad_mean)
-            return (y_mean, y_std) if return_std else y_mean
-        self._make_resident()
-        Hk = self._canonical(self._kernel_theta_for_predict())
-        if return_cov:
-            mean, var, cov = self._ctx.predict(Hk, X, return_cov=True)
-            y_mean = self.y_train_std_ * mean[0] + self.y_train_mean_
-            return y_mean, cov[0] * self.y_train_std_**2
-        mean, var = self._ctx.predict(Hk, X)
+        mean, var, cov = self._post.predict(self, X, return_cov)
         y_mean = self.y_train_std_ * mean[0] + self.y_train_mean_
+        if return_cov:
+            return y_mean, cov[0] * self.y_train_std_**2
         y_std = np.sqrt(var[0] * self.y_train_std_**2)
         if return_mean_grad:
-            grad_mean, grad_std = self._predict_gradients(X[0], Hk[0], y_std, return_std_grad)
+            grad_mean, grad_std = self._predict_gradients(X[0], y_std, return_std_grad)
             if return_std_grad:
                 return y_mean, y_std, grad_mean, grad_std
             return (y_mean, y_std, grad_mean) if return_std else (y_mean, grad_mean)
-        if return_std:
-            return y_mean, y_std
-        return y_mean
+        return (y_mean, y_std) if return_std else y_mean
 
-    def _predict_gradients(self, x, hk, y_std, want_std_grad):
+    def _predict_gradients(self, x, y_std, want_std_grad):
         """Gradients of the predictive mean / std at ONE query point (skopt's
         ``GaussianProcessRegressor.predict(return_mean_grad, return_std_grad)``, the routine
         ``bask/bayesgpr.py:633`` forwards to): ``grad = kernel_.gradient_x(x, X_train_)`` (n, d),
@@ -733,208 +657,64 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         Xt = self.X_train_
         if self.warp_inputs:
             x = self.warp(x[None, :])[0]
-        d = Xt.shape[1]
-        ell2 = np.exp(2.0 * hk[1 : d + 1])
-        diff = x[None, :] - Xt                       # (n, d)
-        r = np.sqrt(np.sum(diff * diff / ell2, axis=1))
-        stat = self._plan.stationary
-        with np.errstate(divide="ignore", invalid="ignore"):
-            if stat == "rbf":
-                S = np.exp(-0.5 * r * r)
-                fac = -S
-            elif stat == "matern12":
-                S = np.exp(-r)
-                fac = np.where(r > 0, -S / r, 0.0)
-            elif stat == "matern32":
-                e = np.exp(-np.sqrt(3.0) * r)
-                S = (1.0 + np.sqrt(3.0) * r) * e
-                fac = -3.0 * e
-            else:
-                e = np.exp(-np.sqrt(5.0) * r)
-                S = (1.0 + np.sqrt(5.0) * r + 5.0 / 3.0 * r * r) * e
-                fac = -(5.0 / 3.0) * (1.0 + np.sqrt(5.0) * r) * e
-        cst = np.exp(hk[0])
-        scale = cst if self._plan.form == "product" else 1.0
-        grad = scale * fac[:, None] * diff / ell2     # d k(x, X_i) / d x   (Constant / White terms: zero)
-        grad_mean = (grad.T @ self.alpha_) * self.y_train_std_
-        if not want_std_grad:
-            return grad_mean, None
-        grad_std = np.zeros(d)
-        if not np.allclose(y_std, 0.0):
-            k_trans = cst * S if self._plan.form == "product" else cst + S
-            grad_std = -(k_trans @ (self.K_inv_ @ grad)) / y_std[0] * self.y_train_std_**2
-        return grad_mean, grad_std
-
-    def _predict_gradients_generic(self, x, y_std, want_std_grad):
-        """The same two gradients for a generic kernel tree: ``kernel_.gradient_x`` is ``kernels.gradient_x`` (skopt's method
-        restated for scikit-learn kernel objects), ``K_*`` comes from the host-evaluated kernel object, ``alpha_`` / ``K_inv_``
-        from the device (``bgp_posterior_batch_gram``)."""
-        from .kernels import gradient_x
-
-        Xt = self.X_train_
-        if self.warp_inputs:
-            x = self.warp(x[None, :])[0]
-        grad = gradient_x(self.kernel_, x, Xt)
+        grad, k_trans = self._post.grad_x(self, x, Xt)
         grad_mean = (grad.T @ self.alpha_) * self.y_train_std_
         if not want_std_grad:
             return grad_mean, None
         grad_std = np.zeros(Xt.shape[1])
         if not np.allclose(y_std, 0.0):
-            k_trans = self.kernel_(x[None, :], Xt)[0]
             grad_std = -(k_trans @ (self.K_inv_ @ grad)) / y_std[0] * self.y_train_std_**2
         return grad_mean, grad_std
 
-    def _make_resident(self):
-        """Make sure the device holds the posterior that alpha_/L_/K_inv_ describe."""
-        if self._generic:
-            if getattr(self, "_gram_resident", None) is None or not np.array_equal(self._gram_resident, self._post_theta):
-                self._ctx.posterior_gram(self._gram_stack(self._post_theta), want_alpha=False)
-                self._gram_resident = np.array(self._post_theta, copy=True)
-            return
-        H = self._canonical(self._post_theta)
-        res = self._ctx.resident_H
-        if res is None or res.shape[0] < 1 or not np.array_equal(res[0], H[0]):
-            self._ctx.posterior(H, want_alpha=False)
+    @contextmanager
+    def _row_warps(self):
+        """Yields ``install(row)``, which gives the estimator chain row ``row``'s own input warp (its own training inputs)
+        and returns the row's kernel parameters as a (1, p) block; the current warpers are back on exit, however it is left
+        (``bask/acquisition.py:142-145``)."""
+        n_theta, d = len(self.kernel_.theta), self._X_train_.shape[1]
+        backup = (np.copy(self.warp_alphas_), np.copy(self.warp_betas_))
+
+        def install(row):
+            self.create_warpers(row[n_theta : n_theta + d], row[n_theta + d :])
+            self.rewarp()
+            return row[None, :n_theta]
+
+        try:
+            yield install
+        finally:
+            self.create_warpers(*backup)
+            self.rewarp()
 
     def _predict_hyper_samples(self, thetas, X, noise_zero=True):
         """Posterior build + predict for a whole batch of hyper-posterior draws (what
         ``evaluate_acquisitions`` does one ``gpr.theta = chain_[i]`` at a time,
-        ``bask/acquisition.py:112-125``): ONE batched device build, ONE batched predict."""
+        ``bask/acquisition.py:112-125``): ONE batched device build, ONE batched predict.  With input warping every draw
+        carries its own warp, i.e. its own training inputs: one build + predict per draw (``:113-119``)."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        rows = np.atleast_2d(thetas)
         if self.warp_inputs:
-            return self._predict_hyper_samples_warped(np.atleast_2d(thetas), X, noise_zero)
-        if self._generic:
-            mean, var, _ = self._rows_predict(np.atleast_2d(thetas), X, noise_zero)
-            return self.y_train_std_ * mean + self.y_train_mean_, np.sqrt(var * self.y_train_std_**2)
-        Hk = self._build_hyper_samples(thetas).copy()
-        if noise_zero:
-            Hk[:, -1] = -np.inf
-        mean, var = self._ctx.predict(Hk, X)
-        mu = self.y_train_std_ * mean + self.y_train_mean_
-        return mu, np.sqrt(var * self.y_train_std_**2)
-
-    def _rows_predict(self, thetas, X, noise_zero, return_cov=False):
-        """Posterior build + predict for the GP of every row of ``thetas`` under the CURRENT warpers, in the units of the
-        normalised targets: (mean, var, cov | None), each with a leading row axis.  ``thetas=None``: the resident posterior
-        of ``theta`` with the kernel parameters currently in ``kernel_`` (what ``predict`` needs).  Canonical kernels: one
-        batched device build over the distinct rows + one batched device predict.  Generic trees: the kernel object is
-        evaluated on the host (training matrix, cross covariances, prior variances), everything else on the device."""
-        if not self._generic:
-            H = self._canonical(thetas)
-            uniq, inverse = np.unique(H, axis=0, return_inverse=True)
-            res = self._ctx.posterior(uniq, want_alpha=False)
-            self._raise_if_not_pd(res["status"])
-            Hk = uniq.copy()
-            if noise_zero:
-                Hk[:, -1] = -np.inf
-            out = self._ctx.predict(Hk, X, return_cov=return_cov)
-            inverse = np.asarray(inverse).ravel()
-            return out[0][inverse], out[1][inverse], (out[2][inverse] if return_cov else None)
-        Xw = self.warp(X) if self.warp_inputs else X  # BayesGPR.predict warps the query points (bask/bayesgpr.py:630-632)
-        Xt = self.X_train_
-        if thetas is None:
-            self._make_resident()
-            kernels = [self.kernel_]
+            validate_zeroone(X)
+            mean, var = np.empty((len(rows), X.shape[0])), np.empty((len(rows), X.shape[0]))
+            with self._row_warps() as install:
+                for i, row in enumerate(rows):
+                    m, v, _ = self._post.rows_predict(self, install(row), X, noise_zero)
+                    mean[i], var[i] = m[0], v[0]
         else:
-            thetas = np.atleast_2d(thetas)
-            self._gram_resident = None
-            res = self._ctx.posterior_gram(self._gram_stack(thetas, Xt), want_alpha=False)
-            self._raise_if_not_pd(res["status"])
-            kernels = [self._kernel_at(t) for t in thetas]
-        if noise_zero:
-            kernels = [_with_white_zeroed(k) for k in kernels]
-        Ks = np.stack([k(Xw, Xt) for k in kernels])
-        kss = np.stack([k.diag(Xw) for k in kernels])
-        Kss = np.stack([k(Xw) for k in kernels]) if return_cov else None
-        out = self._ctx.predict_gram(Ks, kss, Kss)
-        return out[0], out[1], (out[2] if return_cov else None)
-
-    def _raise_if_not_pd(self, status):
-        if np.any(status != 0):
-            bad = int(np.flatnonzero(status)[0])
-            raise np.linalg.LinAlgError(
-                _PD_MESSAGE % self.kernel_,
-                "%d-th leading minor of the array is not positive definite" % status[bad],
-            )
-
-    def _build_hyper_samples(self, thetas):
-        """One batched device posterior build for a set of chain rows; returns the canonical hyper-parameters."""
-        H = self._canonical(np.atleast_2d(thetas))
-        res = self._ctx.posterior(H, want_alpha=False)
-        if np.any(res["status"] != 0):
-            b = int(np.flatnonzero(res["status"])[0])
-            raise np.linalg.LinAlgError(
-                _PD_MESSAGE % self.kernel_,
-                "%d-th leading minor of the array is not positive definite" % res["status"][b],
-            )
-        return H
+            mean, var = self._post.hyper_predict(self, rows, X, noise_zero)
+        return self.y_train_std_ * mean + self.y_train_mean_, np.sqrt(var * self.y_train_std_**2)
 
     def _acq_hyper_samples(self, thetas, X, kinds, params, n_samples, noise_zero=True):
         """Closed-form acquisition values averaged over a batch of hyper-posterior draws, entirely on the device:
         batched posterior build, batched predict and the acquisition / averaging pass of
         ``evaluate_acquisitions`` (``bask/acquisition.py:112-139``) -- only (len(kinds), m) numbers come back."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        Hk = self._build_hyper_samples(thetas).copy()
-        if noise_zero:
-            Hk[:, -1] = -np.inf
+        H = self._post.build_rows(self, thetas)
         y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
-        return self._ctx.acq(Hk, X, y_mean, y_std, kinds, params, n_samples)
-
-    def _predict_hyper_samples_warped(self, rows, X, noise_zero):
-        """With input warping every hyper-posterior draw carries its own warp, i.e. its own training
-        inputs: one posterior build + predict per draw (``bask/acquisition.py:113-119``), all on the
-        device; the warpers are restored afterwards (``:142-145``)."""
-        validate_zeroone(X)
-        n_theta = len(self.kernel_.theta)
-        d = self._X_train_.shape[1]
-        backup = (np.copy(self.warp_alphas_), np.copy(self.warp_betas_))
-        mus, stds = [], []
-        for row in rows:
-            self.create_warpers(row[n_theta : n_theta + d], row[n_theta + d :])
-            self.rewarp()
-            mean, var, _ = self._rows_predict(row[None, :n_theta], X, noise_zero)
-            mus.append(self.y_train_std_ * mean[0] + self.y_train_mean_)
-            stds.append(np.sqrt(var[0] * self.y_train_std_**2))
-        self.create_warpers(*backup)
-        self.rewarp()
-        return np.array(mus), np.array(stds)
+        return self._ctx.acq(noise_off(H) if noise_zero else H, X, y_mean, y_std, kinds, params, n_samples)
 
     def _pvrs(self, X, thompson_points, has_alpha_vec):
         """Device side of PVRS / VarianceReduction (``bask/acquisition.py:287-300,328-338``)."""
-        if self._generic:
-            return self._pvrs_gram(np.atleast_2d(X), np.atleast_2d(thompson_points), has_alpha_vec)
-        Hk = self._canonical(self._kernel_theta_for_predict())
-        status = self._ctx.pvrs_prepare(Hk, has_alpha_vec)
-        if status != 0:
-            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % status)
-        return self._ctx.pvrs(Hk, X, np.atleast_2d(thompson_points))
-
-    def _pvrs_gram(self, X, T, has_alpha_vec):
-        """PVRS for a generic kernel tree through the bordered-inverse identity of ``bgp_pvrs``,
-        ``covs_i = sum_t [k_t^T K^-1 k_t + (k(x_t, x_i) - k_i^T K^-1 k_t)^2 / (kappa_i - k_i^T K^-1 k_i)]``, every term read off
-        ONE device predictive covariance ``C = K_** - K_* K^-1 K_*^T`` over [Thompson points; candidates] per candidate chunk:
-        ``C_ti``, ``C_ii`` and ``k_t^T K^-1 k_t = kappa_t - C_tt``.  K carries alpha only when it is a vector (reference quirk,
-        ``bask/acquisition.py:332-333``); the kernel matrices come from the host-evaluated ``kernel_``."""
-        k = self.kernel_
-        Xt = self.X_train_
-        self._gram_resident = None
-        res = self._ctx.posterior_gram(k(Xt)[None], use_alpha=bool(has_alpha_vec), want_alpha=False)
-        self._raise_if_not_pd(res["status"])
-        if self.warp_inputs:
-            X, T = self.warp(X), self.warp(T)
-        nt = T.shape[0]
-        covs = np.empty(X.shape[0])
-        step = max(1, 2048 - nt)
-        for lo in range(0, X.shape[0], step):
-            Q = np.vstack([T, X[lo : lo + step]])
-            kss = k.diag(Q)
-            _mean, _var, C = self._ctx.predict_gram(k(Q, Xt)[None], kss[None], k(Q)[None])
-            C = C[0]
-            tt = kss[:nt] - np.diag(C)[:nt]
-            cross = C[:nt, nt:]
-            cii = np.diag(C)[nt:]
-            covs[lo : lo + step] = tt.sum() + np.sum(cross * cross / cii[None, :], axis=0)
-        return covs
+        return self._post.pvrs(self, np.atleast_2d(X), np.atleast_2d(thompson_points), has_alpha_vec)
 
     # ---- batch proposals (Optimizer.ask(n_points > 1); DESIGN.md section 12)
     def _fantasy_batch(self, X, first, q, acq, rows, n_samples, acq_kwargs, lie, thompson=None, replay=None, path="auto",
@@ -957,8 +737,8 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             raise ValueError(f"a batch of {q} points from {X.shape[0]} candidates")
         lie_n = None if lie is None else (float(lie) - float(np.ravel(self.y_train_mean_)[0])) / float(np.ravel(self.y_train_std_)[0])
         spec = A._device_acq_spec(acq, acq_kwargs) if isinstance(acq, A.UncertaintyAcquisition) else None
-        fast = (path != "fallback" and spec is not None and A.DEVICE_ACQUISITIONS and not self.warp_inputs and not self._generic
-                and X.shape[1] <= 32)
+        fast = (path != "fallback" and spec is not None and A.DEVICE_ACQUISITIONS and not self.warp_inputs
+                and self._post.canonical and X.shape[1] <= 32)
         if isinstance(acq, A.UncertaintyAcquisition) and (rows is None or len(rows) == 0):
             # no hyper-posterior draws (n_samples=0): every value is 0, np.argmax takes the lowest index left
             rest = [i for i in range(X.shape[0]) if i != first][: q - 1]
@@ -976,17 +756,13 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         resident posteriors are left as they are."""
         import time
 
-        Xt, n = self._X_train_, self._X_train_.shape[0]
-        alpha_diag = np.broadcast_to(np.asarray(self.alpha, dtype=np.float64), (n,)) if not np.iterable(self.alpha) \
-            else np.asarray(self.alpha, dtype=np.float64)
         H = self._canonical(np.atleast_2d(rows))
-        ctx = _lib.Context(Xt, self.y_train_, alpha_diag, form=self._plan.form, stationary=self._plan.stationary,
-                           max_batch=self._ctx.max_batch, device=self.device)
+        ctx = _lib.Context(self._X_train_, self.y_train_, self._alpha_diag(), form=self._plan.form,
+                           stationary=self._plan.stationary, max_batch=self._ctx.max_batch, device=self.device)
         info = {"step_ms": []}
         try:
-            self._raise_if_not_pd(ctx.posterior(H, want_alpha=False)["status"])
-            Hk = H.copy()
-            Hk[:, -1] = -np.inf
+            raise_if_not_pd(ctx.posterior(H, want_alpha=False)["status"], self.kernel_)
+            Hk = noise_off(H)
             noise = self._fantasy_base_alpha() + np.exp(H[:, -1])
             y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
             t0 = time.perf_counter()
@@ -1078,7 +854,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             raise ValueError("mvn must be 'auto', 'reference' or 'cholesky', got %r" % (mode,))
         if mode == "auto":
             mode = "reference" if m <= self.MVN_REFERENCE_MAX_POINTS else "cholesky"
-        if self._generic:
+        if not self._post.canonical:
             # the device draw builds the predictive covariance from the canonical hyper-parameters; a generic tree has none:
             # mean / covariance through the host-evaluated kernel, the reference's own SVD draw on the host
             mode = "reference"
@@ -1137,27 +913,19 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         predictive means / covariances in chunks -- and the host doing what numpy does there: one legacy
         ``multivariate_normal`` (SVD) per sample, in sample order, on the caller's generator.  (len(rows), m)."""
         rows = np.atleast_2d(rows)
-        n_theta = len(self.kernel_.theta)
         m = X.shape[0]
         out = np.empty((len(rows), m))
         if self.warp_inputs:
             validate_zeroone(X)
-            d = self._X_train_.shape[1]
-            backup = (np.copy(self.warp_alphas_), np.copy(self.warp_betas_))
-            try:
+            with self._row_warps() as install:
                 for i, row in enumerate(rows):  # every draw has its own warped training inputs
-                    self.create_warpers(row[n_theta : n_theta + d], row[n_theta + d :])
-                    self.rewarp()
-                    mean, cov = self._mean_cov_rows(row[None, :n_theta], X, noise)
+                    mean, cov = self._mean_cov_rows(install(row), X, noise)
                     out[i] = _legacy_mvn(rng, mean[0], cov[0], 1)[0]
-            finally:
-                self.create_warpers(*backup)
-                self.rewarp()
             return out
         # the covariances of a chunk of samples at a time (m^2 doubles each)
         chunk = max(1, int((256 << 20) // (8 * m * m)))
         for lo in range(0, len(rows), chunk):
-            mean, cov = self._mean_cov_rows(rows[lo : lo + chunk, :n_theta], X, noise)
+            mean, cov = self._mean_cov_rows(rows[lo : lo + chunk, : len(self.kernel_.theta)], X, noise)
             for i in range(mean.shape[0]):
                 out[lo + i] = _legacy_mvn(rng, mean[i], cov[i], 1)[0]
         return out
@@ -1165,44 +933,28 @@ class BayesGPR(RegressorMixin, BaseEstimator):
     def _mean_cov_rows(self, thetas, X, noise):
         """Predictive mean and covariance (y units) of the GP of every chain row: batched device posterior build over the
         distinct rows + batched device predict with the full covariance; ``theta`` / ``alpha_`` / ``L_`` stay untouched."""
-        mean, _var, cov = self._rows_predict(np.atleast_2d(thetas), X, noise_zero=not noise, return_cov=True)
+        mean, _var, cov = self._post.rows_predict(self, np.atleast_2d(thetas), X, not noise, return_cov=True)
         return self.y_train_std_ * mean + self.y_train_mean_, cov * self.y_train_std_**2
 
     def _draw_rows(self, rows, X, Z, noise):
         """f_i = mean_i + chol(cov_i) Z[i] for the GP of chain row i (kernel parameters and, with input warping, its
         own warp); (len(rows), m) in the units of y.  The resident posterior of ``theta`` is rebuilt lazily by the
-        next call that needs it (``_make_resident``), so ``theta`` / ``alpha_`` / ``L_`` / ``K_inv_`` are untouched."""
+        next call that needs it (``make_resident``), so ``theta`` / ``alpha_`` / ``L_`` / ``K_inv_`` are untouched."""
         rows = np.atleast_2d(rows)
-        n_theta = len(self.kernel_.theta)
         if self.warp_inputs:
             validate_zeroone(X)
-            d = self._X_train_.shape[1]
-            backup = (np.copy(self.warp_alphas_), np.copy(self.warp_betas_))
             out = np.empty((len(rows), X.shape[0]))
-            try:
+            with self._row_warps() as install:
                 for i, row in enumerate(rows):  # every draw has its own warped training inputs
-                    self.create_warpers(row[n_theta : n_theta + d], row[n_theta + d :])
-                    self.rewarp()
-                    out[i] = self._draw_rows_device(row[None, :n_theta], X, Z[i : i + 1], noise)[0]
-            finally:
-                self.create_warpers(*backup)
-                self.rewarp()
+                    out[i] = self._draw_rows_device(install(row), X, Z[i : i + 1], noise)[0]
             return out
-        return self._draw_rows_device(rows[:, :n_theta], X, Z, noise)
+        return self._draw_rows_device(rows[:, : len(self.kernel_.theta)], X, Z, noise)
 
     def _draw_rows_device(self, thetas, X, Z, noise):
         H = self._canonical(thetas)
         uniq, inverse = np.unique(H, axis=0, return_inverse=True)  # repeated chain rows share one posterior build
-        res = self._ctx.posterior(uniq, want_alpha=False)
-        if np.any(res["status"] != 0):
-            bad = int(np.flatnonzero(res["status"])[0])
-            raise np.linalg.LinAlgError(
-                _PD_MESSAGE % self.kernel_,
-                "%d-th leading minor of the array is not positive definite" % res["status"][bad],
-            )
-        Hk = H.copy()
-        if not noise:
-            Hk[:, -1] = -np.inf  # noise_set_to_zero(): the factors keep the noise, the predictive kernel drops it
+        raise_if_not_pd(self._ctx.posterior(uniq, want_alpha=False)["status"], self.kernel_)
+        Hk = H if noise else noise_off(H)  # noise_set_to_zero(): the factors keep the noise, the predictive kernel drops it
         pidx = np.asarray(inverse, dtype=np.int32).ravel()
         out = np.empty_like(Z)
         todo = np.arange(len(H))
@@ -1220,7 +972,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         return self.y_train_std_ * out + self.y_train_mean_
 
     def _draw(self, X, n_samples, rng):
-        self._make_resident()
+        self._post.make_resident(self)
         Hk = self._canonical(self._kernel_theta_for_predict())
         z = rng.standard_normal((n_samples, X.shape[0]))
         jitter = 1e-10
@@ -1254,19 +1006,6 @@ def _fantasy_tell_once():
         _fantasy_told.append(True)
         print("[bayes_skopt_amd] ask(n_points > 1): fantasy points through the fallback path (one posterior build + "
               "evaluation per point on an augmented training set)", file=sys.stderr, flush=True)
-
-
-def _with_white_zeroed(kernel):
-    """A copy of ``kernel`` with its WhiteKernel (inside nested sums) at level 0: what ``noise_set_to_zero`` does to
-    ``kernel_`` (``bask/bayesgpr.py:327-333``)."""
-    k = clone(kernel)
-    if isinstance(k, WhiteKernel):
-        k.set_params(noise_level=0.0)
-        return k
-    present, white_param = param_for_white_kernel_in_sum(k)
-    if present:
-        k.set_params(**{white_param: WhiteKernel(noise_level=0.0)})
-    return k
 
 
 def _legacy_mvn(rng, mean, cov, n_samples):
@@ -1314,7 +1053,7 @@ class _ShardedLogProb:
         # From here on every rank is committed to ONE collective in ``finish``.  Whatever fails locally in between -- the
         # priors raising, a failed submit, a device error -- is carried in the token and reported THROUGH that collective
         # (status word next to the values): a rank that raised here would leave its peers blocked in the all-gather.
-        if gp.warp_inputs or gp._generic:  # per-walker warps / host-evaluated kernels: finished values gathered from the host
+        if gp.warp_inputs or not gp._post.canonical:  # per-walker warps / host kernels: finished values gathered via the host
             try:
                 return ("host", B, gp._log_prob_begin(Theta[lo:hi], priors, warp_priors) if hi > lo else None, None)
             except Exception as exc:
@@ -1448,7 +1187,7 @@ def _resident_run(gp, n_walkers, n_dim, priors, warp_priors, comm):
     ``comm``: the communicator of a sharded ensemble (every rank decides from the same facts: the same answer everywhere)."""
     if not getattr(gp, "resident_sampler", True):
         return None, None  # (asked for: not a fallback)
-    if gp._generic:
+    if not gp._post.canonical:
         return None, "the kernel tree has no canonical device form: its matrices are evaluated on the host"
     if n_walkers % 2:
         return None, "an odd number of walkers: the two halves of a step differ in size"
