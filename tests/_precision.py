@@ -1,0 +1,429 @@
+"""The precision model of the fp64 GP kernels: ONE tolerance function, the error metrics it applies to, the case lists shared by
+tests/test_cpu_precision.py (fp64 LAPACK reaches the tolerance; a single-precision slip misses it) and
+tests/test_gpu_precision.py (the device meets it), and the cached extended-precision references (oracle/hp_oracle.py).
+
+Every error is measured against the scale that a correct fp64 computation can lose digits on, and compared with
+``tol(quantity, kappa, n) = max(FLOOR[q], C[q] * kappa * eps64)`` (+ the Beta-CDF budget for warped inputs), kappa = the
+2-norm condition number of the training Gram matrix:
+
+* lml      |dLML| / (|y^T a|/2 + sum_i |log L_ii| + n/2 log 2 pi)        (the absolute sum of its terms)
+* alpha    max |d a| / max |a|;   K_inv  max |d K^-1| / max |K^-1|;   L  max_ij |d L_ij| / sqrt(K_ii)
+* grad     max_k |d g_k| / (0.5 sum_ij |W_ij dK_ij/dh_k|),  W = a a^T - K^-1   (components can cancel to ~0)
+* mean     max |d m_i| / max_i sum_j |K*_ij a_j|;   var  max |d var| (and |d cov|) / prior variance
+* pvrs     max |d cov_i| / max |cov_i|;   sample  max |d f| / max |f|
+* warped   + CDF_REL * sens, sens = the quantity's error with the inputs rounded to fp32 divided by 2^-24: the first-order
+             response to a relative input perturbation, times the device Beta CDF's relative accuracy.
+"""
+import functools
+import math
+
+import numpy as np
+
+EPS = float(np.finfo(np.float64).eps)
+F32 = 2.0 ** -24  # unit round-off of fp32
+CDF_REL = 1e-11  # device Beta CDF vs mpmath: within 2e-12 relative (x5 margin)
+
+# Set by tests/test_cpu_precision.py: on every case fp64 LAPACK is within tol / 10 of the reference and a single-precision
+# slip misses it by >= 10 tol -- inputs or Gram entries rounded to fp32 for lml / alpha / grad, inputs rounded to fp32 for
+# the predictive mean and variance, the augmented Gram matrices for pvrs, the predictive covariance for sample.  The mean's
+# fp64 error is ~1e-16 absolute whatever kappa (a dot product with alpha), hence its small constant.  sample's constant is
+# the loosest: the draws go through chol(cov + jitter I) of a covariance that is itself the remainder of a cancellation, at
+# the larger of two condition numbers (``sample_kappa``); fp32 there still misses by >= 10 tol.
+C = {"lml": 0.5, "alpha": 4.0, "K_inv": 4.0, "L": 4.0, "mean": 0.02, "var": 4.0, "grad": 2.0, "pvrs": 2.0, "sample": 16.0}
+FLOOR = {"lml": 4e-13, "alpha": 2e-12, "K_inv": 2e-12, "L": 2e-12, "mean": 1e-13, "var": 4e-12, "grad": 1e-12,
+         "pvrs": 4e-12, "sample": 4e-12}
+
+
+def tol(quantity, kappa, n, sens=0.0):
+    """The tolerance of every precision assertion: condition-scaled, with a floor that grows with sqrt(n) (fp64 sums of n
+    rounded terms), plus the Beta-CDF budget (``sens``) for warped inputs."""
+    base = max(FLOOR[quantity] * max(1.0, math.sqrt(n / 128.0)), C[quantity] * kappa * EPS)
+    return base + CDF_REL * sens
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# error metrics
+# ------------------------------------------------------------------------------------------------------------------------------
+def f(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def err_lml(got, ref):
+    return abs(float(got) - float(ref["lml"])) / float(ref["scale"])
+
+
+def err_alpha(got, ref):
+    a = f(ref["alpha"])
+    return float(np.abs(f(got) - a).max() / np.abs(a).max())
+
+
+def err_K_inv(got, Kinv):
+    Kinv = f(Kinv)
+    return float(np.abs(f(got) - Kinv).max() / np.abs(Kinv).max())
+
+
+def err_L(got, ref):
+    K = ref["K"]
+    s = np.sqrt(f(np.diagonal(K)))
+    return float((np.abs(np.tril(f(got)) - f(ref["L"])) / s[:, None]).max())
+
+
+def err_grad(got, ref):
+    s = f(ref["grad_scale"])
+    return float((np.abs(f(got) - f(ref["grad"])) / np.maximum(s, 1e-30 * s.max() + 1e-300)).max())
+
+
+def err_rel_max(got, ref_vals, scale=None):
+    r = f(ref_vals)
+    sc = np.abs(r).max() if scale is None else float(scale)
+    return float(np.abs(f(got) - r).max() / sc)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fp64 computations from a given Gram matrix (the "bites" perturbations enter through X or K)
+# ------------------------------------------------------------------------------------------------------------------------------
+def lml64(K, y):
+    from scipy.linalg import cho_solve, cholesky
+
+    L = cholesky(K, lower=True, check_finite=False)
+    a = cho_solve((L, True), y, check_finite=False)
+    return -0.5 * float(y @ a) - float(np.log(np.diag(L)).sum()) - len(y) / 2.0 * math.log(2 * math.pi), a, L
+
+
+def grad64(K, y, X, h, stationary, form):
+    from oracle import gp_oracle as O
+    from scipy.linalg import cho_solve
+
+    _v, a, L = lml64(K, y)
+    Ki = cho_solve((L, True), np.eye(len(y)), check_finite=False)
+    return 0.5 * np.einsum("ij,jik->k", np.outer(a, a) - Ki, O.kernel_gradient(X, h, stationary, form))
+
+
+def to32(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# cases
+# ------------------------------------------------------------------------------------------------------------------------------
+FAMILIES = [(s, fm) for fm in ("product", "sum") for s in ("rbf", "matern12", "matern32", "matern52")]
+KAPPA_MAX = 1e5
+
+
+def _problem(n, d, seed, stationary, form, B, vec_alpha, dup=False, big_c=False):
+    """Inputs, targets, alpha diagonal and B canonical vectors.  The noise level of each vector is raised until
+    cond(K) <= KAPPA_MAX (``_fit_noise``)."""
+    rng = np.random.RandomState(seed)
+    X = rng.uniform(size=(n, d))
+    if dup and n > 3:
+        X[2] = X[0]  # r = 0 off the diagonal
+    y = np.sin(3.0 * X.sum(axis=1)) + 0.1 * rng.randn(n)
+    if n > 1:
+        y = (y - y.mean()) / y.std()
+    alpha = 10.0 ** rng.uniform(-8, -2, size=n) if vec_alpha else 1e-8
+    ell0 = math.log(0.25 * math.sqrt(d))  # typical spacing-relative length scale
+    H = np.column_stack([rng.uniform(-0.5, 0.5, B) + (math.log(1e3) if big_c else 0.0),
+                         ell0 + 0.3 * rng.randn(B, d), rng.uniform(math.log(1e-4), math.log(1e-2), B)])
+    return X, y, alpha, H
+
+
+def kappa_of(X, alpha, h, stationary, form):
+    from oracle import gp_oracle as O
+
+    K = O.gram_with_jitter(X, np.broadcast_to(alpha, (len(X),)), h, stationary, form)
+    w = np.linalg.eigvalsh(K)
+    return float(w[-1] / w[0])
+
+
+def _fit_noise(X, alpha, H, stationary, form):
+    """Raise log s2 of each row until kappa <= KAPPA_MAX; returns H and the kappas."""
+    H = H.copy()
+    kap = []
+    for b in range(len(H)):
+        while True:
+            k = kappa_of(X, alpha, H[b], stationary, form)
+            if k <= KAPPA_MAX:
+                break
+            H[b, -1] += math.log(4.0)
+        kap.append(k)
+    return H, np.array(kap)
+
+
+def _lml_cases():
+    ns = [1, 2, 17, 127, 128, 129, 255, 257, 640, 1024, 1025, 2048, 4096]
+    ds = [1, 3, 16, 17, 33]
+    Bs = [1, 3, 9]
+    out = []
+    for j in range(26):
+        n = ns[j % 13]
+        st, fm = FAMILIES[j % 8]
+        d = ds[j % 5]
+        B = Bs[j % 3] if n <= 640 else 1
+        out.append(dict(id="lml%d_n%d_d%d_%s_%s_B%d" % (j, n, d, st, fm, B), n=n, d=d, stationary=st, form=fm, B=B,
+                        vec_alpha=bool(j % 2), seed=100 + j))
+    # (the stride above leaves these two families without a ragged last tile beyond the first block)
+    for j, (n, d, st, fm, B) in enumerate([(385, 17, "rbf", "product", 3), (257, 33, "matern12", "product", 9)], start=26):
+        out.append(dict(id="lml%d_n%d_d%d_%s_%s_B%d" % (j, n, d, st, fm, B), n=n, d=d, stationary=st, form=fm, B=B,
+                        vec_alpha=bool(j % 2), seed=100 + j))
+    return out
+
+
+def _grad_cases():
+    ns = [1, 2, 128, 129, 300, 385, 1024]
+    ds = [1, 15, 16, 17, 32, 33]
+    out = []
+    for j in range(16):
+        n = ns[j % 7] if j < 14 else 129
+        if n == 1024 and j > 7:
+            n = 300  # (one long-double inverse at n = 1024 is enough)
+        st, fm = FAMILIES[j % 8]
+        d = ds[j % 6]
+        out.append(dict(id="grad%d_n%d_d%d_%s_%s" % (j, n, d, st, fm), n=n, d=d, stationary=st, form=fm,
+                        B=9 if j % 4 == 0 and n <= 300 else 1, vec_alpha=bool(j % 3 == 0), seed=300 + j,
+                        dup=(j == 14), big_c=(j == 15)))
+    out[14]["stationary"], out[14]["form"] = "matern12", "product"
+    out[14]["id"] = "grad14_n129_dup_matern12_product"
+    out[15]["id"] = "grad15_n129_bigc_%s_%s" % (out[15]["stationary"], out[15]["form"])
+    # off-diagonal tiles for rbf / product, the dimension-staging loop for matern32 / sum
+    for j, (n, d, st, fm) in enumerate([(385, 17, "rbf", "product"), (129, 33, "matern32", "sum")], start=16):
+        out.append(dict(id="grad%d_n%d_d%d_%s_%s" % (j, n, d, st, fm), n=n, d=d, stationary=st, form=fm, B=1,
+                        vec_alpha=bool(j % 2), seed=300 + j))
+    return out
+
+
+def _post_cases():
+    out = []
+    for j, (n, m) in enumerate([(127, 65), (128, 64), (129, 257), (255, 63), (257, 1), (385, 65)]):
+        st, fm = FAMILIES[(j * 3) % 8]
+        out.append(dict(id="post%d_n%d_m%d_%s_%s" % (j, n, m, st, fm), n=n, d=[2, 3, 5, 1, 4, 3][j], m=m, stationary=st,
+                        form=fm, B=1, vec_alpha=bool(j % 2), seed=500 + j))
+    return out
+
+
+LML_CASES = _lml_cases()
+# every factorisation schedule runs on these (matern52 product, d = 3: the family the launch-free Gram generation serves);
+# three distinct canonical vectors, tiled to the batch size a schedule needs (``sched_problem``)
+SCHED_CASES = [dict(id="sched_n%d" % n, n=n, d=3, stationary="matern52", form="product", B=3, vec_alpha=True, seed=1000 + n)
+               for n in (640, 1025, 2048)]
+GRAD_CASES = _grad_cases()
+POST_CASES = _post_cases()
+WARP_CASES = [dict(id="warp_n100_d2", n=100, d=2, stationary="matern52", form="product", B=3, vec_alpha=False, seed=700),
+              dict(id="warp_n300_d3", n=300, d=3, stationary="matern32", form="sum", B=3, vec_alpha=True, seed=701)]
+PVRS_CASES = [dict(id="pvrs_n60_d2", n=60, d=2, stationary="matern52", form="product", B=1, vec_alpha=False, seed=800,
+                   nc=12, nt=5),
+              dict(id="pvrs_n200_d3", n=200, d=3, stationary="rbf", form="product", B=1, vec_alpha=True, seed=801, nc=10,
+                   nt=7)]
+SAMPLE_CASES = [dict(id="sample_n80_m150", n=80, d=2, stationary="matern52", form="product", B=1, vec_alpha=False, seed=900,
+                     m=150),
+                dict(id="sample_n257_m129", n=257, d=3, stationary="matern32", form="sum", B=1, vec_alpha=False,
+                     seed=901, m=129)]
+ALL = {c["id"]: c for c in LML_CASES + SCHED_CASES + GRAD_CASES + POST_CASES + WARP_CASES + PVRS_CASES + SAMPLE_CASES}
+
+
+@functools.lru_cache(maxsize=None)
+def problem(cid):
+    """(X, y, alpha, H, kappas) of a case, the noise fitted to KAPPA_MAX."""
+    c = ALL[cid]
+    X, y, alpha, H = _problem(c["n"], c["d"], c["seed"], c["stationary"], c["form"], c["B"], c["vec_alpha"],
+                              c.get("dup", False), c.get("big_c", False))
+    if cid.startswith("warp"):
+        return X, y, alpha, H, None
+    H, kap = _fit_noise(X, alpha, H, c["stationary"], c["form"])
+    return X, y, alpha, H, kap
+
+
+def warp_params(cid):
+    c = ALL[cid]
+    rng = np.random.RandomState(c["seed"] + 1)
+    return rng.uniform(-0.7, 0.7, size=(c["B"], 2 * c["d"]))
+
+
+@functools.lru_cache(maxsize=None)
+def warped_problem(cid):
+    """Per-walker warped inputs (long double, mpmath Beta CDF) and kappas of the warped Gram matrices."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    W = warp_params(cid)
+    Xw = [HP.warp_inputs(X, W[b]) for b in range(len(W))]
+    kap = np.array([kappa_of(f(Xw[b]), alpha, H[b], c["stationary"], c["form"]) for b in range(len(W))])
+    return Xw, W, kap
+
+
+@functools.lru_cache(maxsize=None)
+def ref_lml(cid, b):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    return HP.lml(X, y, alpha, H[b], c["stationary"], c["form"])
+
+
+@functools.lru_cache(maxsize=None)
+def ref_grad(cid, b):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    return HP.lml_and_grad(X, y, alpha, H[b], c["stationary"], c["form"])
+
+
+@functools.lru_cache(maxsize=None)
+def ref_post(cid):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    return HP.posterior(X, y, alpha, H[0], c["stationary"], c["form"])
+
+
+def query(cid):
+    c = ALL[cid]
+    lo, hi = (0.0, 1.0) if cid.startswith("warp") else (-0.1, 1.1)  # (the Beta CDF is defined on [0, 1])
+    return np.random.RandomState(c["seed"] + 2).uniform(lo, hi, size=(c.get("m", 40), c["d"]))
+
+
+@functools.lru_cache(maxsize=None)
+def ref_predict(cid, noise_zero):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    return HP.predict(X, y, alpha, H[0], query(cid), c["stationary"], c["form"], noise_zero=noise_zero, return_cov=True,
+                      post=ref_post(cid))
+
+
+def mean_scale(cid):
+    """max_i sum_j |K*_ij a_j| (long double reference)."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    Ks = HP.gram(query(cid), H[0], c["stationary"], c["form"], Y=X)
+    return float(np.abs(Ks * ref_post(cid)["alpha"][None, :]).sum(axis=1).max())
+
+
+def prior_var(cid, noise_zero):
+    c = ALL[cid]
+    _X, _y, _a, H, _ = problem(cid)
+    from oracle import hp_oracle as HP
+
+    return float(HP.prior_var(H[0], c["d"], c["form"], noise=not noise_zero))
+
+
+def pvrs_inputs(cid):
+    c = ALL[cid]
+    rng = np.random.RandomState(c["seed"] + 3)
+    return rng.uniform(size=(c["nc"], c["d"])), rng.uniform(size=(c["nt"], c["d"]))
+
+
+@functools.lru_cache(maxsize=None)
+def ref_pvrs(cid):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, _y, alpha, H, _ = problem(cid)
+    Xc, Xt = pvrs_inputs(cid)
+    return HP.pvrs_covs(X, alpha if c["vec_alpha"] else None, H[0], Xc, Xt, c["stationary"], c["form"])
+
+
+SAMPLE_JITTER = 1e-8
+
+
+def sample_z(cid):
+    c = ALL[cid]
+    return np.random.RandomState(c["seed"] + 4).standard_normal((3, c["m"]))
+
+
+@functools.lru_cache(maxsize=None)
+def ref_sample(cid):
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    out, _p = HP.sample_y(X, y, alpha, H[0], query(cid), sample_z(cid), SAMPLE_JITTER, c["stationary"], c["form"],
+                         noise_zero=True)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def sample_kappa(cid):
+    """The draws go through chol(cov + jitter I): the larger of the two condition numbers governs them."""
+    _X, _y, _a, _H, kap = problem(cid)
+    C = f(ref_predict(cid, True)["cov"])
+    w = np.linalg.eigvalsh(C + SAMPLE_JITTER * np.eye(len(C)))
+    return max(float(kap[0]), float(w[-1] / w[0]))
+
+
+def grad_vs_fp64(g_dev, X, y, alpha, h, stationary="matern52", form="product"):
+    """(err, tol) of a device LML gradient against the fp64 oracle (whose own error is within tol / 10 on the cases of
+    tests/test_cpu_precision.py), on the gradient's absolute-sum scale, kappa from the oracle's Gram matrix."""
+    from oracle import gp_oracle as O
+    from scipy.linalg import cho_solve, cholesky
+
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    n = len(X)
+    K = O.gram_with_jitter(X, np.broadcast_to(alpha, (n,)), h, stationary, form)
+    L = cholesky(K, lower=True)
+    a = cho_solve((L, True), y)
+    Wm = np.outer(a, a) - cho_solve((L, True), np.eye(n))
+    G = O.kernel_gradient(X, h, stationary, form)
+    g = 0.5 * np.einsum("ij,jik->k", Wm, G)
+    s = 0.5 * np.einsum("ij,jik->k", np.abs(Wm), np.abs(G))
+    w = np.linalg.eigvalsh(K)
+    err = float((np.abs(f(g_dev) - g) / np.maximum(s, 1e-30 * s.max() + 1e-300)).max())
+    return err, tol("grad", float(w[-1] / w[0]), n)
+
+
+def sched_problem(n, B):
+    """The schedule case at n: (cid, X, y, alpha, H, kappas) with its three canonical vectors tiled to B rows."""
+    cid = "sched_n%d" % n
+    X, y, alpha, H, kap = problem(cid)
+    r = -(-B // 3)
+    return cid, X, y, alpha, np.tile(H, (r, 1))[:B], np.tile(kap, r)[:B]
+
+
+@functools.lru_cache(maxsize=None)
+def ref_set_warp(cid):
+    """Context-level warp with the first walker's parameters: the long-double posterior alpha and predict at the warped query
+    points, and per quantity (alpha, mean, var) the scale its error is measured on and the Beta-CDF sensitivity ``sens``
+    (the fp64 computation's error with the warped inputs rounded to fp32, over 2^-24)."""
+    from oracle import gp_oracle as O
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    st, fm = c["stationary"], c["form"]
+    X, y, alpha, H, _ = problem(cid)
+    Xw, W, kap = warped_problem(cid)
+    ad = np.broadcast_to(alpha, (len(X),))
+    Xqw = HP.warp_inputs(query(cid), W[0])
+    post = HP.posterior(Xw[0], y, alpha, H[0], st, fm)
+    pr = HP.predict(Xw[0], y, alpha, H[0], Xqw, st, fm, post=post)
+    Ks = HP.gram(Xqw, H[0], st, fm, Y=Xw[0])
+    scale = {"alpha": None, "mean": float(np.abs(Ks * post["alpha"][None, :]).sum(axis=1).max()),
+             "var": float(HP.prior_var(H[0], c["d"], fm))}
+    ref = {"alpha": post["alpha"], "mean": pr["mean"], "var": pr["var"]}
+    X32, Xq32 = to32(f(Xw[0])), to32(f(Xqw))
+    m32, s32 = O.predict(X32, y, ad, H[0], Xq32, st, fm)
+    got32 = {"alpha": O.posterior(X32, y, ad, H[0], st, fm)[2], "mean": m32, "var": s32**2}
+    sens = {q: err_rel_max(got32[q], ref[q], scale[q]) / F32 for q in ref}
+    return {"ref": ref, "scale": scale, "sens": sens, "kappa": float(kap[0]), "W": W[0]}
+
+
+def pvrs_gram32(X_train, alpha_vec, h, X_cand, thompson_points, stationary, form):
+    """``gp_oracle.pvrs_covs`` with every augmented Gram matrix rounded to fp32 before its factorisation (the "bites"
+    perturbation of PVRS: a single-precision slip in the matrix the device inverts)."""
+    from oracle import gp_oracle as O
+    from scipy.linalg import cho_solve, cholesky
+
+    out = np.empty(len(X_cand))
+    for i in range(len(X_cand)):
+        Xa = np.concatenate([X_train, X_cand[i : i + 1]])
+        K = O.kernel_matrix(Xa, h, stationary, form)
+        if alpha_vec is not None:
+            K[np.diag_indices_from(K)] += np.concatenate([alpha_vec, [0.0]])
+        L = cholesky(to32(K), lower=True)
+        Kt = O.kernel_matrix(thompson_points, h, stationary, form, Y=Xa)
+        out[i] = float(np.einsum("ij,ji->", Kt, cho_solve((L, True), Kt.T)))
+    return out

@@ -1,0 +1,178 @@
+"""The precision model of tests/_precision.py is right, shown without a GPU on the whole case list of
+tests/test_gpu_precision.py, against the extended-precision reference (oracle/hp_oracle.py):
+
+* reachable -- fp64 LAPACK (oracle/gp_oracle.py) lies within tol / 10 of the reference, so a correct fp64 kernel is not
+  near the edge and the GPU test cannot be flaky;
+* bites -- the same computation with the inputs rounded to fp32, and separately with the Gram entries rounded to fp32,
+  misses the reference by at least 10 tol on the LML, alpha and the gradient, so a single-precision slip fails it; so do
+  fp32 inputs for the predictive mean and variance, fp32 augmented Gram matrices for PVRS and an fp32 predictive
+  covariance for sample_y.
+  (Rounding the inputs of a one-point problem changes nothing: that check is skipped at n = 1.)"""
+import numpy as np
+import pytest
+
+import _precision as P
+
+hp = pytest.importorskip("oracle.hp_oracle")
+if not hp.available():
+    pytest.skip("np.longdouble has no 64-bit mantissa here: no extended-precision reference", allow_module_level=True)
+
+from oracle import gp_oracle as O  # noqa: E402
+
+MARGIN = 10.0
+
+
+def _report(name, reach, bite=None):
+    print("%-44s reachable err/tol %.2e%s" % (name, reach, "" if bite is None else "   bites err/tol %.1e" % bite))
+
+
+def test_every_family_reaches_a_ragged_tile_beyond_the_first_block():
+    """Each of the eight kernel families runs the LML at three or more sizes, one of them > 128 with a ragged last tile."""
+    for st, fm in P.FAMILIES:
+        ns = {c["n"] for c in P.LML_CASES if (c["stationary"], c["form"]) == (st, fm)}
+        assert len(ns) >= 3 and any(n > 128 and n % 128 for n in ns), (st, fm, sorted(ns))
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.LML_CASES + P.SCHED_CASES])
+def test_lml_and_alpha(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, kap = P.problem(cid)
+    n, st, fm = len(X), c["stationary"], c["form"]
+    ad = np.broadcast_to(alpha, (n,))
+    worst_reach, worst_bite = 0.0, np.inf
+    for b in range(len(H)):
+        ref = P.ref_lml(cid, b)
+        tl, ta = P.tol("lml", kap[b], n), P.tol("alpha", kap[b], n)
+        K = O.gram_with_jitter(X, ad, H[b], st, fm)
+        v, a, _ = P.lml64(K, y)
+        r = max(P.err_lml(v, ref) / tl, P.err_alpha(a, ref) / ta)
+        assert r <= 1 / MARGIN, (cid, b, P.err_lml(v, ref), tl, P.err_alpha(a, ref), ta)
+        np.testing.assert_allclose(v, O.lml(X, y, ad, H[b], st, fm), rtol=1e-15, atol=0)  # (the same fp64 computation)
+        slips = [K.astype(np.float32).astype(np.float64)]
+        if n > 1:
+            slips.append(O.gram_with_jitter(P.to32(X), ad, H[b], st, fm))
+        for Ks in slips:
+            vs, as_, _ = P.lml64(Ks, y)
+            bl, ba = P.err_lml(vs, ref) / tl, P.err_alpha(as_, ref) / ta
+            assert bl >= MARGIN and ba >= MARGIN, (cid, b, bl, ba)
+            worst_bite = min(worst_bite, bl, ba)
+        worst_reach = max(worst_reach, r)
+    _report(cid, worst_reach, worst_bite)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.GRAD_CASES])
+def test_gradient(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, kap = P.problem(cid)
+    n, st, fm = len(X), c["stationary"], c["form"]
+    ad = np.broadcast_to(alpha, (n,))
+    worst_reach, worst_bite = 0.0, np.inf
+    for b in range(min(len(H), 2)):
+        ref = P.ref_grad(cid, b)
+        tg = P.tol("grad", kap[b], n)
+        v, g = O.lml_and_grad(X, y, ad, H[b], st, fm)
+        r = P.err_grad(g, ref) / tg
+        assert r <= 1 / MARGIN, (cid, b, P.err_grad(g, ref), tg)
+        assert P.err_lml(v, ref) <= P.tol("lml", kap[b], n) / MARGIN
+        K = O.gram_with_jitter(X, ad, H[b], st, fm)
+        slips = [P.grad64(P.to32(K), y, X, H[b], st, fm)]
+        if n > 1:
+            slips.append(P.grad64(O.gram_with_jitter(P.to32(X), ad, H[b], st, fm), y, P.to32(X), H[b], st, fm))
+        for gs in slips:
+            bg = P.err_grad(gs, ref) / tg
+            assert bg >= MARGIN, (cid, b, bg)
+            worst_bite = min(worst_bite, bg)
+        worst_reach = max(worst_reach, r)
+    _report(cid, worst_reach, worst_bite)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.POST_CASES])
+def test_posterior_and_predict(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, kap = P.problem(cid)
+    n, st, fm, k = len(X), c["stationary"], c["form"], kap[0]
+    ad = np.broadcast_to(alpha, (n,))
+    ref = P.ref_post(cid)
+    L, Ki, a = O.posterior(X, y, ad, H[0], st, fm)
+    errs = {"L": P.err_L(L, ref), "alpha": P.err_alpha(a, ref), "K_inv": P.err_K_inv(Ki, ref["K_inv"])}
+    Xq = P.query(cid)
+    for nz in (False, True):
+        pr = P.ref_predict(cid, nz)
+        mo, so, co = O.predict(X, y, ad, H[0], Xq, st, fm, noise_zero=nz, return_cov=True)
+        pv = P.prior_var(cid, nz)
+        errs["mean"] = max(errs.get("mean", 0), P.err_rel_max(mo, pr["mean"], P.mean_scale(cid)))
+        errs["var"] = max(errs.get("var", 0), P.err_rel_max(so**2, np.maximum(P.f(pr["var"]), 0), pv),
+                          P.err_rel_max(co, pr["cov"], pv))
+    worst = max(e / P.tol(q, k, n) for q, e in errs.items())
+    assert worst <= 1 / MARGIN, (cid, {q: (e, P.tol(q, k, n)) for q, e in errs.items()})
+    # bites: the inputs rounded to fp32 move the mean and the variance by >= 10 tol
+    pr = P.ref_predict(cid, False)
+    m32, s32 = O.predict(P.to32(X), y, ad, H[0], P.to32(Xq), st, fm)
+    bite = min(P.err_rel_max(m32, pr["mean"], P.mean_scale(cid)) / P.tol("mean", k, n),
+               P.err_rel_max(s32**2, pr["var"], P.prior_var(cid, False)) / P.tol("var", k, n))
+    assert bite >= MARGIN, (cid, bite)
+    _report(cid, worst, bite)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.WARP_CASES])
+def test_warped_lml(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, _ = P.problem(cid)
+    Xw, W, kap = P.warped_problem(cid)
+    n, st, fm = len(X), c["stationary"], c["form"]
+    ad = np.broadcast_to(alpha, (n,))
+    worst = 0.0
+    for b in range(len(H)):
+        ref = hp.lml(Xw[b], y, alpha, H[b], st, fm)
+        v = O.lml_warped(X, y, ad, H[b], W[b], st, fm)
+        sens = P.err_lml(O.lml(P.to32(P.f(Xw[b])), y, ad, H[b], st, fm), ref) / P.F32
+        t = P.tol("lml", kap[b], n, sens)
+        worst = max(worst, P.err_lml(v, ref) / t)
+        assert P.err_lml(v, ref) <= t / MARGIN, (cid, b, P.err_lml(v, ref), t)
+        assert P.err_lml(O.lml_warped(P.to32(X), y, ad, H[b], W[b], st, fm), ref) >= MARGIN * t
+    # context-level warp: posterior alpha and predict on warped inputs (scipy's Beta CDF in fp64)
+    sw = P.ref_set_warp(cid)
+    Xw64, Xqw64 = O.warp_inputs(X, sw["W"]), O.warp_inputs(P.query(cid), sw["W"])
+    m64, s64 = O.predict(Xw64, y, ad, H[0], Xqw64, st, fm)
+    got = {"alpha": O.posterior(Xw64, y, ad, H[0], st, fm)[2], "mean": m64, "var": s64**2}
+    for q in ("alpha", "mean", "var"):
+        t = P.tol(q, sw["kappa"], n, sw["sens"][q])
+        e = P.err_rel_max(got[q], sw["ref"][q], sw["scale"][q])
+        assert e <= t / MARGIN, (cid, q, e, t)
+        worst = max(worst, e / t)
+    _report(cid, worst)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.PVRS_CASES])
+def test_pvrs(cid):
+    c = P.ALL[cid]
+    X, _y, alpha, H, kap = P.problem(cid)
+    Xc, Xt = P.pvrs_inputs(cid)
+    got = O.pvrs_covs(X, alpha if c["vec_alpha"] else None, H[0], Xc, Xt, c["stationary"], c["form"])
+    ref = P.ref_pvrs(cid)
+    t = P.tol("pvrs", kap[0], len(X))
+    e = P.err_rel_max(got, ref) / t
+    assert e <= 1 / MARGIN
+    got32 = P.pvrs_gram32(X, alpha if c["vec_alpha"] else None, H[0], Xc, Xt, c["stationary"], c["form"])
+    bite = P.err_rel_max(got32, ref) / t
+    assert bite >= MARGIN, (cid, bite)
+    _report(cid, e, bite)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.SAMPLE_CASES])
+def test_sample_y(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, kap = P.problem(cid)
+    Xq, z = P.query(cid), P.sample_z(cid)
+    mean, _s, cov = O.predict(X, y, np.broadcast_to(alpha, (len(X),)), H[0], Xq, c["stationary"], c["form"],
+                              noise_zero=True, return_cov=True)
+    Lc = np.linalg.cholesky(cov + P.SAMPLE_JITTER * np.eye(len(Xq)))
+    got = mean[None, :] + z @ Lc.T
+    t = P.tol("sample", P.sample_kappa(cid), len(X))
+    e = P.err_rel_max(got, P.ref_sample(cid)) / t
+    assert e <= 1 / MARGIN
+    # bites: the predictive covariance rounded to fp32 before its factorisation
+    C32 = P.to32(cov) + P.SAMPLE_JITTER * np.eye(len(Xq))
+    bite = P.err_rel_max(mean[None, :] + z @ np.linalg.cholesky(C32).T, P.ref_sample(cid)) / t
+    assert bite >= MARGIN, (cid, bite)
+    _report(cid, e, bite)

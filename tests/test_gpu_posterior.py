@@ -3,6 +3,7 @@ the golden vectors (sklearn 1.7.2; reference bask.acquisition via tier-1 import)
 import numpy as np
 import pytest
 
+from _precision import grad_vs_fp64
 from conftest import assert_variance_close, load_golden, synth
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +82,9 @@ def test_lml_gradient(lib):
         assert np.all(status == 0)
         np.testing.assert_allclose(val, g[pre + "lml"], rtol=RTOL)
         np.testing.assert_allclose(grad, g[pre + "grad"], rtol=1e-5, atol=1e-6)
+        for b in range(len(grad)):  # the precision model (tests/_precision.py)
+            err, t = grad_vs_fp64(grad[b], g[pre + "X"], g[pre + "y"], 1e-10, np.atleast_2d(g[pre + "theta"])[b], st, form)
+            assert err <= t, (c, b, err, t)
         ctx.close()
 
 
@@ -96,6 +100,8 @@ def test_lml_gradient_many_dims_and_tiles(lib):
     vo, go = O.lml_and_grad(X, y, np.full(n, 1e-10), th)
     np.testing.assert_allclose(val[0], vo, rtol=RTOL)
     np.testing.assert_allclose(grad[0], go, rtol=1e-5, atol=1e-6)
+    err, t = grad_vs_fp64(grad[0], X, y, 1e-10, th)  # the precision model (tests/_precision.py)
+    assert err <= t, (err, t)
     ctx.close()
 
 

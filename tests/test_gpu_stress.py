@@ -10,6 +10,8 @@ checked at cond-scaled tolerances and their worst errors are printed (``pytest -
 import numpy as np
 import pytest
 
+from _precision import grad_vs_fp64
+
 pytestmark = pytest.mark.gpu
 
 STATS = ["rbf", "matern12", "matern32", "matern52"]
@@ -57,6 +59,8 @@ def test_random_problem_matches_oracle(lib, O, seed):
         l0, g0 = O.lml_and_grad(X, y, alpha, h, stationary=stat, form=form)
         np.testing.assert_allclose(l1[0], l0, rtol=1e-7, atol=1e-9)
         np.testing.assert_allclose(g1[0], g0, rtol=1e-5, atol=1e-6 * (1 + np.abs(g0).max()))
+        err, t = grad_vs_fp64(g1[0], X, y, alpha, h, stat, form)  # the precision model (tests/_precision.py)
+        assert err <= t, (err, t)
         cond = np.linalg.cond(O.gram_with_jitter(X, alpha, h, stationary=stat, form=form))
         # 1e-6 below the bound; beyond it the digits go at cond * eps on either path (factor 50: two n^3 passes)
         tol = 1e-6 if cond <= COND_BOUND else max(1e-6, 50 * cond * np.finfo(float).eps)
