@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- the BASELINE.json headline metric on MI355X: MCMC LML-evaluations/s of the BayesGPR
-hot path at n=2048 (config C: d=16, Matern-5/2 ARD + White, 256 walkers), plus the roofline of the
-dominant kernel (fp64-MFMA trailing update of the blocked Cholesky) and a CPU baseline.
+hot path at n=2048 (config C: d=16, Matern-5/2 ARD + White, 256 walkers); with --full also the roofline
+of the dominant kernel (fp64-MFMA trailing update of the blocked Cholesky), the other BASELINE
+configurations and the CPU baselines.
 
 A "step" is one ensemble-MCMC step = two half-steps, each one batched device call that builds,
 factorises and scores W/2 = 128 kernel matrices; K steps = 256*K LML evaluations.
 Inputs (X, y, walker positions) are resident / tiny; only (128, 18) doubles of proposals go up and
 128 log-likelihoods come back per half-step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set-up, the warm-up, three timed passes of K steps, the
+--dump-outputs arrays, the line.  --full adds, behind the same timed passes and without changing them: the
+instrumented one-stream pass (`roofline`, `roofline_kernels`, `kernel_ms_per_half_step`, `end_to_end`), the live
+HBM-traffic passes, the final chain gather, at N > 1 the other sharding and the collective alone, and at N = 1
+`shard_ms`, `fit_plus_sample_ms`, `roofline_n4096`, `launch_free`, configs A / B / E and the CPU baselines
+(--no-extras / --no-cpu-baseline / --no-live-pmc leave parts of that out).
 
 N > 1, one process per GPU either way: without a launcher's RANK / WORLD_SIZE in the environment `bench.py --gpus N`
 starts its N ranks itself (fresh child processes, before this process has imported the package or made any HIP
@@ -145,7 +153,7 @@ def _kill_group(proc, grace=3.0):
 
 def live_pmc_traffic(kernel_sub="syrk4_kernel", timeout_s=240):
     """HBM bytes per launch of the trailing-update kernel, collected NOW: two child runs of this script's hot path
-    (`--steps 1 --warmup 1 --no-extras`, one stream) under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` and
+    (`--steps 1 --warmup 1 --full --no-extras`, one stream) under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` and
     `... --pmc WRITE_SIZE` (separate passes, MI355X_MICROARCH.md section HBM), FETCH_SIZE x 2 (gfx950 correction for
     wide coalesced reads) + WRITE_SIZE, counters in KiB.  None when rocprofv3 is missing or a pass fails."""
     import glob
@@ -165,7 +173,7 @@ def live_pmc_traffic(kernel_sub="syrk4_kernel", timeout_s=240):
         out = tempfile.mkdtemp(prefix="bgp_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", out, "-o", "pmc", "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-extras"]
+                   os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full", "--no-extras"]
             # own session: on a timeout the whole group goes (rocprofv3 AND the bench it started), so nothing of this
             # pass can linger on the GPU under the measurements that follow
             proc = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
@@ -788,18 +796,33 @@ def setup_config_c(bask, device, seed_gp, W=N_WALKERS):
     return gp, X, y, priors, theta0, pos
 
 
+def emit(line, rank, grouped):
+    """Rank 0 prints the ONE JSON line; every rank of a group then leaves it together."""
+    from bayes_skopt_amd import distributed
+
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if grouped:
+        distributed.barrier()
+        distributed.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed passes, measure everything else the line can carry (instrumented pass and "
+                    "rooflines, HBM traffic, other configurations and shardings, CPU baselines); off: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the config C hot path (no fit(), no configs B / D / E, no CPU baselines): what the "
-                    "rocprofv3 passes of tools/profile_round.sh run, so that their per-kernel numbers are config C's alone")
+                    help="with --full: only the config C hot path and its instrumented pass (no fit(), no configs B / D / E, "
+                    "no CPU baselines): what the profiler passes of tools/profile_round.sh run, so that their per-kernel "
+                    "numbers are config C's alone")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not collect roofline.traffic with two rocprofv3 --pmc child passes (~25 s); use the "
-                    "newest committed profiles/rNN[_vK]_pmc_traffic.json instead")
+                    help="with --full: do not collect roofline.traffic with two rocprofv3 --pmc child passes (~25 s); use "
+                    "the newest committed profiles/rNN[_vK]_pmc_traffic.json instead")
     ap.add_argument("--shard", choices=("ensemble", "chains"), default="ensemble",
                     help="N > 1 only.  ensemble (default; BASELINE config C as stated, the reference's semantics): ONE "
                     "256-walker ensemble, each half-step's 128 proposals split over the GPUs + a device-to-device "
@@ -896,6 +919,52 @@ def main():
         np.save(os.path.join(args.dump_outputs, "coords.npy"), np.ascontiguousarray(pos, dtype=np.float64))
         np.save(os.path.join(args.dump_outputs, "log_prob.npy"), np.ascontiguousarray(lp, dtype=np.float64))
 
+    evals = W * args.steps * (1 if (ensemble or ws == 1) else ws)
+    value = evals / dt
+    B = W // 2
+    if ensemble:  # this rank's share of every proposal block
+        lo, hi = distributed.shard_rows(B, rank, ws)
+        B = hi - lo
+    line = {
+        "metric": "mcmc_lml_evals_per_s_n2048",
+        "value": value,
+        "unit": "LML-evals/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "timed_passes_ms_per_step": [t / args.steps * 1e3 for t in passes],
+        "value_is": "the median of three timed passes of exactly `steps` steps each",
+        "sampler": ("device-resident (bgp_mcmc_begin_ex / _steps / _end: no transfer or host synchronisation between half-steps"
+                    + ("; the ranks' log-likelihoods all-gathered on the context's stream)" if ensemble else ")"))
+                   if resident_runs else "host-driven (one LML batch call" + (" + one all-gather" if ensemble else "") + " per half-step)",
+        "resident": bool(resident_runs),
+        "env_defaults": _lib.env_defaults(),
+        "higher_is_better": True,
+        "scaling": "strong" if ensemble else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": "BASELINE config C: BayesGPR hyper-posterior MCMC, n=2048, d=16, c*Matern52(ARD)+White, "
+            + ("ONE 256-walker ensemble, the 128 proposals of each half-step split over the GPUs and their "
+               "log-likelihoods all-gathered device to device over RCCL, " if ensemble else
+               "256 walkers per GPU (128 batched kernel-build+Cholesky+LML per half-step), ")
+            + "start ball of bask/bayesgpr.py:506-509, default priors",
+            "n": n,
+            "d": d,
+            "walkers_total": W if (ensemble or ws == 1) else W * ws,
+            "proposals_per_gpu_per_half_step": B,
+            "parallelism": f"ensemble_sharded{ws}" if ensemble else f"chains{ws}",
+        },
+        "dist_backend": info["backend"],
+        "rccl_nranks": info["rccl_nranks"],
+        "rank_devices": info["rank_devices"],
+    }
+    if not args.full:  # the headline alone
+        return emit(line, rank, grouped)
+
+    # --full from here on: every figure below comes from work of its own behind the timed passes
     # final posterior-sample gather (RCCL over xGMI when N > 1; the shared ensemble's chain is on every rank already)
     tg = time.perf_counter()
     chain_local = sampler.get_chain(flat=True, discard=max(args.warmup, 1) + 2 * args.steps)  # (the last timed pass's steps)
@@ -948,10 +1017,6 @@ def main():
     gp._ctx.set_timing(False)
     gp.resident_sampler = True
 
-    B = W // 2
-    if ensemble:  # this rank's share of every proposal block
-        lo, hi = distributed.shard_rows(B, rank, ws)
-        B = hi - lo
     fl = trailing_flops_per_launch(n)
     syrk_ms, syrk_launches = acc["syrk"]
     flops_per_call = float(sum(fl)) * B
@@ -1090,40 +1155,7 @@ def main():
                                      note="peak = 128 dependent pivots x %.0f ns (the in-register pivot chain alone, tools/potrf_bench); "
                                      "frac = that floor / the measured launch" % PIVOT_CHAIN_NS))
 
-    evals = W * args.steps * (1 if (ensemble or ws == 1) else ws)
-    value = evals / dt
-    line = {
-        "metric": "mcmc_lml_evals_per_s_n2048",
-        "value": value,
-        "unit": "LML-evals/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "timed_passes_ms_per_step": [t / args.steps * 1e3 for t in passes],
-        "value_is": "the median of three timed passes of exactly `steps` steps each",
-        "sampler": ("device-resident (bgp_mcmc_begin_ex / _steps / _end: no transfer or host synchronisation between half-steps"
-                    + ("; the ranks' log-likelihoods all-gathered on the context's stream)" if ensemble else ")"))
-                   if resident_runs else "host-driven (one LML batch call" + (" + one all-gather" if ensemble else "") + " per half-step)",
-        "resident": bool(resident_runs),
-        "env_defaults": _lib.env_defaults(),
-        "higher_is_better": True,
-        "scaling": "strong" if ensemble else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": "BASELINE config C: BayesGPR hyper-posterior MCMC, n=2048, d=16, c*Matern52(ARD)+White, "
-            + ("ONE 256-walker ensemble, the 128 proposals of each half-step split over the GPUs and their "
-               "log-likelihoods all-gathered device to device over RCCL, " if ensemble else
-               "256 walkers per GPU (128 batched kernel-build+Cholesky+LML per half-step), ")
-            + "start ball of bask/bayesgpr.py:506-509, default priors",
-            "n": n,
-            "d": d,
-            "walkers_total": W if (ensemble or ws == 1) else W * ws,
-            "proposals_per_gpu_per_half_step": B,
-            "parallelism": f"ensemble_sharded{ws}" if ensemble else f"chains{ws}",
-        },
+    line.update({
         "roofline": roofline,
         "roofline_kernels": roofline_kernels,
         "end_to_end": {
@@ -1137,12 +1169,9 @@ def main():
         "device_ms_per_half_step": dev_total / max(n_calls, 1),
         "instrumented_ms_per_step": dt_instr / args.steps * 1e3,
         "gather_ms": gather_ms,
-        "dist_backend": info["backend"],
-        "rccl_nranks": info["rccl_nranks"],
-        "rank_devices": info["rank_devices"],
         "gathered_chain_rows": int(chain_all.shape[0]),
         "acceptance_fraction": float(np.mean(sampler.acceptance_fraction)),
-    }
+    })
     ps = gp._ctx.persist_stats()
     line["launch_free_calls_in_timed_path"] = {"calls": ps["calls"], "timeouts": ps["timeouts"]}
     if grouped:
@@ -1260,10 +1289,7 @@ def main():
                 line["cpu_baseline_sklearn"] = sk
             except Exception as exc:  # reported, never fatal for the bench line
                 line["cpu_baseline_sklearn"] = {"error": repr(exc)}
-        print(json.dumps(line), flush=True)
-    if grouped:
-        distributed.barrier()
-        distributed.destroy_process_group()
+    emit(line, rank, grouped)
 
 
 if __name__ == "__main__":

@@ -470,7 +470,8 @@ def test_bench_two_ranks_through_the_native_backends_host_side(tmp_path, shard):
     communicator and context, tests/_stub_rccl_bench.py): the group that forms is reported as the native one (`dist_backend`,
     `rccl_nranks` = 2, a device per rank out of the 8 visible ones), the sharded log-probability takes its native branch (submit ->
     collective with status words), the line carries the N > 1 keys."""
-    outs, _ = _stub_ranks(2, "bench", ["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras", "--shard", shard], tmp_path)
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--shard", shard]
+    outs, _ = _stub_ranks(2, "bench", args, tmp_path)
     assert [rc for rc, _o, _e in outs] == [0, 0], outs[0][2][-1500:] + outs[1][2][-1500:]
     lines = [ln for ln in outs[0][1].splitlines() if ln.strip()]
     assert len(lines) == 1 and not outs[1][1].strip()
@@ -483,6 +484,26 @@ def test_bench_two_ranks_through_the_native_backends_host_side(tmp_path, shard):
         assert d["config"]["walkers_total"] == 256 and d["gathered_chain_rows"] == 2 * 256
     else:
         assert d["scaling"] == "weak" and d["strong_ensemble_evals_per_s"] > 0 and d["gathered_chain_rows"] == 2 * 2 * 256
+
+
+@pytest.mark.parametrize("shard", ["ensemble", "chains"])
+def test_bench_plain_two_rank_line_is_the_headline_alone(tmp_path, shard):
+    """Without --full the N > 1 job stops behind its three timed passes: the line says what was timed and what group formed,
+    nothing measured afterwards (no gather, no other sharding, no collective alone, no instrumented pass), and both ranks
+    leave the native group cleanly."""
+    outs, _ = _stub_ranks(2, "bench", ["--gpus", "2", "--steps", "2", "--warmup", "1", "--shard", shard], tmp_path)
+    assert [rc for rc, _o, _e in outs] == [0, 0], outs[0][2][-1500:] + outs[1][2][-1500:]
+    lines = [ln for ln in outs[0][1].splitlines() if ln.strip()]
+    assert len(lines) == 1 and not outs[1][1].strip()
+    d = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"} <= set(d)
+    assert d["n_gpus"] == 2 and d["dist_backend"] == "rccl" and d["rccl_nranks"] == 2 and d["rank_devices"] == [0, 1]
+    assert len(d["timed_passes_ms_per_step"]) == 3 and sorted(d["timed_passes_ms_per_step"])[1] == d["ms_per_step"]
+    walkers = 256 if shard == "ensemble" else 2 * 256
+    assert abs(d["value"] - walkers * 2 / (d["ms_per_step"] * 2 * 1e-3)) / d["value"] < 1e-9
+    assert d["scaling"] == ("strong" if shard == "ensemble" else "weak")
+    assert not {"roofline", "kernel_ms_per_half_step", "gathered_chain_rows", "collective_ms_per_half_step",
+                "weak_chains_evals_per_s", "strong_ensemble_evals_per_s", "acceptance_fraction"} & set(d)
 
 
 def test_a_rank_interrupted_inside_a_half_step_takes_the_native_group_down(tmp_path):

@@ -1,5 +1,6 @@
-"""bench.py contract: one JSON line with the driver's keys plus `roofline`, on one GPU and as a 2-rank job
-(both ranks on GPU 0 over gloo -- the box has one device) in both sharding modes."""
+"""bench.py contract: one JSON line with the driver's keys -- the headline alone on a plain run, plus `roofline` and the
+rest with --full -- on one GPU and as a 2-rank job (both ranks on GPU 0 over gloo -- the box has one device) in both
+sharding modes."""
 import json
 import os
 import socket
@@ -33,7 +34,7 @@ def _line(res):
 
 
 def test_bench_single_gpu_line():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=1500)
     d = _line(res)
     assert KEYS <= set(d)
@@ -120,6 +121,23 @@ def test_bench_single_gpu_line():
     assert "EXTRAPOLATED" in d["cpu_fit_plus_sample"]["label"]
 
 
+def test_bench_plain_line_is_the_headline_alone():
+    """Without --full: set-up, warm-up, the three timed passes and the line -- the same headline keys meaning the same things,
+    and nothing that takes work of its own afterwards (instrumented pass, rooflines, other configurations, CPU baselines)."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=900)
+    d = _line(res)
+    assert KEYS - {"roofline"} <= set(d)
+    assert d["metric"] == "mcmc_lml_evals_per_s_n2048" and d["unit"] == "LML-evals/s" and d["n_gpus"] == 1
+    assert d["dtype"] == "f64" and d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 256 * 2 / (d["ms_per_step"] * 2 * 1e-3)) / d["value"] < 1e-9
+    tp = d["timed_passes_ms_per_step"]
+    assert len(tp) == 3 and sorted(tp)[1] == d["ms_per_step"] and d["resident"] is True and d["sampler"].startswith("device-resident")
+    assert not {"roofline", "roofline_kernels", "end_to_end", "kernel_ms_per_half_step", "instrumented_ms_per_step",
+                "gathered_chain_rows", "shard_ms", "fit_plus_sample_ms", "roofline_n4096", "launch_free", "config_A",
+                "config_B", "config_E", "cpu_baseline", "cpu_baseline_sklearn", "cpu_fit_plus_sample"} & set(d)
+
+
 def test_bench_spawns_its_own_ranks_without_a_launcher():
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment (how the driver calls it): the parent starts two
     fresh rank processes itself, both on GPU 0 here (one device on the box -> the ranks agree on gloo: RCCL refuses two
@@ -128,7 +146,7 @@ def test_bench_spawns_its_own_ranks_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT",
                                                             "BGP_DIST_BACKEND")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     d = _line(res)
     assert KEYS <= set(d) and d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["config"]["parallelism"] == "ensemble_sharded2" and d["config"]["proposals_per_gpu_per_half_step"] == 64
@@ -144,7 +162,7 @@ def test_bench_two_ranks_on_one_gpu(shard):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", BGP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--shard", shard]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--shard", shard]
     d = _line(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900))
     assert KEYS <= set(d) and d["n_gpus"] == 2
     if shard == "chains":   # independent 256-walker sub-ensemble per rank: whole-job evaluations = 2 x

@@ -110,7 +110,7 @@ def test_bench_line_through_native_rccl_group():
     env = dict(os.environ, BGP_DIST_FORCE="1", BGP_DIST_BACKEND="rccl", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--no-extras"]
+           "--warmup", "1", "--full", "--no-extras"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     # the bench line is the ONLY thing on standard output: RCCL's start-up banner ("RCCL version : ...") goes to stderr

@@ -22,7 +22,7 @@ def per_kernel(db, sub):
 
 def main():
     out, fdb, wdb, mdb, sub = sys.argv[1:6]
-    what = sys.argv[6] if len(sys.argv) > 6 else "tools/profile_round.sh: bench.py --steps 2 --warmup 1 --no-extras (config C only)"
+    what = sys.argv[6] if len(sys.argv) > 6 else "tools/profile_round.sh: bench.py --steps 2 --warmup 1 --full --no-extras (config C only)"
     f = per_kernel(fdb, sub)["FETCH_SIZE"]
     w = per_kernel(wdb, sub)["WRITE_SIZE"]
     m = per_kernel(mdb, sub)

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
-rocprofv3 --kernel-trace -d $OUT -o ${TAG} -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-extras > $OUT/${TAG}.log 2>&1
+rocprofv3 --kernel-trace -d $OUT -o ${TAG} -- python3 $ROOT/bench.py --steps 3 --warmup 1 --full --no-extras > $OUT/${TAG}.log 2>&1
 DB=$(find $OUT -name "${TAG}_results.db" | head -1)
 python3 $ROOT/tools/rocprof_overlap.py $DB 1500 90 > $OUT/${TAG}_overlap.txt
 python3 $ROOT/tools/rocprof_gaps.py $DB 1500 > $OUT/${TAG}_gaps.txt

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the parts of a bench.py line that the round's review items are about."""
+"""Print the parts of a `bench.py --full` line that the round's review items are about."""
 import json, sys
 d = json.load(open(sys.argv[1]))
 print("value", d["value"], "ms/step", d["ms_per_step"], "frac", d["roofline"]["frac"], "e2e", d["end_to_end"]["frac"])
