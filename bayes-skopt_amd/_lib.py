@@ -88,6 +88,9 @@ SIGNATURES = {
     "bgp_fantasy_moments": (C.c_int, [_vp, _dp, _dp]),
     "bgp_fantasy_end": (C.c_int, [_vp]),
     "bgp_fantasy_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
+                                      C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -573,6 +576,44 @@ class Context:
         out = (C.c_longlong * 2)()
         _check(self._lib.bgp_fantasy_stats(self._h, out), "bgp_fantasy_stats")
         return {"begins": int(out[0]), "steps": int(out[1])}
+
+    # ---- prediction gradients and the device-resident optimum search (bgp_predgrad.hip)
+    def predict_grad(self, H_kernel, Xq, want_dvar=True):
+        """(mean (B, m), var (B, m), dmean (B, m, d), dvar (B, m, d) | None) of the resident posteriors at the rows of ``Xq``
+        (``bgp_predict_grad_batch``; normalised-target units).  Needs d <= 32 and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xq = _c(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"query points must have {self.d} columns, got {Xq.shape[1]}")
+        m = Xq.shape[0]
+        mean, var = np.empty((B, m)), np.empty((B, m))
+        dmean = np.empty((B, m, self.d))
+        dvar = np.empty((B, m, self.d)) if want_dvar else None
+        _check(self._lib.bgp_predict_grad_batch(self._h, B, _p(H), m, _p(Xq), _p(mean), _p(var), _p(dmean),
+                                                _p(dvar) if want_dvar else C.cast(None, _dp)), "bgp_predict_grad_batch")
+        return mean, var, dmean, dvar
+
+    def minimize_starts(self, b, H_kernel, y_mean, y_std, kappa, X0, lo, hi, gtol=1e-5, max_iter=200):
+        """``bgp_minimize_starts``: minimise ``y_mean + y_std mean(x) + kappa y_std sqrt(var(x))`` of resident posterior ``b``
+        (``H_kernel``: its d + 2 kernel parameters, or the block of all resident posteriors) over the box [lo, hi] from every row
+        of ``X0``, in one launch.  Returns a dict: x (S, d), mean, var (S,; normalised units, the bits of ``predict_grad`` at x),
+        iters, evals, status (S,; 0 converged to ``gtol``, 1 ``max_iter`` reached, 2 no decrease found)."""
+        H = self._H(H_kernel)
+        h = _c(H[int(b)] if H.shape[0] > 1 else H[0])
+        X0 = _c(np.atleast_2d(X0))
+        S, d = X0.shape
+        lo = _c(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.d,)))
+        hi = _c(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.d,)))
+        if d != self.d:
+            raise ValueError(f"start points must have {self.d} columns, got {d}")
+        x = np.empty((S, d))
+        mean, var = np.empty(S), np.empty(S)
+        iters, evals, status = (np.zeros(S, dtype=np.int32) for _ in range(3))
+        _check(self._lib.bgp_minimize_starts(self._h, int(b), _p(h), float(y_mean), float(y_std), float(kappa), S, _p(X0), _p(lo),
+                                             _p(hi), float(gtol), int(max_iter), _p(x), _p(mean), _p(var), _p(iters), _p(evals),
+                                             _p(status)), "bgp_minimize_starts")
+        return {"x": x, "mean": mean, "var": var, "iters": iters, "evals": evals, "status": status}
 
     def sample_y(self, b, h_kernel, Xq, z, jitter=0.0):
         H = self._H(h_kernel)

@@ -134,6 +134,24 @@ class CanonicalPosterior:
         grad = (cst if product else 1.0) * fac[:, None] * diff / ell2  # (Constant / White terms: zero)
         return grad, (cst * S if product else cst + S)
 
+    def device_gradients(self, gp):
+        """The device gradient kernels serve this estimator (``bgp_predict_grad_batch``'s limits: d <= 32, no input warp)."""
+        return not gp.warp_inputs and gp._X_train_.shape[1] <= 32
+
+    def predict_grad(self, gp, X, want_dvar=True):
+        """(mean (m,), var (m,), dmean (m, d), dvar (m, d) | None) of the resident posterior at the rows of X, with the kernel
+        parameters currently in ``kernel_``."""
+        self.make_resident(gp)
+        mean, var, dmean, dvar = gp._ctx.predict_grad(gp._canonical(gp._kernel_theta_for_predict()), X, want_dvar=want_dvar)
+        return mean[0], var[0], dmean[0], (dvar[0] if want_dvar else None)
+
+    def minimize(self, gp, kappa, X0, lo, hi, gtol=1e-5, max_iter=200):
+        """Minima of mean + kappa std (y units) of the resident posterior over the box from every start, in one launch."""
+        self.make_resident(gp)
+        y_mean, y_std = float(np.ravel(gp.y_train_mean_)[0]), float(np.ravel(gp.y_train_std_)[0])
+        return gp._ctx.minimize_starts(0, gp._canonical(gp._kernel_theta_for_predict()), y_mean, y_std, kappa, X0, lo, hi,
+                                       gtol=gtol, max_iter=max_iter)
+
     def pvrs(self, gp, X, T, has_alpha_vec):
         Hk = gp._canonical(gp._kernel_theta_for_predict())
         raise_if_not_pd(gp._ctx.pvrs_prepare(Hk, has_alpha_vec))

@@ -666,6 +666,36 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             grad_std = -(k_trans @ (self.K_inv_ @ grad)) / y_std[0] * self.y_train_std_**2
         return grad_mean, grad_std
 
+    def predict_gradients(self, X, return_std=True):
+        """Predictive mean, std and their gradients at ANY number of query rows: ``(mean (m,), std (m,), grad_mean (m, d),
+        grad_std (m, d))`` in y units, or ``(mean, grad_mean)`` with ``return_std=False`` -- what
+        ``predict(x, return_std=True, return_mean_grad=True, return_std_grad=True)`` returns one point at a time (the reference
+        raises for more than one row, and so does ``predict``).  Same normalisation, and the same rule for a vanishing std:
+        where ``std <= 1e-8`` (``np.allclose(std, 0)``) ``grad_std`` is zero.  Canonical kernels in up to 32 dimensions without
+        input warping: one device call for all rows (``bgp_predict_grad_batch``).  Warped inputs and
+        generic kernel trees: the one-point routine row by row, with its results."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if self.warp_inputs:
+            validate_zeroone(X)
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        if not (self._post.canonical and self._post.device_gradients(self)):
+            rows = [self.predict(x[None, :], return_std=return_std, return_mean_grad=True, return_std_grad=return_std) for x in X]
+            if return_std:
+                return (np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows]),
+                        np.stack([r[2] for r in rows]), np.stack([r[3] for r in rows]))
+            return np.concatenate([r[0] for r in rows]), np.stack([r[1] for r in rows])
+        mean, var, dmean, dvar = self._post.predict_grad(self, X, want_dvar=return_std)
+        y_mean = self.y_train_std_ * mean + self.y_train_mean_
+        grad_mean = dmean * self.y_train_std_
+        if not return_std:
+            return y_mean, grad_mean
+        y_std = np.sqrt(var * self.y_train_std_**2)
+        grad_std = np.zeros_like(dvar)
+        nz = ~(np.abs(y_std) <= 1e-8)  # (np.allclose(std, 0.0) of the one-point routine, row by row)
+        grad_std[nz] = dvar[nz] / (2.0 * y_std[nz])[:, None] * self.y_train_std_**2
+        return y_mean, y_std, grad_mean, grad_std
+
     @contextmanager
     def _row_warps(self):
         """Yields ``install(row)``, which gives the estimator chain row ``row``'s own input warp (its own training inputs)

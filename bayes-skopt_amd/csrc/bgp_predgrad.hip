@@ -1,0 +1,511 @@
+// Prediction gradients for many query rows and the device-resident optimum search.
+//
+// With G_i = d k(x, X_i) / dx = cf fac(r_i) (x - X_i) / l^2  (cf = c in the product form, 1 in the sum form; fac(r) = (dS/dr) / r in
+// the closed forms of _posterior.CanonicalPosterior.grad_x, 0 at r = 0 for Matern 1/2; the constant and white terms add nothing):
+//   mean = sum_i alpha_i k_i            dmean = sum_i alpha_i G_i
+//   v    = K^-1 k                       var   = max(0, k_** - k^T v)            dvar = -2 sum_i v_i G_i
+// ONE __device__ function, pg_eval, evaluates all of it for one query point with one workgroup of PG_NT threads:
+//   pass 1  every thread takes a strided share of the training points, writes k_i and g_i = cf fac_i to the workgroup's row
+//           buffers (LDS up to PG_NLDS points, a device scratch row beyond) and accumulates the mean; then dmean, lane t of a wave
+//           owning dimension t over the wave's share of the points; a fixed butterfly inside every wave, then the wave partials in
+//           ascending order;
+//   pass 2  (variance wanted) v_j by row-wise dot products of the symmetric resident inverse against k -- one wave per group of four
+//           rows, coalesced row reads, n^2 doubles per evaluation out of L2 / the Infinity Cache: that is its floor --, and from v_j at
+//           once the sum of k^T v; g_j becomes v_j g_j and dvar is the contraction of dmean once more.
+// bgp_predict_grad_batch runs it on one workgroup per (query row, posterior); bgp_minimize_starts on one workgroup per start, which
+// carries the whole bounded quasi-Newton iteration itself: no workgroup ever waits for another, every loop has a fixed cap.
+// fp64 VALU work throughout (no MFMA shape); every reduction has a fixed order: results are bitwise reproducible and a row / a start
+// does not depend on what shares its launch.
+#include "bgp_common.h"
+#include "bgp_device.h"
+
+#define PG_NT 512                 // threads of a workgroup
+#define PG_NW (PG_NT / 64)        // its waves
+#define PG_DMAX 32                // input dimensions (the limit of the fantasy fast path): a dimension per lane of half a wave
+#define PG_NLDS 3072              // training points whose k / g rows fit the workgroup's LDS (2 x 24 KB); beyond: device scratch rows
+#define PG_RS (PG_DMAX + 1)       // stride of a wave's partial sums
+#define PG_LS_MAX 30              // cap of the backtracking line search
+#define PG_HS (PG_DMAX + 1)       // row stride of the inverse-Hessian approximation in LDS (32 x 33 doubles: 8.25 KB)
+
+struct PgWork {                   // LDS of one evaluation
+  double x[PG_DMAX];              // the query point
+  double il[PG_DMAX];             // 1 / length scale
+  double red[PG_NW * PG_RS];      // wave partials
+  double mean, var;
+  double dmean[PG_DMAX], dvar[PG_DMAX];
+};
+
+static __device__ __forceinline__ double pg_wave_sum(double s) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+// S(r) and fac(r) = (dS/dr) / r from the squared scaled distance (kb_stationary's expressions for S)
+template <int STAT>
+static __device__ __forceinline__ void pg_stat(double r2, double& S, double& fac) {
+#pragma clang fp contract(off)
+  if (STAT == BGP_RBF) {
+    S = kb_exp_neg(0.5 * r2);
+    fac = -S;
+    return;
+  }
+  const double r = kb_sqrt_pos(r2);
+  if (STAT == BGP_MATERN12) {
+    S = kb_exp_neg(r);
+    fac = (r > 0.0) ? -S / r : 0.0;  // (the r = 0 rule of grad_x)
+    return;
+  }
+  if (STAT == BGP_MATERN32) {
+    const double t = r * 1.7320508075688772;
+    const double e = kb_exp_neg(t);
+    S = (1.0 + t) * e;
+    fac = -3.0 * e;
+    return;
+  }
+  const double t = r * 2.23606797749979;
+  const double e = kb_exp_neg(t);
+  S = (1.0 + t + t * t * 0.3333333333333333) * e;
+  fac = -(5.0 / 3.0) * ((1.0 + t) * e);
+}
+
+// dst[t] = scale il_t sum_i w_i (x_t - X_it) il_t with w_i = a_i gb_i (a == nullptr: gb_i): the contraction of dmean and dvar.  Lane
+// (t, half) of wave wv owns dimension t over the points 2 wv + half, + 2 PG_NW, ...; the two halves, then the waves in ascending
+// order.  Ends with a barrier.
+static __device__ __forceinline__ void pg_wsum(const double* __restrict__ X, int n, int d, const double* __restrict__ a,
+                                               const double* gb, PgWork& W, double scale, double* dst) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, t = lane & 31;
+  double acc = 0.0;
+  if (t < d) {
+    const double xl = W.x[t], ill = W.il[t];
+    for (int i = 2 * wv + (lane >> 5); i < n; i += 2 * PG_NW) {
+      const double w = a ? a[i] * gb[i] : gb[i];
+      acc = fma(w, (xl - X[(size_t)i * d + t]) * ill, acc);
+    }
+  }
+  acc += __shfl_xor(acc, 32, 64);
+  if (lane < d) W.red[wv * PG_RS + 1 + lane] = acc;
+  __syncthreads();
+  if (tid < d) {
+    double s = 0.0;
+    for (int w = 0; w < PG_NW; w++) s += W.red[w * PG_RS + 1 + tid];
+    dst[tid] = scale * (s * W.il[tid]);
+  }
+  __syncthreads();
+}
+
+// mean / dmean (and, with want_var, var / dvar) of one posterior at W.x into W.  Called by every thread of the workgroup; W.x and
+// W.il may have been written just before (the function starts with a barrier) and W's results are visible to every thread on return.
+template <int STAT, int FORM>
+static __device__ __noinline__ void pg_eval(const double* __restrict__ X, int n, int d, const double* __restrict__ alpha,
+                               const double* __restrict__ Kinv, int npad, double cst, double kdiag, bool want_var, double* kb,
+                               double* gb, PgWork& W) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __syncthreads();
+  // pass 1: k_i, g_i = cf fac_i, the mean
+  double am = 0.0;
+  for (int i = tid; i < n; i += PG_NT) {
+    const double* xi = X + (size_t)i * d;
+    double r2 = 0.0;
+    for (int t = 0; t < d; t++) {
+      const double df = (W.x[t] - xi[t]) * W.il[t];
+      r2 = fma(df, df, r2);
+    }
+    double S, fac;
+    pg_stat<STAT>(r2, S, fac);
+    const double k = (FORM == BGP_FORM_PRODUCT) ? cst * S : cst + S;
+    kb[i] = k;
+    gb[i] = (FORM == BGP_FORM_PRODUCT) ? cst * fac : fac;
+    am = fma(k, alpha[i], am);
+  }
+  am = pg_wave_sum(am);
+  if (lane == 0) W.red[wv * PG_RS] = am;
+  __syncthreads();  // (the k / g rows are complete behind it too)
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < PG_NW; w++) s += W.red[w * PG_RS];
+    W.mean = s;
+  }
+  pg_wsum(X, n, d, alpha, gb, W, 1.0, W.dmean);
+  if (!want_var) return;
+  // pass 2: v_j = (K^-1 k)_j, four rows per wave and step; g_j becomes v_j g_j
+  double q = 0.0;
+  for (int j0 = wv * 4; j0 < n; j0 += PG_NW * 4) {  // (rows j0 .. j0 + 3 < npad: a multiple of 128)
+    const double* K0 = Kinv + (size_t)j0 * npad;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int i = lane; i < n; i += 64) {
+      const double kk = kb[i];
+      a0 = fma(K0[i], kk, a0);
+      a1 = fma(K0[(size_t)npad + i], kk, a1);
+      a2 = fma(K0[2 * (size_t)npad + i], kk, a2);
+      a3 = fma(K0[3 * (size_t)npad + i], kk, a3);
+    }
+    const double v[4] = {pg_wave_sum(a0), pg_wave_sum(a1), pg_wave_sum(a2), pg_wave_sum(a3)};
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int j = j0 + r;
+      if (j < n) {
+        q = fma(kb[j], v[r], q);
+        if (lane == 0) gb[j] = v[r] * gb[j];
+      }
+    }
+  }
+  if (lane == 0) W.red[wv * PG_RS] = q;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < PG_NW; w++) s += W.red[w * PG_RS];
+    const double vv = kdiag - s;
+    W.var = vv > 0.0 ? vv : 0.0;  // (clipped at 0 as bgp_predict_batch clips)
+  }
+  pg_wsum(X, n, d, nullptr, gb, W, -2.0, W.dvar);
+}
+
+// the workgroup's k / g rows: dynamic LDS, or its slice of the device scratch
+static __device__ __forceinline__ void pg_rows(double* dyn, double* scratch, int n, int npad, int wg, double*& kb, double*& gb) {
+  if (scratch) {
+    kb = scratch + (size_t)wg * 2 * npad;
+    gb = kb + npad;
+  } else {
+    kb = dyn;
+    gb = dyn + n;
+  }
+}
+
+// one workgroup per (query row, posterior)
+template <int STAT, int FORM>
+__global__ void __launch_bounds__(PG_NT) pg_rows_kernel(const double* __restrict__ X, int n, int d, int npad,
+                                                        const double* __restrict__ alphaB, const double* __restrict__ KinvB,
+                                                        const double* __restrict__ H, const double* __restrict__ Xq, int m,
+                                                        double* scratch, double* __restrict__ mean, double* __restrict__ var,
+                                                        double* __restrict__ dmean, double* __restrict__ dvar) {
+  extern __shared__ double pg_dyn[];
+  __shared__ PgWork W;
+  const int tid = threadIdx.x, i = blockIdx.x, b = blockIdx.y;
+  const double* h = H + (size_t)b * (d + 2);
+  if (tid < d) {
+    W.x[tid] = Xq[(size_t)i * d + tid];
+    W.il[tid] = 1.0 / exp(h[1 + tid]);
+  }
+  const double cst = exp(h[0]);
+  const double kdiag = ((FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0) + exp(h[d + 1]);
+  double *kb, *gb;
+  pg_rows(pg_dyn, scratch, n, npad, b * gridDim.x + i, kb, gb);
+  pg_eval<STAT, FORM>(X, n, d, alphaB + (size_t)b * npad, KinvB + (size_t)b * npad * npad, npad, cst, kdiag, true, kb, gb, W);
+  const size_t o = (size_t)b * m + i;
+  if (tid == 0) {
+    mean[o] = W.mean;
+    var[o] = W.var;
+  }
+  if (tid < d) {
+    dmean[o * d + tid] = W.dmean[tid];
+    if (dvar) dvar[o * d + tid] = W.dvar[tid];
+  }
+}
+
+// f and its gradient (y units) from the evaluation in W; where y_std sqrt(var) <= 1e-8 the std term contributes no gradient
+// (skopt's allclose(std, 0) rule, BayesGPR._predict_gradients)
+static __device__ __forceinline__ double pg_objective(const PgWork& W, double y_mean, double y_std, double kappa) {
+#pragma clang fp contract(off)
+  double f = y_mean + y_std * W.mean;
+  if (kappa != 0.0) f = f + kappa * (y_std * sqrt(W.var));
+  return f;
+}
+static __device__ __forceinline__ double pg_gradient(const PgWork& W, int t, double y_std, double kappa) {
+#pragma clang fp contract(off)
+  double g = y_std * W.dmean[t];
+  if (kappa != 0.0) {
+    const double sd = y_std * sqrt(W.var);
+    if (sd > 1e-8) g = g + kappa * (W.dvar[t] / sd * (0.5 * (y_std * y_std)));
+  }
+  return g;
+}
+
+// One workgroup per start: projected BFGS (dense inverse Hessian in LDS, active set read off the projected gradient, Armijo
+// backtracking along the projected path).  status 0: |projected gradient|_inf <= gtol; 1: max_iter reached; 2: no decrease found.
+template <int STAT, int FORM>
+__global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict__ X, int n, int d, int npad,
+                                                       const double* __restrict__ alpha, const double* __restrict__ Kinv,
+                                                       const double* __restrict__ h, double y_mean, double y_std, double kappa,
+                                                       const double* __restrict__ X0, const double* __restrict__ lo_,
+                                                       const double* __restrict__ hi_, double gtol, int max_iter, double* scratch,
+                                                       double* __restrict__ X_out, double* __restrict__ mean_out,
+                                                       double* __restrict__ var_out, int* __restrict__ iters,
+                                                       int* __restrict__ evals, int* __restrict__ status) {
+#pragma clang fp contract(off)
+  extern __shared__ double pg_dyn[];
+  __shared__ PgWork W;
+  __shared__ double Hm[PG_DMAX * PG_HS];
+  __shared__ double x[PG_DMAX], g[PG_DMAX], p[PG_DMAX], sv[PG_DMAX], yv[PG_DMAX], Hy[PG_DMAX], lo[PG_DMAX], hi[PG_DMAX];
+  __shared__ int act[PG_DMAX];
+  const int tid = threadIdx.x, s = blockIdx.x;
+  const bool wantv = kappa != 0.0;
+  if (tid < d) {
+    lo[tid] = lo_[tid];
+    hi[tid] = hi_[tid];
+    double v = X0[(size_t)s * d + tid];
+    v = v < lo[tid] ? lo[tid] : (v > hi[tid] ? hi[tid] : v);
+    x[tid] = v;
+    W.x[tid] = v;
+    W.il[tid] = 1.0 / exp(h[1 + tid]);
+  }
+  for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
+  const double cst = exp(h[0]);
+  const double kdiag = ((FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0) + exp(h[d + 1]);
+  double *kb, *gb;
+  pg_rows(pg_dyn, scratch, n, npad, s, kb, gb);
+  pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W);
+  double f = pg_objective(W, y_mean, y_std, kappa);
+  if (tid < d) g[tid] = pg_gradient(W, tid, y_std, kappa);
+  __syncthreads();
+  // (every thread follows the same control flow: all decisions are taken on values read from LDS)
+  int st = 1, it = 0, nev = 1;
+  bool fresh = true;  // Hm is the identity
+  for (; it < max_iter; it++) {
+    if (tid < d) act[tid] = (x[tid] <= lo[tid] && g[tid] > 0.0) || (x[tid] >= hi[tid] && g[tid] < 0.0);
+    __syncthreads();
+    double pgn = 0.0;
+    for (int t = 0; t < d; t++)
+      if (!act[t]) pgn = fmax(pgn, fabs(g[t]));
+    if (pgn <= gtol) {
+      st = 0;
+      break;
+    }
+    if (tid < d) {
+      double pt = 0.0;
+      if (!act[tid])
+        for (int u = 0; u < d; u++)
+          if (!act[u]) pt = fma(-Hm[tid * PG_HS + u], g[u], pt);
+      p[tid] = pt;
+    }
+    __syncthreads();
+    double gp = 0.0, pn = 0.0;
+    for (int t = 0; t < d; t++) gp = fma(g[t], p[t], gp), pn = fma(p[t], p[t], pn);
+    if (!(gp < 0.0)) {  // not a descent direction: forget the curvature, steepest descent on the free variables
+      __syncthreads();
+      for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
+      if (tid < d) p[tid] = act[tid] ? 0.0 : -g[tid];
+      fresh = true;
+      __syncthreads();
+      gp = 0.0, pn = 0.0;
+      for (int t = 0; t < d; t++) gp = fma(g[t], p[t], gp), pn = fma(p[t], p[t], pn);
+    }
+    double a = 1.0;
+    if (fresh) {
+      const double r = 1.0 / sqrt(pn);
+      a = r < 1.0 ? r : 1.0;
+    }
+    bool accepted = false;
+    double fn = f;
+    for (int ls = 0; ls < PG_LS_MAX; ls++) {
+      if (tid < d) {
+        double v = fma(a, p[tid], x[tid]);
+        v = v < lo[tid] ? lo[tid] : (v > hi[tid] ? hi[tid] : v);
+        W.x[tid] = v;
+      }
+      pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W);
+      nev++;
+      fn = pg_objective(W, y_mean, y_std, kappa);
+      double dd = 0.0;  // the decrease the gradient predicts along the projected step
+      for (int t = 0; t < d; t++) dd = fma(g[t], W.x[t] - x[t], dd);
+      if (dd < 0.0 && fn <= f + 1e-4 * dd) {
+        accepted = true;
+        break;
+      }
+      a *= 0.5;
+      __syncthreads();  // (W.x is rewritten next)
+    }
+    if (!accepted) {
+      if (!fresh) {  // once more from this iterate along the steepest descent (counts as an iteration)
+        __syncthreads();
+        for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
+        fresh = true;
+        __syncthreads();
+        continue;
+      }
+      st = 2;
+      break;
+    }
+    __syncthreads();
+    if (tid < d) {
+      const double gn = pg_gradient(W, tid, y_std, kappa);
+      sv[tid] = W.x[tid] - x[tid];
+      yv[tid] = gn - g[tid];
+      x[tid] = W.x[tid];
+      g[tid] = gn;
+    }
+    f = fn;
+    __syncthreads();
+    double sy = 0.0, yy = 0.0, ss = 0.0;
+    for (int t = 0; t < d; t++) sy = fma(sv[t], yv[t], sy), yy = fma(yv[t], yv[t], yy), ss = fma(sv[t], sv[t], ss);
+    if (sy > 1e-10 * sqrt(ss * yy)) {
+      if (fresh) {  // the first pair scales the identity
+        const double sc = sy / yy;
+        for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? sc : 0.0;
+        __syncthreads();
+      }
+      if (tid < d) {
+        double v = 0.0;
+        for (int u = 0; u < d; u++) v = fma(Hm[tid * PG_HS + u], yv[u], v);
+        Hy[tid] = v;
+      }
+      __syncthreads();
+      double yHy = 0.0;
+      for (int t = 0; t < d; t++) yHy = fma(yv[t], Hy[t], yHy);
+      const double rho = 1.0 / sy, c2 = (sy + yHy) * rho * rho;
+      for (int idx = tid; idx < d * d; idx += PG_NT) {
+        const int t = idx / d, u = idx - t * d;
+        Hm[t * PG_HS + u] = Hm[t * PG_HS + u] + (c2 * (sv[t] * sv[u]) - rho * (Hy[t] * sv[u] + sv[t] * Hy[u]));
+      }
+      fresh = false;
+      __syncthreads();
+    }
+  }
+  // the moments at the end point, variance included: the bits bgp_predict_grad_batch returns there
+  __syncthreads();
+  if (tid < d) W.x[tid] = x[tid];
+  pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, true, kb, gb, W);
+  nev++;
+  if (tid < d) X_out[(size_t)s * d + tid] = x[tid];
+  if (tid == 0) {
+    mean_out[s] = W.mean;
+    var_out[s] = W.var;
+    iters[s] = it;
+    evals[s] = nev;
+    status[s] = st;
+  }
+}
+
+struct PgScratch {
+  double* base;
+  size_t used;
+  double* take(size_t k) {
+    double* q = base + used;
+    used += (k + 1) & ~(size_t)1;
+    return q;
+  }
+};
+
+static int pg_check(bgp_ctx* c, const char* who) {
+  if (c->d > PG_DMAX || c->has_warp) {
+    bgp_set_error("%s: %s", who, c->has_warp ? "warped inputs are not supported" : "d > 32 is not supported");
+    return BGP_ERR_INVALID;
+  }
+  return BGP_OK;
+}
+
+extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
+                                      double* var, double* dmean, double* dvar) {
+  BGP_REQUIRE_IDLE(c, "bgp_predict_grad_batch");
+  if (!c || !h_kernel || !Xq || !mean || !var || !dmean || m <= 0 || B <= 0) {
+    bgp_set_error("bgp_predict_grad_batch: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  int rc = pg_check(c, "bgp_predict_grad_batch");
+  if (rc) return rc;
+  if (B > c->post_B) {
+    bgp_set_error("bgp_predict_grad_batch: %d posteriors requested but %d resident (call bgp_posterior_batch first)", B,
+                  c->post_B);
+    return BGP_ERR_STATE;
+  }
+  BGP_HIP(hipSetDevice(c->device));
+  const int n = c->n, d = c->d, npad = c->npad;
+  const size_t p = d + 2;
+  const bool lds = n <= PG_NLDS;
+  // chunks of query rows: outputs of B mc (2 + 2 d) doubles, and B mc scratch rows of 2 npad doubles beyond PG_NLDS points
+  size_t mc = std::min<size_t>((size_t)m, 65535);
+  mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)B * (2 + 2 * (size_t)d))));
+  if (!lds) mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 26) / ((size_t)B * 2 * npad)));
+  const size_t Bm = (size_t)B * mc;
+  rc = bgp_ensure_scratch(c, mc * d + B * p + 2 * Bm + 2 * Bm * d + (lds ? 0 : Bm * 2 * npad) + 64);
+  if (rc) return rc;
+  PgScratch s{c->dscratch, 0};
+  double* dXq = s.take(mc * d);
+  double* dH = s.take(B * p);
+  double* dm = s.take(Bm);
+  double* dv = s.take(Bm);
+  double* ddm = s.take(Bm * d);
+  double* ddv = s.take(Bm * d);
+  double* rows = lds ? nullptr : s.take(Bm * 2 * npad);
+  const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
+  BGP_HIP(bgp_memcpy_async(dH, h_kernel, B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
+    const int mm = (int)std::min(mc, (size_t)m - m0);
+    BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((pg_rows_kernel<S, F>), dim3(mm, B), dim3(PG_NT), shmem, c->stream, c->dXeff, n, d, npad,
+                                   c->dalpha_sol, c->dKinv, dH, dXq, mm, rows, dm, dv, ddm, dvar ? ddv : nullptr));
+    BGP_HIP(hipGetLastError());
+    const size_t w1 = (size_t)mm * sizeof(double), wd = (size_t)mm * d * sizeof(double);
+    BGP_HIP(bgp_memcpy2d_async(mean + m0, (size_t)m * sizeof(double), dm, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_memcpy2d_async(var + m0, (size_t)m * sizeof(double), dv, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_memcpy2d_async(dmean + m0 * d, (size_t)m * d * sizeof(double), ddm, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
+    if (dvar)
+      BGP_HIP(bgp_memcpy2d_async(dvar + m0 * d, (size_t)m * d * sizeof(double), ddv, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the buffers)
+  }
+  return BGP_OK;
+}
+
+extern "C" int bgp_minimize_starts(bgp_ctx* c, int b, const double* h_kernel, double y_mean, double y_std, double kappa, int S_,
+                                   const double* X0, const double* lo, const double* hi, double gtol, int max_iter, double* X_out,
+                                   double* mean_out, double* var_out, int* iters, int* evals, int* status) {
+  BGP_REQUIRE_IDLE(c, "bgp_minimize_starts");
+  if (!c || !h_kernel || !X0 || !lo || !hi || !X_out || !mean_out || !var_out || !iters || !evals || !status || S_ <= 0 ||
+      S_ > 65535 || b < 0 || max_iter < 0 || !(gtol >= 0.0)) {
+    bgp_set_error("bgp_minimize_starts: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  int rc = pg_check(c, "bgp_minimize_starts");
+  if (rc) return rc;
+  for (int t = 0; t < c->d; t++)
+    if (!(lo[t] <= hi[t])) {
+      bgp_set_error("bgp_minimize_starts: empty box in dimension %d", t);
+      return BGP_ERR_INVALID;
+    }
+  if (b >= c->post_B) {
+    bgp_set_error("bgp_minimize_starts: posterior %d not resident (%d resident)", b, c->post_B);
+    return BGP_ERR_STATE;
+  }
+  BGP_HIP(hipSetDevice(c->device));
+  const int n = c->n, d = c->d, npad = c->npad;
+  const size_t p = d + 2, Sd = (size_t)S_ * d;
+  const bool lds = n <= PG_NLDS;
+  rc = bgp_ensure_scratch(c, p + 2 * Sd + 2 * (size_t)d + 2 * (size_t)S_ + 3 * ((size_t)S_ / 2 + 1) +
+                                 (lds ? 0 : (size_t)S_ * 2 * npad) + 64);
+  if (rc) return rc;
+  PgScratch s{c->dscratch, 0};
+  double* dH = s.take(p);
+  double* dX0 = s.take(Sd);
+  double* dXo = s.take(Sd);
+  double* dlo = s.take(d);
+  double* dhi = s.take(d);
+  double* dm = s.take(S_);
+  double* dv = s.take(S_);
+  int* dit = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
+  int* dev = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
+  int* dst = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
+  double* rows = lds ? nullptr : s.take((size_t)S_ * 2 * npad);
+  const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
+  hipStream_t st = c->stream;
+  BGP_HIP(bgp_memcpy_async(dH, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, st));
+  BGP_HIP(bgp_memcpy_async(dX0, X0, Sd * sizeof(double), hipMemcpyHostToDevice, st));
+  BGP_HIP(bgp_memcpy_async(dlo, lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  BGP_HIP(bgp_memcpy_async(dhi, hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  KB_DISPATCH(c->ks.stationary, c->ks.form,
+              hipLaunchKernelGGL((pg_min_kernel<S, F>), dim3(S_), dim3(PG_NT), shmem, st, c->dXeff, n, d, npad,
+                                 c->dalpha_sol + (size_t)b * npad, c->dKinv + (size_t)b * npad * npad, dH, y_mean, y_std, kappa, dX0,
+                                 dlo, dhi, gtol, max_iter, rows, dXo, dm, dv, dit, dev, dst));
+  BGP_HIP(hipGetLastError());
+  BGP_HIP(bgp_memcpy_async(X_out, dXo, Sd * sizeof(double), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_memcpy_async(mean_out, dm, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_memcpy_async(var_out, dv, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_memcpy_async(iters, dit, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_memcpy_async(evals, dev, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_memcpy_async(status, dst, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+  BGP_HIP(bgp_stream_sync(st));
+  return BGP_OK;
+}

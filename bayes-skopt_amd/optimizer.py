@@ -16,7 +16,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import construct_default_kernel, expected_minimum, hdi
+from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi
 
 __all__ = ["Optimizer"]
 
@@ -239,24 +239,37 @@ class Optimizer:
                       gp_samples=gp_samples, gp_burnin=gp_burnin)
         return self._result()
 
-    def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed):
+    def expected_optimum(self, kappa=0.0, n_random_starts=100, random_state=None):
+        """Where the optimum is right now: the minimiser of the surrogate mean (``kappa = 0``) or of the upper confidence bound
+        ``mean + kappa std``, found on the device from the best observed point and ``n_random_starts`` random points
+        (``utils.expected_optimum``).  Returns (x, value, info)."""
+        return expected_optimum(self._result(), kappa=kappa, n_random_starts=n_random_starts, random_state=random_state)
+
+    def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed, minimizer="scipy"):
         """Function draws (device ``sample_y``) at [expected optimum, n_space_samples random points]:
         (1 + n_space_samples, n_gp_samples); row 0 belongs to the minimiser of the surrogate mean found by
         ``utils.expected_minimum`` (``bask/optimizer.py:493-512``).  ``seed`` is handed unchanged to each of the
-        three consumers, as the reference does."""
+        three consumers, as the reference does.  ``minimizer="device"``: the minimiser comes from ``utils.expected_optimum``."""
+        if minimizer not in ("scipy", "device"):
+            raise ValueError(f"minimizer must be 'scipy' or 'device', got {minimizer!r}")
         res = self._result()
-        x_opt, _ = expected_minimum(res, n_random_starts=n_random_starts, random_state=seed)
+        if minimizer == "device":
+            x_opt = expected_optimum(res, n_random_starts=n_random_starts, random_state=seed)[0]
+        else:
+            x_opt, _ = expected_minimum(res, n_random_starts=n_random_starts, random_state=seed)
         points = [x_opt] + self.space.rvs(n_samples=n_space_samples, random_state=seed)
         return self.gp.sample_y(self.space.transform(points), sample_mean=use_mean_gp, n_samples=n_gp_samples,
                                 random_state=seed)
 
     def probability_of_optimality(self, threshold, n_space_samples=500, n_gp_samples=200, n_random_starts=100,
-                                  use_mean_gp=True, normalized_scores=True, random_state=None):
+                                  use_mean_gp=True, normalized_scores=True, random_state=None, minimizer="scipy"):
         """Probability that no point of the space beats the current expected optimum by more than
         ``threshold`` (a float, or a list giving a list of probabilities) -- ``bask/optimizer.py:447-525``,
         same arguments.  With ``normalized_scores`` the gaps are measured in units of each draw's standard
-        deviation over the points."""
-        draws = self._optimum_vs_space_draws(n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, random_state)
+        deviation over the points.  ``minimizer``: "scipy" (``utils.expected_minimum``) or "device" (``utils.expected_optimum``)
+        finds the expected optimum."""
+        draws = self._optimum_vs_space_draws(n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, random_state,
+                                             minimizer=minimizer)
         gap = draws[0][None, :] - draws          # how much better every point is than the optimum, per draw
         if normalized_scores:
             gap = gap / np.std(draws, axis=0)
@@ -266,7 +279,7 @@ class Optimizer:
 
     def expected_optimality_gap(self, max_tries=3, n_probabilities=50, n_space_samples=500, n_gp_samples=200,
                                 n_random_starts=100, tol=0.01, use_mean_gp=True, normalized_scores=True,
-                                random_state=None):
+                                random_state=None, minimizer="scipy"):
         """Expected optimality gap of the current global optimum (``bask/optimizer.py:527-620``): the
         distribution function of the gap is sampled with ``probability_of_optimality`` on ``n_probabilities``
         thresholds between 0 and the smallest threshold at which the probability reaches 1 (found by a
@@ -275,7 +288,7 @@ class Optimizer:
 
         seed = check_random_state(random_state).randint(0, 2**32 - 1, dtype=np.int64)
         kw = dict(n_space_samples=n_space_samples, n_gp_samples=n_gp_samples, n_random_starts=n_random_starts,
-                  use_mean_gp=use_mean_gp, normalized_scores=normalized_scores, random_state=seed)
+                  use_mean_gp=use_mean_gp, normalized_scores=normalized_scores, random_state=seed, minimizer=minimizer)
         span = float(np.max(self.yi) - np.min(self.yi))
         upper = None
         for _ in range(max_tries):

@@ -2,6 +2,7 @@
 default kernel, input validation."""
 import collections.abc
 import math
+import sys
 
 import numpy as np
 
@@ -9,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -145,6 +146,92 @@ def expected_minimum(res, n_random_starts=20, random_state=None):
         if r.fun < best_fun:
             best_x, best_fun = r.x, r.fun
     return [float(v) for v in best_x], float(best_fun)
+
+
+_told = set()
+
+
+def _tell_once(reason):
+    """One line on stderr, once per process and reason: a search that could have stayed on the device is driven from the host."""
+    if reason not in _told:
+        _told.add(reason)
+        print("[bayes_skopt_amd] expected_optimum: this search is driven from the host, one device predict per iterate (%s)" % reason,
+              file=sys.stderr, flush=True)
+
+
+def _host_optimum(res, kappa, n_random_starts, random_state):
+    """The scipy loop of ``expected_minimum`` on ``mean + kappa std`` (``predict(return_std=True)``), same starts."""
+    from scipy.optimize import minimize
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    reg = res.models[-1]
+    bounds = np.asarray(space.bounds, dtype=np.float64)
+    d = len(bounds)
+    eps = np.sqrt(np.finfo(np.float64).eps)
+
+    def fun_and_grad(x):
+        h = eps * np.maximum(1.0, np.abs(x))
+        sign = np.where(x + h > bounds[:, 1], -1.0, 1.0)
+        pts = np.tile(x, (d + 1, 1))
+        pts[1:, :][np.arange(d), np.arange(d)] += sign * h
+        mu, sd = reg.predict(space.transform(pts.tolist()), return_std=True)
+        vals = np.asarray(mu, dtype=np.float64) + kappa * np.asarray(sd, dtype=np.float64)
+        return float(vals[0]), (vals[1:] - vals[0]) / (sign * h)
+
+    rng = check_random_state(random_state)
+    xs = [res.x]
+    if n_random_starts > 0:
+        xs.extend(space.rvs(n_random_starts, random_state=rng))
+    best_x, best_fun = None, np.inf
+    for x0 in xs:
+        r = minimize(fun_and_grad, x0=np.asarray(x0, dtype=np.float64), jac=True, bounds=space.bounds, method="L-BFGS-B")
+        if r.fun < best_fun:
+            best_x, best_fun = r.x, r.fun
+    return [float(v) for v in best_x], float(best_fun)
+
+
+def expected_optimum(res, kappa=0.0, n_random_starts=20, random_state=None, gtol=1e-5, max_iter=200):
+    """Minimum of ``mean + kappa std`` of the surrogate (``kappa = 0``: the predictive mean, as ``expected_minimum``; ``kappa``
+    > 0: an upper confidence bound of the optimum), searched on the device: every start -- ``[res.x] + space.rvs(n_random_starts,
+    random_state)``, the starts of ``expected_minimum`` -- is one workgroup of ONE launch that runs a bounded quasi-Newton iteration
+    with analytic gradients in the transformed unit box (``bgp_minimize_starts``) until the projected gradient
+    is below ``gtol`` (y units) or ``max_iter`` iterations.  Returns ``(x, value, info)``: ``x`` in the original space, un-rounded
+    (integer dimensions by their affine map: ``expected_minimum`` returns un-rounded values too), ``info`` with per-start
+    ``status`` (0 converged, 1 ``max_iter``, 2 no decrease), ``iters``, ``evals``, ``fun``, the transformed end points
+    ``x_transformed`` with their normalised ``mean`` / ``var``, ``best`` and ``path``.  Warped inputs, generic kernel trees and more than 32 dimensions take the host
+    loop (``expected_minimum``, or the same loop over ``predict(return_std=True)``), ``path == "host"``, and say so once."""
+    from sklearn.utils import check_random_state
+
+    from .space import Integer
+
+    space = res.space
+    if space.is_partly_categorical:
+        raise ValueError("expected_minimum does not support any categorical values")
+    reg = res.models[-1]
+    post = getattr(reg, "_post", None)
+    if post is None or not post.canonical or not post.device_gradients(reg):
+        _tell_once("input warping" if getattr(reg, "warp_inputs", False) else
+                   "more than 32 dimensions" if getattr(post, "canonical", False) else "generic kernel tree")
+        if kappa == 0.0:
+            x, fun = expected_minimum(res, n_random_starts=n_random_starts, random_state=random_state)
+        else:
+            x, fun = _host_optimum(res, kappa, n_random_starts, random_state)
+        return x, fun, {"path": "host"}
+    rng = check_random_state(random_state)
+    xs = [res.x]
+    if n_random_starts > 0:
+        xs.extend(space.rvs(n_random_starts, random_state=rng))
+    out = post.minimize(reg, float(kappa), space.transform(xs), 0.0, 1.0, gtol=gtol, max_iter=max_iter)
+    y_mean, y_std = float(np.ravel(reg.y_train_mean_)[0]), float(np.ravel(reg.y_train_std_)[0])
+    fun = y_mean + y_std * out["mean"] + kappa * (y_std * np.sqrt(out["var"]))
+    best = int(np.argmin(fun))
+    xt = out["x"][best]
+    x = [float(xt[j] * (dim.high - dim.low) + dim.low) if isinstance(dim, Integer) else float(dim.inverse_transform(xt[j]))
+         for j, dim in enumerate(space.dimensions)]
+    info = {"path": "device", "status": out["status"], "iters": out["iters"], "evals": out["evals"], "fun": fun,
+            "x_transformed": out["x"], "mean": out["mean"], "var": out["var"], "best": best}
+    return x, float(fun[best]), info
 
 
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):

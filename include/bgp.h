@@ -225,6 +225,31 @@ int bgp_fantasy_end(bgp_ctx* ctx);
 int bgp_fantasy_stats(bgp_ctx* ctx, long long* out);
 
 /*
+ * Prediction gradients for any number of query rows, and the optimum search that stays on the device.
+ * With G_i = d k(x, X_i) / dx (closed forms of kernel_.gradient_x for the four stationary families and both forms; the constant and
+ * white terms contribute zeros; Matern 1/2: zero at r = 0):
+ *   dmean = sum_i alpha_i G_i ;  dvar = -2 sum_i v_i G_i ,  v = K^-1 k(X, x)
+ * bgp_predict_grad_batch: the B resident posteriors at m query rows; h_kernel as in bgp_predict_batch (white level -inf:
+ *   noise_set_to_zero).  Outputs in normalised-y units: mean B*m, var B*m (clipped at 0), dmean B*m*d, dvar B*m*d (may be NULL).
+ *   Replaces: skopt's GaussianProcessRegressor.predict(return_mean_grad, return_std_grad) for ONE point, reached from
+ *   bask/bayesgpr.py:633; the reference raises for more than one row.
+ * bgp_minimize_starts: minimise f(x) = y_mean + y_std mean(x) + kappa y_std sqrt(var(x)) over the box [lo, hi] (d doubles each) from
+ *   the S starts X0 (S*d) with resident posterior b (h_kernel: its d + 2 kernel parameters); kappa = 0: the surrogate mean.  ONE
+ *   launch, one workgroup per start running a projected BFGS iteration with Armijo backtracking (at most max_iter iterations of at
+ *   most 30 trial points); where y_std sqrt(var) <= 1e-8 the std term contributes no gradient.  Per start: X_out (inside the box
+ *   exactly), mean_out / var_out (normalised units: the bits bgp_predict_grad_batch returns at X_out), iters, evals (evaluations of f,
+ *   the closing one at X_out included) and status -- 0: the inf-norm of the projected gradient of f (y units) is <= gtol, 1: max_iter
+ *   reached, 2: the line search found no decrease.  A start's result does not depend on the other starts.
+ *   Replaces: the scipy L-BFGS-B loop of skopt.utils.expected_minimum (bask/optimizer.py:497-503).
+ * Both need d <= 32 and no context-level warp (BGP_ERR_INVALID otherwise), and resident posteriors (BGP_ERR_STATE).
+ */
+int bgp_predict_grad_batch(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
+                           double* dmean, double* dvar);
+int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_mean, double y_std, double kappa, int S,
+                        const double* X0, const double* lo, const double* hi, double gtol, int max_iter, double* X_out,
+                        double* mean_out, double* var_out, int* iters, int* evals, int* status);
+
+/*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
  * the host (z: n_draws*m), via a Cholesky factor of cov (+jitter) instead of numpy's SVD.
  * Replaces: sklearn sample_y (sklearn/_gpr.py:522-526) reached from BayesGPR.sample_y
