@@ -176,68 +176,29 @@ extern "C" int bgp_device_pci_bus_id(int device, char* buf, int len) {
   return BGP_OK;
 }
 
-static void free_dev(void* p) {
-  if (p) (void)hipFree(p);
-}
-
 static int alloc_data(bgp_ctx* c, int n) {
-  // training-set buffers sized for npad rows; grow-only
+  // training-set buffers sized for npad rows; grow-only, and TOGETHER: their common row capacity is dy's.  The warped copies go with
+  // them (dXw1 is sized by that capacity: bgp_ctx_set_warp; the per-walker buffers are re-created on demand)
   const size_t npad = (size_t)((n + BGP_NB - 1) / BGP_NB) * BGP_NB;
-  if (npad > c->cap_n) {
-    free_dev(c->dX);
-    free_dev(c->dy);
-    free_dev(c->dalpha);
-    free_dev(c->dXw1);
-    free_dev(c->dXwB);
-    c->dX = c->dy = c->dalpha = c->dXw1 = c->dXwB = nullptr;
-    c->cap_xwb = 0;
-    BGP_HIP(hipMalloc(&c->dX, npad * c->d * sizeof(double)));
-    BGP_HIP(hipMalloc(&c->dy, npad * sizeof(double)));
-    BGP_HIP(hipMalloc(&c->dalpha, npad * sizeof(double)));
-    c->cap_n = npad;
+  if (npad > c->dy.cap) {
+    for (BgpDev<double>* b : {&c->dX, &c->dy, &c->dalpha, &c->dXw1, &c->dXwB}) b->release();
+    int rc = c->dX.ensure(npad * c->d);
+    if (!rc) rc = c->dalpha.ensure(npad);
+    if (!rc) rc = c->dy.ensure(npad);  // (last: its capacity stands for all three)
+    return rc;
   }
   return BGP_OK;
 }
 
 static int alloc_work(bgp_ctx* c) {
   const size_t npad = c->npad, nblk = c->nblk, mb = c->max_batch;
-  const size_t need_mat = mb * npad * npad;
-  const size_t need_w = mb * nblk * 128 * 128;
-  const size_t need_yw = mb * 2 * npad;  // augmented right-hand sides are 2 npad long
-  if (need_mat > c->cap_mat) {
-    free_dev(c->dK);
-    c->dK = nullptr;
-    c->cap_mat = 0;
-    BGP_HIP(hipMalloc(&c->dK, need_mat * sizeof(double)));
-    c->cap_mat = need_mat;
-  }
-  if (need_w > c->cap_w) {
-    free_dev(c->dW);
-    c->dW = nullptr;
-    c->cap_w = 0;
-    BGP_HIP(hipMalloc(&c->dW, need_w * sizeof(double)));
-    c->cap_w = need_w;
-  }
-  if (need_yw > c->cap_yw) {
-    free_dev(c->dyw);
-    c->dyw = nullptr;
-    c->cap_yw = 0;
-    BGP_HIP(hipMalloc(&c->dyw, need_yw * sizeof(double)));
-    c->cap_yw = need_yw;
-  }
-  return BGP_OK;
+  int rc = c->dK.ensure(mb * npad * npad);
+  if (!rc) rc = c->dW.ensure(mb * nblk * 128 * 128);
+  if (!rc) rc = c->dyw.ensure(mb * 2 * npad);  // augmented right-hand sides are 2 npad long
+  return rc;
 }
 
-int bgp_grow_workspace(bgp_ctx* c, size_t doubles) {
-  if (doubles > c->cap_mat) {
-    free_dev(c->dK);
-    c->dK = nullptr;
-    c->cap_mat = 0;
-    BGP_HIP(hipMalloc(&c->dK, doubles * sizeof(double)));
-    c->cap_mat = doubles;
-  }
-  return BGP_OK;
-}
+int bgp_grow_workspace(bgp_ctx* c, size_t doubles) { return c->dK.ensure(doubles); }
 
 static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, const double* alpha_diag) {
   if (n <= 0 || !X || !y || !alpha_diag) {
@@ -261,13 +222,8 @@ static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, cons
   // Staged through the context's own pinned buffer: copies from pageable memory (numpy arrays, fresh vectors) were
   // measured at 10-20 ms per tell on MI355X for these 80 KB (the runtime locks / unlocks the pages around each copy).
   const size_t nx = (size_t)n * c->d, np_ = c->npad, need = nx + 2 * np_;
-  if (need > c->cap_stage) {
-    if (c->hstage) (void)hipHostFree(c->hstage);
-    c->hstage = nullptr;
-    c->cap_stage = 0;
-    BGP_HIP(hipHostMalloc((void**)&c->hstage, (need + need / 4) * sizeof(double), hipHostMallocDefault));
-    c->cap_stage = need + need / 4;
-  }
+  rc = c->hstage.ensure(need, need + need / 4);
+  if (rc) return rc;
   double *hx = c->hstage, *hy = hx + nx, *ha = hy + np_;
   memcpy(hx, X, nx * sizeof(double));
   memset(hy, 0, 2 * np_ * sizeof(double));
@@ -373,18 +329,11 @@ extern "C" int bgp_ctx_create(int device, int n, int d, const double* X, const d
     }
   }
   const size_t mb = max_batch;
-  int rc = BGP_OK;
-  do {
-    if (hipMalloc(&c->dacc, mb * 4 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->dh, mb * (d + 2) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->dlml, mb * sizeof(double)) != hipSuccess ||
-        hipMalloc(&c->dstatus, mb * sizeof(int)) != hipSuccess) {
-      bgp_set_error("hipMalloc of per-batch buffers failed");
-      rc = BGP_ERR_HIP;
-      break;
-    }
-    rc = upload_data(c, n, X, y, alpha_diag);
-  } while (0);
+  int rc = c->dacc.ensure(mb * 4);
+  if (!rc) rc = c->dh.ensure(mb * (d + 2));
+  if (!rc) rc = c->dlml.ensure(mb);
+  if (!rc) rc = c->dstatus.ensure(mb);
+  if (!rc) rc = upload_data(c, n, X, y, alpha_diag);
   if (rc) {
     bgp_ctx_destroy(c);
     return rc;
@@ -410,33 +359,6 @@ extern "C" void bgp_ctx_destroy(bgp_ctx* c) {
   bgp_mcmc_abandon(c);  // (a sampler run left open: its work is drained, its block freed)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   bgp_free_child(c);
-  free_dev(c->dX);
-  free_dev(c->dy);
-  free_dev(c->dalpha);
-  free_dev(c->dK);
-  free_dev(c->dW);
-  free_dev(c->dyw);
-  free_dev(c->dacc);
-  free_dev(c->dh);
-  free_dev(c->dlml);
-  free_dev(c->dstatus);
-  free_dev(c->dalpha_sol);
-  free_dev(c->dKinv);
-  free_dev(c->dXw1);
-  free_dev(c->dXwB);
-  free_dev(c->dXs);
-  free_dev(c->dwarp);
-  free_dev(c->dwarpB);
-  free_dev(c->dscratch);
-  free_dev(c->drowpart);
-  if (c->hstage) (void)hipHostFree(c->hstage);
-  if (c->hlml) (void)hipHostFree(c->hlml);
-  if (c->hstatus) (void)hipHostFree(c->hstatus);
-  if (c->hh) (void)hipHostFree(c->hh);
-  if (c->hwarp) (void)hipHostFree(c->hwarp);
-  free_dev(c->ps_flags);
-  free_dev(c->ps_trace);
-  if (c->ps_herr) (void)hipHostFree(c->ps_herr);
   for (int g = 0; g < BGP_MAX_STREAMS; g++) {
     if (c->gstream[g]) {
       (void)hipStreamSynchronize(c->gstream[g]);
@@ -450,24 +372,13 @@ extern "C" void bgp_ctx_destroy(bgp_ctx* c) {
     bgp_xfer_forget(c->stream);  // (synchronised above: nothing of this context is in flight into the arena any more)
     (void)hipStreamDestroy(c->stream);
   }
-  delete c;
+  delete c;  // (frees every buffer the context owns)
   bool last;
   {
     std::lock_guard<std::mutex> lock(g_xfer_mutex);
     last = --g_live_contexts == 0;
   }
   if (last) xfer_free_all();
-}
-
-int bgp_ensure_scratch(bgp_ctx* c, size_t doubles) {
-  if (doubles > c->cap_scratch) {
-    free_dev(c->dscratch);
-    c->dscratch = nullptr;
-    c->cap_scratch = 0;
-    BGP_HIP(hipMalloc(&c->dscratch, doubles * sizeof(double)));
-    c->cap_scratch = doubles;
-  }
-  return BGP_OK;
 }
 
 // Factorise one chunk (<= max_batch) of hyper-parameter vectors already validated by the caller.
@@ -629,16 +540,8 @@ int bgp_lml_enqueue_dev(bgp_ctx* c, int nb, int warped) {
 
 // per-walker warped inputs (max_batch x n x d) and warp parameters (max_batch x 2 d) of a warped LML batch
 int bgp_ensure_warp_buffers(bgp_ctx* c) {
-  const size_t need = (size_t)c->max_batch * c->n * c->d;
-  if (need > c->cap_xwb) {
-    free_dev(c->dXwB);
-    c->dXwB = nullptr;
-    c->cap_xwb = 0;
-    BGP_HIP(hipMalloc(&c->dXwB, need * sizeof(double)));
-    c->cap_xwb = need;
-  }
-  if (!c->dwarpB) BGP_HIP(hipMalloc(&c->dwarpB, (size_t)c->max_batch * 2 * c->d * sizeof(double)));
-  return BGP_OK;
+  const int rc = c->dXwB.ensure((size_t)c->max_batch * c->n * c->d);
+  return rc ? rc : c->dwarpB.ensure((size_t)c->max_batch * 2 * c->d);
 }
 
 static int lml_batch_run(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status,
@@ -740,20 +643,11 @@ static int lml_submit_impl(bgp_ctx* c, int B, const double* h, const double* war
     return BGP_ERR_INVALID;
   }
   BGP_HIP(hipSetDevice(c->device));
-  if ((size_t)B > c->cap_pinned) {
-    if (c->hlml) (void)hipHostFree(c->hlml);
-    if (c->hstatus) (void)hipHostFree(c->hstatus);
-    if (c->hh) (void)hipHostFree(c->hh);
-    c->hlml = nullptr;
-    c->hstatus = nullptr;
-    c->hh = nullptr;
-    c->cap_pinned = 0;
-    BGP_HIP(hipHostMalloc(&c->hlml, (size_t)c->max_batch * sizeof(double)));
-    BGP_HIP(hipHostMalloc(&c->hstatus, (size_t)c->max_batch * sizeof(int)));
-    BGP_HIP(hipHostMalloc(&c->hh, (size_t)c->max_batch * (c->d + 2) * sizeof(double)));
-    c->cap_pinned = c->max_batch;
-  }
-  if (warp && !c->hwarp) BGP_HIP(hipHostMalloc(&c->hwarp, (size_t)c->max_batch * 2 * c->d * sizeof(double)));
+  int rca = c->hlml.ensure(c->max_batch);
+  if (!rca) rca = c->hstatus.ensure(c->max_batch);
+  if (!rca) rca = c->hh.ensure((size_t)c->max_batch * (c->d + 2));
+  if (!rca && warp) rca = c->hwarp.ensure((size_t)c->max_batch * 2 * c->d);
+  if (rca) return rca;
   // the proposals go up from pinned memory too: an asynchronous copy out of a pageable numpy array costs the runtime
   // a page lock / unlock per call (tens of microseconds in front of every half-step)
   memcpy(c->hh, h, (size_t)B * (c->d + 2) * sizeof(double));

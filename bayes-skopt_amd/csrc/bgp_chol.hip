@@ -240,14 +240,7 @@ int bgp_persist_fits(bgp_ctx* c, int B) {
 // the flag block of a launch-free call with B matrices exists (grown with 50 % head room; contents undefined)
 int bgp_ps_ensure_flags(bgp_ctx* c, int B) {
   const size_t words = ps_flag_words(B, c->nblk);
-  if (words > c->cap_psflags) {
-    if (c->ps_flags) (void)hipFree(c->ps_flags);
-    c->ps_flags = nullptr;
-    c->cap_psflags = 0;
-    BGP_HIP(hipMalloc(&c->ps_flags, (words + words / 2) * sizeof(unsigned)));
-    c->cap_psflags = words + words / 2;
-  }
-  return BGP_OK;
+  return c->ps_flags.ensure(words, words + words / 2);
 }
 
 int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
@@ -258,7 +251,8 @@ int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
   }
   const int ncu = c->ncu;
   if (!c->ps_herr) {
-    BGP_HIP(hipHostMalloc((void**)&c->ps_herr, sizeof(unsigned), hipHostMallocDefault));
+    const int rch = c->ps_herr.ensure(1);
+    if (rch) return rch;
     *c->ps_herr = 0;
   }
   const size_t words = ps_flag_words(B, nblk);
@@ -370,13 +364,8 @@ int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
     }
     if (want) {
       const size_t need = (size_t)B * nblk * 8 + (size_t)a.total * 8;
-      if (need > c->cap_pstrace) {
-        if (c->ps_trace) (void)hipFree(c->ps_trace);
-        c->ps_trace = nullptr;
-        c->cap_pstrace = 0;
-        BGP_HIP(hipMalloc(&c->ps_trace, need * sizeof(unsigned long long)));
-        c->cap_pstrace = need;
-      }
+      const int rct = c->ps_trace.ensure(need);
+      if (rct) return rct;
       BGP_HIP(hipMemsetAsync(c->ps_trace, 0, need * sizeof(unsigned long long), c->stream));
       a.trace = c->ps_trace;
       c->ps_trace_B = B;

@@ -99,11 +99,8 @@ struct bgp_comm {
   int device = 0, rank = 0, world = 1;
   ncclComm_t comm = nullptr;
   hipStream_t stream = nullptr;
-  double* dsend = nullptr;  // device-resident staging, grown on demand
-  double* drecv = nullptr;
-  size_t cap_send = 0, cap_recv = 0;
-  double* hrecv = nullptr;  // pinned landing buffer of the device-resident gathers
-  size_t cap_hrecv = 0;
+  BgpDev<double> dsend, drecv;  // device-resident staging, grown on demand (owned: freed with the communicator)
+  BgpPinned<double> hrecv;      // pinned landing buffer of the device-resident gathers
   hipEvent_t ev_ctx = nullptr;  // the communicator's stream waits for a context's stream through this event
   int aborted = 0;              // the communicator was aborted (a collective outlasted its bound / an asynchronous error)
 };
@@ -200,21 +197,8 @@ static int comm_download(bgp_comm* c, double* host, size_t count, const char* wh
   } while (0)
 
 static int comm_reserve(bgp_comm* c, size_t nsend, size_t nrecv) {
-  if (nsend > c->cap_send) {
-    if (c->dsend) (void)hipFree(c->dsend);
-    c->dsend = nullptr;
-    c->cap_send = 0;
-    BGP_HIP(hipMalloc(&c->dsend, nsend * sizeof(double)));
-    c->cap_send = nsend;
-  }
-  if (nrecv > c->cap_recv) {
-    if (c->drecv) (void)hipFree(c->drecv);
-    c->drecv = nullptr;
-    c->cap_recv = 0;
-    BGP_HIP(hipMalloc(&c->drecv, nrecv * sizeof(double)));
-    c->cap_recv = nrecv;
-  }
-  return BGP_OK;
+  const int rc = c->dsend.ensure(nsend);
+  return rc ? rc : c->drecv.ensure(nrecv);
 }
 
 extern "C" int bgp_comm_available(void) { return load_rccl() == BGP_OK ? 1 : 0; }
@@ -303,12 +287,11 @@ extern "C" int bgp_comm_init(int device, int rank, int world, const void* id128,
   // only) between a submitted batch and its collective
   if (hipEventCreateWithFlags(&c->ev_ctx, hipEventDisableTiming) != hipSuccess ||
       comm_reserve(c, 4096 + 1, (size_t)(4096 + 1) * world) != BGP_OK ||
-      hipHostMalloc((void**)&c->hrecv, (size_t)(4096 + 1) * world * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      c->hrecv.ensure((size_t)(4096 + 1) * world) != BGP_OK) {
     bgp_set_error("bgp_comm_init: allocating the exchange buffers failed");
     bgp_comm_destroy(c);
     return BGP_ERR_HIP;
   }
-  c->cap_hrecv = (size_t)(4096 + 1) * world;
   *out = c;
   return BGP_OK;
 }
@@ -345,14 +328,11 @@ extern "C" void bgp_comm_destroy(bgp_comm* c) {
   }
   if (c->ev_ctx) (void)hipEventDestroy(c->ev_ctx);
   if (c->comm) (void)g_rccl.CommDestroy(c->comm);
-  if (c->dsend) (void)hipFree(c->dsend);
-  if (c->drecv) (void)hipFree(c->drecv);
-  if (c->hrecv) (void)hipHostFree(c->hrecv);
   if (c->stream) {
     bgp_xfer_forget(c->stream);
     (void)hipStreamDestroy(c->stream);
   }
-  delete c;
+  delete c;  // (frees the exchange buffers)
 }
 
 extern "C" int bgp_comm_abort(bgp_comm* c) {
@@ -434,18 +414,10 @@ extern "C" int bgp_lml_batch_wait_allgather(bgp_ctx* ctx, bgp_comm* c, int per_r
   const size_t slot = (size_t)per_rank + 1, total = slot * c->world;
   int rc = BGP_OK;
   if (hipSetDevice(c->device) != hipSuccess) local_error = local_error ? local_error : BGP_ERR_HIP;
-  if (slot > c->cap_send || total > c->cap_recv || total > c->cap_hrecv) {
+  if (slot > c->dsend.cap || total > c->drecv.cap || total > c->hrecv.cap) {
     // larger than the buffers of bgp_comm_init (per_rank > 4096): grown here, the same on every rank
     rc = comm_reserve(c, slot, total);
-    if (!rc && total > c->cap_hrecv) {
-      if (c->hrecv) (void)hipHostFree(c->hrecv);
-      c->hrecv = nullptr;
-      c->cap_hrecv = 0;
-      if (hipHostMalloc((void**)&c->hrecv, total * sizeof(double), hipHostMallocDefault) == hipSuccess)
-        c->cap_hrecv = total;
-      else
-        rc = BGP_ERR_HIP;
-    }
+    if (!rc) rc = c->hrecv.ensure(total);
     if (rc) {  // without buffers this rank cannot take part: abort the communicator so that the peers fail too
       if (g_rccl.CommAbort && c->comm) (void)g_rccl.CommAbort(c->comm);
       c->comm = nullptr;
@@ -517,10 +489,10 @@ int bgp_comm_rank(const bgp_comm* c, int* rank, int* world) {
 
 const double* bgp_comm_recv(bgp_comm* c, size_t doubles) {
   if (!c) return nullptr;
-  if (doubles > c->cap_recv || doubles / c->world > c->cap_send) {
+  if (doubles > c->drecv.cap || doubles / c->world > c->dsend.cap) {
     if (hipSetDevice(c->device) != hipSuccess) return nullptr;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;  // (nothing of an earlier exchange reads the old buffers)
-    if (comm_reserve(c, std::max(c->cap_send, doubles / c->world), std::max(c->cap_recv, doubles)) != BGP_OK) return nullptr;
+    if (comm_reserve(c, doubles / c->world, doubles) != BGP_OK) return nullptr;
   }
   return c->drecv;
 }
@@ -551,7 +523,7 @@ static int loop_meet(LoopGroup* g, const char* what) {
 int bgp_comm_enqueue_lml_gather(bgp_comm* c, bgp_ctx* ctx, hipStream_t st, int Bp, int per, const unsigned* ps_err) {
   BGP_COMM_LIVE_OR_LOOP(c, "bgp_mcmc (sharded run)");
   const size_t slot = (size_t)per + 1;
-  if (slot > c->cap_send || slot * c->world > c->cap_recv || (c->loop && slot > LOOP_SLOT)) {
+  if (slot > c->dsend.cap || slot * c->world > c->drecv.cap || (c->loop && slot > LOOP_SLOT)) {
     bgp_set_error("bgp_mcmc (sharded run): %d rows per rank exceed the communicator's exchange buffers", per);
     return BGP_ERR_INVALID;
   }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/bgp.h"
+#include "bgp_mem.h"
 
 #define BGP_NB 128          // block size of the right-looking Cholesky == tile edge
 #define BGP_TILE_LD 129     // LDS leading dimension of a 128x128 tile (odd -> conflict-free columns)
@@ -137,61 +138,49 @@ struct bgp_ctx {
   hipStream_t gstream[BGP_MAX_STREAMS] = {nullptr};
   hipEvent_t ev_ready = nullptr;
   hipEvent_t ev_done[BGP_MAX_STREAMS] = {nullptr};
-  // resident training set
-  double* dX = nullptr;      // n*d  (original inputs)
-  double* dXeff = nullptr;   // what the kernels read: dX, or dXw1 when a context-level warp is set
-  double* dXw1 = nullptr;    // training inputs through the context-level Beta-CDF warp
-  double* dXwB = nullptr;    // per-walker warped inputs of a warped LML batch (max_batch * n * d)
-  double* dwarp = nullptr;   // context-level warp parameters (2d, log space)
-  double* dwarpB = nullptr;  // per-walker warp parameters (max_batch * 2d)
-  size_t cap_xwb = 0;
+  // resident training set (every buffer below is owned: bgp_mem.h; deleting the context frees them)
+  BgpDev<double> dX;         // n*d  (original inputs)
+  double* dXeff = nullptr;   // what the kernels read: dX, or dXw1 when a context-level warp is set (borrowed)
+  BgpDev<double> dXw1;       // training inputs through the context-level Beta-CDF warp
+  BgpDev<double> dXwB;       // per-walker warped inputs of a warped LML batch (max_batch * n * d)
+  BgpDev<double> dwarp;      // context-level warp parameters (2d, log space)
+  BgpDev<double> dwarpB;     // per-walker warp parameters (max_batch * 2d)
   int has_warp = 0;
-  double* dXs = nullptr;     // scaled inputs of the current batch, k-major: max_batch * dpad * npad (bgp_kbuild.hip)
-  size_t cap_xs = 0;
-  double* dy = nullptr;      // npad (zero padded)
-  double* dalpha = nullptr;  // npad
-  size_t cap_n = 0;          // capacity (rows) of the three buffers above
+  BgpDev<double> dXs;        // scaled inputs of the current batch, k-major: max_batch * dpad * npad (bgp_kbuild.hip)
+  BgpDev<double> dy;         // npad (zero padded); dy.cap is the row capacity of dX, dy and dalpha
+  BgpDev<double> dalpha;     // npad
   // per-batch workspace
-  double* dK = nullptr;      // max_batch * npad*npad   working matrices (become L in place)
-  double* dW = nullptr;      // max_batch * nblk * 128*128  inverses of the diagonal blocks
-  double* dyw = nullptr;     // max_batch * npad        working rhs (becomes z = L^-1 y)
-  double* dacc = nullptr;    // max_batch * 4           {logdet, z^T z, -, -}
-  double* dh = nullptr;      // max_batch * (d+2)       canonical hyper-parameters
-  double* dlml = nullptr;    // max_batch
-  int* dstatus = nullptr;    // max_batch
-  size_t cap_mat = 0;        // capacity in doubles of dK
-  size_t cap_w = 0;
-  size_t cap_yw = 0;
+  BgpDev<double> dK;         // max_batch * npad*npad   working matrices (become L in place)
+  BgpDev<double> dW;         // max_batch * nblk * 128*128  inverses of the diagonal blocks
+  BgpDev<double> dyw;        // max_batch * npad        working rhs (becomes z = L^-1 y)
+  BgpDev<double> dacc;       // max_batch * 4           {logdet, z^T z, -, -}
+  BgpDev<double> dh;         // max_batch * (d+2)       canonical hyper-parameters
+  BgpDev<double> dlml;       // max_batch
+  BgpDev<int> dstatus;       // max_batch
   // resident posteriors (K^-1 full symmetric npad x npad each, alpha = K^-1 y)
-  double* dKinv = nullptr;
-  double* dalpha_sol = nullptr;
-  size_t cap_kinv = 0;
-  size_t cap_alpha = 0;
+  BgpDev<double> dKinv;
+  BgpDev<double> dalpha_sol;
   // resident posterior state
   int post_B = 0;            // number of resident posteriors (0 = none)
   int post_gen = 0;          // bumped by every posterior build (a fantasy state checks that its posteriors are still there)
   std::vector<double> post_h;
-  // scratch for predict / pvrs (grown on demand)
-  double* dscratch = nullptr;
-  double* drowpart = nullptr;  // column-tile partials of the predictive-variance row dots
-  size_t cap_rowpart = 0;
-  size_t cap_scratch = 0;
+  // scratch for predict / pvrs (grown on demand, carved through BgpScratch below)
+  BgpDev<char> dscratch;
+  int scratch_live = 0;        // pointers carved out of dscratch are in use: a second carve would free them (BgpScratch)
+  BgpDev<double> drowpart;     // column-tile partials of the predictive-variance row dots
   // asynchronous LML batch (bgp_lml_batch_submit / _wait): pinned result buffers and the pending batch size
-  double* hstage = nullptr;  // pinned staging of the training set (bgp_ctx_update_data)
-  size_t cap_stage = 0;
-  double* hh = nullptr;      // pinned copy of the submitted hyper-parameter block
-  double* hwarp = nullptr;   // pinned copy of the submitted per-walker warp parameters (max_batch * 2d)
-  double* hlml = nullptr;
-  int* hstatus = nullptr;
-  size_t cap_pinned = 0;
+  BgpPinned<double> hstage;  // pinned staging of the training set (bgp_ctx_update_data)
+  BgpPinned<double> hh;      // pinned copy of the submitted hyper-parameter block
+  BgpPinned<double> hwarp;   // pinned copy of the submitted per-walker warp parameters (max_batch * 2d)
+  BgpPinned<double> hlml;
+  BgpPinned<int> hstatus;
   int pending_B = 0;
-  bgp_ctx* child = nullptr;  // cached workspace of bgp_sample_y (covariance Cholesky)
+  bgp_ctx* child = nullptr;  // cached workspace of bgp_sample_y (covariance Cholesky); it BORROWS this context's stream
   // launch-free factorisation of small batches (ps_kernel): flag block, pinned error word, trace buffer
   int ncu = 0;               // CUs of the device (the launch-free kernel takes one workgroup per CU)
   int persist = -1;          // env BGP_PERSIST: 0 never, 1 whenever possible, -1 (unset) automatic by batch size
-  unsigned* ps_flags = nullptr;
-  size_t cap_psflags = 0;
-  unsigned* ps_herr = nullptr;  // pinned: error word of the last persistent call
+  BgpDev<unsigned> ps_flags;
+  BgpPinned<unsigned> ps_herr;  // pinned: error word of the last persistent call
   int ps_inflight = 0;          // a persistent call is on the stream (its error word is checked behind the sync)
   int ps_disabled = 0;          // a persistent call timed out: multi-launch path (see bgp_ps_note_timeout)
   int ps_cooldown = 0;          // eligible calls left on the multi-launch path before the launch-free one is tried again
@@ -204,8 +193,7 @@ struct bgp_ctx {
   struct bgp_mcmc_state* mcmc = nullptr;  // an open device-resident sampler run (bgp_mcmc_begin .. bgp_mcmc_end; bgp_mcmc.hip)
   int ps_forbid = 0;            // the device-resident sampler redoes a run after a time-out: launches only, on every rank
   int ps_resident = 0;          // the device-resident sampler is enqueuing: no per-call copy of the error word (its kernels read it)
-  unsigned long long* ps_trace = nullptr;  // BGP_PS_TRACE=1: device buffer of in-kernel time stamps (bgp_debug_ps_trace)
-  size_t cap_pstrace = 0;
+  BgpDev<unsigned long long> ps_trace;  // BGP_PS_TRACE=1: device buffer of in-kernel time stamps (bgp_debug_ps_trace)
   int ps_trace_B = 0, ps_trace_nblk = 0, ps_trace_total = 0;
   // timing
   int timing = 0;
@@ -380,7 +368,28 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_persist_fits(bgp_ctx* ctx, int B);
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
-int bgp_ensure_scratch(bgp_ctx* ctx, size_t doubles);
+// The context's scratch, carved by ONE layout per call (bgp_mem.h; every region on 16 bytes).  A carve may free and re-allocate
+// dscratch, so the pointers of an earlier one would dangle: while a BgpScratch that has carved is in scope, another carve of the
+// same context is refused.  (No scratch user calls another one inside that scope today.)
+struct BgpScratch {
+  bgp_ctx* c;
+  bool mine = false;
+  explicit BgpScratch(bgp_ctx* ctx) : c(ctx) {}
+  BgpScratch(const BgpScratch&) = delete;
+  ~BgpScratch() {
+    if (mine) c->scratch_live = 0;
+  }
+  template <class Layout>
+  int carve(Layout&& layout) {
+    if (c->scratch_live) {
+      bgp_set_error("libbgp: the context's scratch is carved while an earlier carve of it is in use");
+      return BGP_ERR_STATE;
+    }
+    c->scratch_live = 1;
+    mine = true;
+    return bgp_carve(c->dscratch, 16, layout);
+  }
+};
 void bgp_free_child(bgp_ctx* ctx);
 // make the matrix workspace at least `doubles` large (and the per-item side buffers consistent)
 int bgp_grow_workspace(bgp_ctx* ctx, size_t doubles);

@@ -33,17 +33,14 @@ struct bgp_fantasy_state {
   double y_mean = 0.0, y_std = 1.0;
   int kinds[BGP_ACQ_MAX] = {0};
   double params[BGP_ACQ_MAX] = {0};
-  double* dmem = nullptr;  // one allocation, carved below
+  BgpDev<char> mem;  // one allocation, carved by bgp_fantasy_begin
   double *dXc, *dH, *dnoise, *dmu, *dvar, *dU, *dkp, *dw, *dc, *dpv, *dT, *dacc, *dmumin, *dparams;
   int *dbad, *dkinds, *dchosen, *dnext;
 };
 
 static void fantasy_free(bgp_ctx* c) {
   if (!c->fantasy) return;
-  if (c->fantasy->dmem) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->fantasy->dmem);
-  }
+  if (c->fantasy->mem) (void)hipStreamSynchronize(c->stream);
   delete c->fantasy;
   c->fantasy = nullptr;
 }
@@ -254,30 +251,31 @@ extern "C" int bgp_fantasy_begin(bgp_ctx* c, int B, const double* h_kernel, cons
   f->y_mean = y_mean, f->y_std = y_std, f->post_gen = c->post_gen;
   for (int k = 0; k < n_acq; k++) f->kinds[k] = kinds[k], f->params[k] = params[k];
   const size_t Bm = (size_t)B * mpad;
-  size_t sizes[] = {(size_t)m * d, (size_t)B * (d + 2), (size_t)B, Bm, Bm, (size_t)qmax * Bm, (size_t)B * npad, (size_t)B * npad,
-                    Bm, 2 * (size_t)B, (size_t)n_acq * Bm, (size_t)n_acq * mpad, (size_t)B + BGP_ACQ_MAX, BGP_ACQ_MAX,
-                    /* ints, in doubles */ ((size_t)n_acq * B + BGP_ACQ_MAX) / 2 + 1, BGP_ACQ_MAX, (size_t)mpad / 2 + 1, 1};
-  size_t total = 0;
-  for (size_t s : sizes) total += (s + 1) & ~(size_t)1;
-  hipError_t e = hipMalloc(&f->dmem, total * sizeof(double));
-  if (e != hipSuccess) {
-    f->dmem = nullptr;
+  rc = bgp_carve(f->mem, 16, [&](BgpCarve& s) {
+    f->dXc = s.take<double>((size_t)m * d);
+    f->dH = s.take<double>((size_t)B * (d + 2));
+    f->dnoise = s.take<double>(B);
+    f->dmu = s.take<double>(Bm);
+    f->dvar = s.take<double>(Bm);
+    f->dU = s.take<double>((size_t)qmax * Bm);
+    f->dkp = s.take<double>((size_t)B * npad);
+    f->dw = s.take<double>((size_t)B * npad);
+    f->dc = s.take<double>(Bm);
+    f->dpv = s.take<double>(2 * (size_t)B);
+    f->dT = s.take<double>((size_t)n_acq * Bm);
+    f->dacc = s.take<double>((size_t)n_acq * mpad);
+    f->dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);
+    f->dparams = s.take<double>(BGP_ACQ_MAX);
+    f->dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);
+    f->dkinds = s.take<int>(BGP_ACQ_MAX);
+    f->dchosen = s.take<int>(mpad);
+    f->dnext = s.take<int>(1);
+  });
+  if (rc) {
     fantasy_free(c);
-    bgp_set_error("bgp_fantasy_begin: hipMalloc of %zu doubles failed: %s", total, hipGetErrorString(e));
-    return BGP_ERR_HIP;
+    return rc;
   }
-  double* ptr[18];
-  size_t off = 0;
-  for (int k = 0; k < 18; k++) {
-    ptr[k] = f->dmem + off;
-    off += (sizes[k] + 1) & ~(size_t)1;
-  }
-  f->dXc = ptr[0], f->dH = ptr[1], f->dnoise = ptr[2], f->dmu = ptr[3], f->dvar = ptr[4], f->dU = ptr[5], f->dkp = ptr[6];
-  f->dw = ptr[7], f->dc = ptr[8], f->dpv = ptr[9], f->dT = ptr[10], f->dacc = ptr[11], f->dmumin = ptr[12];
-  f->dparams = ptr[13];
-  f->dbad = reinterpret_cast<int*>(ptr[14]), f->dkinds = reinterpret_cast<int*>(ptr[15]);
-  f->dchosen = reinterpret_cast<int*>(ptr[16]), f->dnext = reinterpret_cast<int*>(ptr[17]);
-  BGP_HIP(hipMemsetAsync(f->dmem, 0, total * sizeof(double), c->stream));
+  BGP_HIP(hipMemsetAsync(f->mem, 0, f->mem.cap, c->stream));  // (a fresh block: exactly the layout's bytes)
   BGP_HIP(bgp_memcpy_async(f->dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(f->dH, h_kernel, (size_t)B * (d + 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(f->dnoise, noise, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));

@@ -263,17 +263,8 @@ __global__ void __launch_bounds__(64 * KB2_WAVES, 2) kbuild2_kernel(const double
 
 static int ensure_xs(bgp_ctx* ctx, int dpad) {
   const size_t need = (size_t)ctx->max_batch * dpad * ctx->npad;
-  if (need > ctx->cap_xs) {
-    if (ctx->dXs) {
-      (void)hipDeviceSynchronize();  // (another walker group's launches may still read the old buffer)
-      (void)hipFree(ctx->dXs);
-    }
-    ctx->dXs = nullptr;
-    ctx->cap_xs = 0;
-    BGP_HIP(hipMalloc(&ctx->dXs, need * sizeof(double)));
-    ctx->cap_xs = need;
-  }
-  return BGP_OK;
+  if (need > ctx->dXs.cap && ctx->dXs) (void)hipDeviceSynchronize();  // (another walker group's launches may still read the old buffer)
+  return ctx->dXs.ensure(need);
 }
 
 int bgp_launch_kbuild(bgp_ctx* ctx, int B, int full_square, int augmented, int use_alpha) {
@@ -337,7 +328,7 @@ int bgp_lml_gen_eligible(const bgp_ctx* ctx, int B) {
 // ... and what the generator reads: the scaled inputs of the batch slice at `off` (written by the build of block column 0)
 int bgp_lml_gen_args(const bgp_ctx* ctx, int off, S4Gen* out) {
   const int dpad = ((ctx->d + KB_DK - 1) / KB_DK) * KB_DK;
-  if (!ctx->dXs || (size_t)ctx->max_batch * dpad * ctx->npad > ctx->cap_xs) {
+  if (!ctx->dXs || (size_t)ctx->max_batch * dpad * ctx->npad > ctx->dXs.cap) {
     bgp_set_error("bgp_lml_gen_args: the scaled inputs have not been built");
     return BGP_ERR_STATE;
   }

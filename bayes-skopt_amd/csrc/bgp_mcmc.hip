@@ -148,27 +148,11 @@ static void mcmc_launch_step(const McmcArgs& a, int h, int threads, bool hbm, hi
     hipLaunchKernelGGL(mcmc_step_kernel<false>, dim3(1), dim3(threads), 0, st, a, h);
 }
 
-namespace {
-struct DevBlock {  // one allocation for the whole run, released with it
-  char* base = nullptr;
-  size_t used = 0, cap = 0;
-  ~DevBlock() {
-    if (base) (void)hipFree(base);
-  }
-  template <class T>
-  T* take(size_t count) {
-    const size_t off = (used + 255) & ~(size_t)255;
-    used = off + count * sizeof(T);
-    return base ? reinterpret_cast<T*>(base + off) : nullptr;
-  }
-};
-}  // namespace
-
 // An open run (bgp_mcmc_begin .. bgp_mcmc_end): device block, kernel arguments, how far the plan has been enqueued, and a host
 // copy of the start ensemble (a run whose launch-free factorisation timed out is redone on the launch schedule from it and from
 // the plan, which stays on the device).
 struct bgp_mcmc_state {
-  DevBlock blk;
+  BgpDev<char> blk;  // one allocation for the whole run, released with it
   McmcArgs a;
   int nsteps = 0, threads = 256;
   int enq_half = 0;  // half-steps enqueued so far
@@ -301,9 +285,7 @@ extern "C" int bgp_mcmc_begin_ex(bgp_ctx* c, bgp_comm* comm, int nwarp, int W, i
   const size_t plan = (size_t)nhalf * Ns;
   std::unique_ptr<bgp_mcmc_state> r(new bgp_mcmc_state);
   McmcArgs& a = r->a;
-  for (int pass = 0; pass < 2; pass++) {  // pass 0 sizes the block, pass 1 hands out the pointers
-    DevBlock& blk = r->blk;
-    blk.used = 0;
+  const int rcb = bgp_carve(r->blk, 256, [&](BgpCarve& blk) {
     a.coords = blk.take<double>((size_t)W * p);
     a.logp = blk.take<double>(W);
     a.nacc = blk.take<long long>(W);
@@ -324,11 +306,8 @@ extern "C" int bgp_mcmc_begin_ex(bgp_ctx* c, bgp_comm* comm, int nwarp, int W, i
     a.chain = blk.take<double>((size_t)nsteps * W * p);
     a.lps = blk.take<double>((size_t)nsteps * W);
     a.info = blk.take<unsigned>(MCMC_INFO_WORDS);
-    if (pass == 0) {
-      blk.cap = blk.used;
-      BGP_HIP(hipMalloc((void**)&blk.base, blk.cap));
-    }
-  }
+  });
+  if (rcb) return rcb;
   a.W = W;
   a.p = p;
   a.Ns = Ns;

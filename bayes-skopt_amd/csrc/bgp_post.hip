@@ -104,18 +104,6 @@ __global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, in
   out[(size_t)b * M + i] = s;  // (batched row dots are packed with stride M)
 }
 
-// column-tile partials of the EPI-1 row dots (own buffer: the callers' scratch layouts stay as they are)
-static int ensure_rowpart(bgp_ctx* c, size_t doubles) {
-  if (doubles > c->cap_rowpart) {
-    if (c->drowpart) (void)hipFree(c->drowpart);
-    c->drowpart = nullptr;
-    c->cap_rowpart = 0;
-    BGP_HIP(hipMalloc(&c->drowpart, doubles * sizeof(double)));
-    c->cap_rowpart = doubles;
-  }
-  return BGP_OK;
-}
-
 __global__ void add_diag_kernel(double* __restrict__ C, int ld, int m, double v);
 
 void bgp_launch_rowquad(hipStream_t st, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
@@ -130,7 +118,8 @@ int bgp_rowquad_tile();
 static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
                           const int* pidx, int M, int n, int nb, double* out) {
   const int tn = n / bgp_rowquad_tile();
-  int rc = ensure_rowpart(c, (size_t)nb * tn * M);
+  // (column-tile partials of the row dots in a buffer of their own: the callers' scratch layouts stay as they are)
+  int rc = c->drowpart.ensure((size_t)nb * tn * M);
   if (rc) return rc;
   bgp_launch_rowquad(c->stream, A, lda, sA, S, lds_, sS, pidx, M, n, nb, c->drowpart);
   BGP_HIP(hipGetLastError());
@@ -148,22 +137,8 @@ static int ensure_resident(bgp_ctx* c, int B) {
   // K^-1 needs B npad^2 doubles, alpha B npad: the two capacities are tracked separately (a context reused through
   // bgp_ctx_update_data may see n shrink and B grow: B=1 at npad=1024 and B=64 at npad=128 need the same K^-1
   // bytes but 8x the alpha bytes)
-  const size_t need = (size_t)B * c->npad * c->npad, need_a = (size_t)B * c->npad;
-  if (need > c->cap_kinv) {
-    if (c->dKinv) (void)hipFree(c->dKinv);
-    c->dKinv = nullptr;
-    c->cap_kinv = 0;
-    BGP_HIP(hipMalloc(&c->dKinv, need * sizeof(double)));
-    c->cap_kinv = need;
-  }
-  if (need_a > c->cap_alpha) {
-    if (c->dalpha_sol) (void)hipFree(c->dalpha_sol);
-    c->dalpha_sol = nullptr;
-    c->cap_alpha = 0;
-    BGP_HIP(hipMalloc(&c->dalpha_sol, need_a * sizeof(double)));
-    c->cap_alpha = need_a;
-  }
-  return BGP_OK;
+  const int rc = c->dKinv.ensure((size_t)B * c->npad * c->npad);
+  return rc ? rc : c->dalpha_sol.ensure((size_t)B * c->npad);
 }
 
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
@@ -174,7 +149,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
   int rc = ensure_resident(c, B);
   if (rc) return rc;
   // augmented matrices are 4x the LML workspace per item
-  int chunk = (int)(c->cap_mat / (ld * ld));
+  int chunk = (int)(c->dK.cap / (ld * ld));
   if (chunk < 1) {
     rc = bgp_grow_workspace(c, ld * ld);
     if (rc) return rc;
@@ -210,12 +185,14 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
                                  c->dKinv + (size_t)(off + b) * npad * npad, (size_t)npad * sizeof(double),
                                  (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
     if (L) {
-      rc = bgp_ensure_scratch(c, (size_t)n * n);
+      BgpScratch live(c);
+      double* dL = nullptr;
+      rc = live.carve([&](BgpCarve& s) { dL = s.take<double>((size_t)n * n); });
       if (rc) return rc;
       for (int b = 0; b < nb; b++) {
-        hipLaunchKernelGGL(extract_L_kernel, dim3(512), dim3(256), 0, c->stream, c->dK, c->dscratch, n, (int)ld,
+        hipLaunchKernelGGL(extract_L_kernel, dim3(512), dim3(256), 0, c->stream, c->dK, dL, n, (int)ld,
                            ld * ld, b);
-        BGP_HIP(bgp_memcpy_async(L + (size_t)(off + b) * n * n, c->dscratch, (size_t)n * n * sizeof(double),
+        BGP_HIP(bgp_memcpy_async(L + (size_t)(off + b) * n * n, dL, (size_t)n * n * sizeof(double),
                                hipMemcpyDeviceToHost, c->stream));
         BGP_HIP(bgp_stream_sync(c->stream));
       }
@@ -256,17 +233,6 @@ extern "C" int bgp_posterior_batch_gram(bgp_ctx* c, int B, const double* K, int 
 // ------------------------------------------------------------------------------------------
 // predict
 // ------------------------------------------------------------------------------------------
-// scratch layout helper
-struct Scratch {
-  double* base;
-  size_t used;
-  double* take(size_t n) {
-    double* p = base + used;
-    used += (n + 1) & ~(size_t)1;  // keep 16-byte alignment
-    return p;
-  }
-};
-
 static double kernel_diag_value(const bgp_ctx* c, const double* hk) {
   // kernel_.diag(X) incl. the white level: sklearn/kernels.py:868-884, 968-984
   const double cst = std::exp(hk[0]), s2 = std::exp(hk[c->d + 1]);
@@ -310,22 +276,28 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
   if (chunk >= 8 && chunk < B) chunk &= ~7;  // whole rounds of the item -> XCD pinning (rowquad4_kernel)
   const int n_acq = ap ? ap->n_acq : 0;
-  size_t need = (size_t)m * d + 2 + (size_t)B * p + 2 + (size_t)chunk * per_item + 2 * (size_t)B * mpad + 64 + (size_t)chunk * (npad / 128) * mpad +
-                (size_t)n_acq * ((size_t)B * mpad + (size_t)B + mpad) + 2 * (size_t)B + 64;
-  int rc = bgp_ensure_scratch(c, need);
+  double *dXq, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr, *dT = nullptr, *dacc = nullptr, *dmumin = nullptr;
+  int* dbad = nullptr;
+  BgpScratch live(c);
+  int rc = live.carve([&](BgpCarve& s) {
+    dXq = s.take<double>((size_t)m * d);
+    dH = s.take<double>((size_t)B * p);
+    dKs = s.take<double>((size_t)chunk * mpad * npad);
+    dmpart = s.take<double>((size_t)chunk * (npad / 128) * mpad);  // column-tile partials of the means
+    dqB = s.take<double>((size_t)B * mpad);    // variance of every item (stays on the device for the acquisitions)
+    doutB = s.take<double>((size_t)B * mpad);  // mean of every item
+    if (cov) {
+      dP = s.take<double>((size_t)chunk * mpad * npad);
+      dCov = s.take<double>((size_t)chunk * mpad * mpad);
+    }
+    if (n_acq) {  // (acq_run keeps the parameters behind dmumin's B entries and the kinds behind dbad's n_acq * B)
+      dT = s.take<double>((size_t)n_acq * B * mpad);
+      dacc = s.take<double>((size_t)n_acq * mpad);
+      dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);
+      dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);
+    }
+  });
   if (rc) return rc;
-  Scratch s{c->dscratch, 0};
-  double* dXq = s.take((size_t)m * d);
-  double* dH = s.take((size_t)B * p);
-  double* dKs = s.take((size_t)chunk * mpad * npad);
-  double* dmpart = s.take((size_t)chunk * (npad / 128) * mpad);  // column-tile partials of the means
-  double* dqB = s.take((size_t)B * mpad);    // variance of every item (stays on the device for the acquisitions)
-  double* doutB = s.take((size_t)B * mpad);  // mean of every item
-  double *dP = nullptr, *dCov = nullptr;
-  if (cov) {
-    dP = s.take((size_t)chunk * mpad * npad);
-    dCov = s.take((size_t)chunk * mpad * mpad);
-  }
   const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
   BGP_HIP(bgp_memcpy_async(dXq, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -373,10 +345,6 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     // (the next chunk reuses the scratch slices: stream order keeps its launches behind these copies)
   }
   if (n_acq) {
-    double* dT = s.take((size_t)n_acq * B * mpad);
-    double* dacc = s.take((size_t)n_acq * mpad);
-    double* dmumin = s.take((size_t)B + BGP_ACQ_MAX);
-    int* dbad = reinterpret_cast<int*>(s.take((size_t)n_acq * B / 2 + BGP_ACQ_MAX));
     rc = acq_run(c, c->stream, B, m, mpad, doutB, dqB, *ap, dT, dbad, dmumin, dacc);
     if (rc) return rc;
   }
@@ -425,18 +393,19 @@ extern "C" int bgp_predict_batch_gram(bgp_ctx* c, int B, int m, const double* Ks
   const size_t budget = (size_t)1 << 29;
   int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
   if (chunk >= 8 && chunk < B) chunk &= ~7;
-  int rc = bgp_ensure_scratch(c, (size_t)chunk * per_item + 64);
+  double *dKs, *dq, *dout, *dkss, *dP = nullptr, *dCov = nullptr;
+  BgpScratch live(c);
+  int rc = live.carve([&](BgpCarve& s) {
+    dKs = s.take<double>((size_t)chunk * sKs);
+    dq = s.take<double>((size_t)chunk * mpad);
+    dout = s.take<double>((size_t)chunk * mpad);
+    dkss = s.take<double>((size_t)chunk * mpad);
+    if (cov) {
+      dP = s.take<double>((size_t)chunk * sKs);
+      dCov = s.take<double>((size_t)chunk * sCv);
+    }
+  });
   if (rc) return rc;
-  Scratch s{c->dscratch, 0};
-  double* dKs = s.take((size_t)chunk * sKs);
-  double* dq = s.take((size_t)chunk * mpad);
-  double* dout = s.take((size_t)chunk * mpad);
-  double* dkss = s.take((size_t)chunk * mpad);
-  double *dP = nullptr, *dCov = nullptr;
-  if (cov) {
-    dP = s.take((size_t)chunk * sKs);
-    dCov = s.take((size_t)chunk * sCv);
-  }
   for (int off = 0; off < B; off += chunk) {
     const int nb = std::min(chunk, B - off);
     const double* Kinv = c->dKinv + (size_t)off * npad * npad;
@@ -623,15 +592,18 @@ extern "C" int bgp_acq_values(bgp_ctx* c, int B, int m, const double* mu, const 
   if (rc) return rc;
   BGP_HIP(hipSetDevice(c->device));
   const int mpad = pad128(m);
-  rc = bgp_ensure_scratch(c, 2 * (size_t)B * mpad + (size_t)n_acq * ((size_t)B * mpad + B + mpad) + 2 * (size_t)B + 64);
+  double *dmu, *dvar, *dT, *dacc, *dmumin;
+  int* dbad;
+  BgpScratch live(c);
+  rc = live.carve([&](BgpCarve& s) {
+    dmu = s.take<double>((size_t)B * mpad);
+    dvar = s.take<double>((size_t)B * mpad);
+    dT = s.take<double>((size_t)n_acq * B * mpad);
+    dacc = s.take<double>((size_t)n_acq * mpad);
+    dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);       // (+ the parameters: acq_run)
+    dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);    // (+ the kinds)
+  });
   if (rc) return rc;
-  Scratch s{c->dscratch, 0};
-  double* dmu = s.take((size_t)B * mpad);
-  double* dvar = s.take((size_t)B * mpad);
-  double* dT = s.take((size_t)n_acq * B * mpad);
-  double* dacc = s.take((size_t)n_acq * mpad);
-  double* dmumin = s.take((size_t)B + BGP_ACQ_MAX);
-  int* dbad = reinterpret_cast<int*>(s.take((size_t)n_acq * B / 2 + BGP_ACQ_MAX));
   BGP_HIP(bgp_memcpy2d_async(dmu, (size_t)mpad * sizeof(double), mu, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
                            B, hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy2d_async(dvar, (size_t)mpad * sizeof(double), std_, (size_t)m * sizeof(double),
@@ -825,11 +797,14 @@ extern "C" int bgp_lml_grad_batch(bgp_ctx* c, int B, const double* h, double* lm
   if (rc) return rc;
   c->post_B = 0;  // the resident K^-1 belong to a gradient evaluation, not to a posterior
   const int ntiles = c->nblk * (c->nblk + 1) / 2;
-  rc = bgp_ensure_scratch(c, (size_t)B * p * (2 + ntiles));
+  double *dgrad, *dH, *dgpart;
+  BgpScratch live(c);
+  rc = live.carve([&](BgpCarve& s) {
+    dgrad = s.take<double>((size_t)B * p);
+    dH = s.take<double>((size_t)B * p);
+    dgpart = s.take<double>((size_t)B * p * ntiles);
+  });
   if (rc) return rc;
-  double* dgrad = c->dscratch;
-  double* dH = c->dscratch + (size_t)B * p;
-  double* dgpart = c->dscratch + (size_t)B * p * 2;
   BGP_HIP(hipMemsetAsync(dgpart, 0, (size_t)B * p * ntiles * sizeof(double), c->stream));
   BGP_HIP(bgp_memcpy_async(dH, h, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(lml_grad_kernel, dim3(8 * ((B + 7) / 8) * ntiles), dim3(256), 0, c->stream, c->dXeff, dH, c->dKinv,
@@ -880,22 +855,23 @@ extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double*
   BGP_HIP(hipSetDevice(c->device));
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), Tpad = pad128(T);
   const size_t p = d + 2;
-  size_t need = (size_t)m * d + (size_t)T * d + p + 128 + (size_t)mpad * npad + 2 * (size_t)Tpad * npad +
-                2 * (size_t)mpad * Tpad + 2 * (size_t)mpad + 2 * (size_t)Tpad;
-  int rc = bgp_ensure_scratch(c, need);
+  double *dXc, *dXt, *dhk, *dKc, *dKT, *dPT, *dG, *dKti, *du, *dcov, *dst, *dend;
+  BgpScratch live(c);
+  int rc = live.carve([&](BgpCarve& s) {
+    dXc = s.take<double>((size_t)m * d);
+    dXt = s.take<double>((size_t)T * d);
+    dhk = s.take<double>(p);
+    dKc = s.take<double>((size_t)mpad * npad);   // k(cand, train)
+    dKT = s.take<double>((size_t)Tpad * npad);   // k(thompson, train)
+    dPT = s.take<double>((size_t)Tpad * npad);   // K_T Kinv
+    dG = s.take<double>((size_t)mpad * Tpad);    // K_c Kinv K_T^T
+    dKti = s.take<double>((size_t)mpad * Tpad);  // k(cand, thompson)
+    du = s.take<double>(mpad);
+    dcov = s.take<double>(mpad);
+    dst = s.take<double>(Tpad);
+    dend = s.take<double>(0);
+  });
   if (rc) return rc;
-  Scratch s{c->dscratch, 0};
-  double* dXc = s.take((size_t)m * d);
-  double* dXt = s.take((size_t)T * d);
-  double* dhk = s.take(p);
-  double* dKc = s.take((size_t)mpad * npad);   // k(cand, train)
-  double* dKT = s.take((size_t)Tpad * npad);   // k(thompson, train)
-  double* dPT = s.take((size_t)Tpad * npad);   // K_T Kinv
-  double* dG = s.take((size_t)mpad * Tpad);    // K_c Kinv K_T^T
-  double* dKti = s.take((size_t)mpad * Tpad);  // k(cand, thompson)
-  double* du = s.take(mpad);
-  double* dcov = s.take(mpad);
-  double* dst = s.take(Tpad);
   const double* Kinv = c->dKinv;
   BGP_HIP(bgp_memcpy_async(dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(dXt, Xthompson, (size_t)T * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -906,8 +882,7 @@ extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double*
     rc = bgp_launch_warp(c, c->stream, dXt, c->dwarp, dXt, T, 1, 0);
     if (rc) return rc;
   }
-  BGP_HIP(hipMemsetAsync(dKc, 0, ((size_t)mpad * npad + 2 * (size_t)Tpad * npad + 2 * (size_t)mpad * Tpad +
-                                   2 * (size_t)mpad + 2 * (size_t)Tpad + 16) * sizeof(double), c->stream));
+  BGP_HIP(hipMemsetAsync(dKc, 0, (size_t)(dend - dKc) * sizeof(double), c->stream));  // (zero padding of every matrix and vector)
   rc = bgp_launch_kcross(c, dhk, m, dXc, n, c->dXeff, dKc, npad, 0);
   if (rc) return rc;
   rc = bgp_launch_kcross(c, dhk, T, dXt, n, c->dXeff, dKT, npad, 0);
@@ -978,21 +953,6 @@ __global__ void add_mean_rows_kernel(double* __restrict__ out, int ldo, const do
   if (j < m && i < rows) out[(size_t)i * ldo + j] += mean[j];
 }
 
-static void free_child(bgp_ctx* w) {
-  if (!w) return;
-  if (w->dK) (void)hipFree(w->dK);
-  if (w->dW) (void)hipFree(w->dW);
-  if (w->dyw) (void)hipFree(w->dyw);
-  if (w->dacc) (void)hipFree(w->dacc);
-  if (w->dlml) (void)hipFree(w->dlml);
-  if (w->dstatus) (void)hipFree(w->dstatus);
-  // (launch-free factorisation of the covariance: its own flag block)
-  if (w->ps_flags) (void)hipFree(w->ps_flags);
-  if (w->ps_trace) (void)hipFree(w->ps_trace);
-  if (w->ps_herr) (void)hipHostFree(w->ps_herr);
-  delete w;
-}
-
 static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out);
 
 // out[r] = mean + L z[r] for ALL draws r of one posterior: one wave per row of the lower factor, which is read once
@@ -1048,17 +1008,18 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
   w->npad = mpad;
   w->nblk = mpad / 128;
   do {
-    size_t need = (size_t)m * d + p + 2 * (size_t)mpad * npad + 2 * (size_t)mpad + 2 * (size_t)rpad * mpad + 64;
-    rc = bgp_ensure_scratch(c, need);
+    double *dXq, *dhk, *dKs, *dP, *dmean, *dZ, *dO;
+    BgpScratch live(c);
+    rc = live.carve([&](BgpCarve& s) {
+      dXq = s.take<double>((size_t)m * d);
+      dhk = s.take<double>(p);
+      dKs = s.take<double>((size_t)mpad * npad);
+      dP = s.take<double>((size_t)mpad * npad);
+      dmean = s.take<double>(mpad);
+      dZ = s.take<double>((size_t)rpad * mpad);
+      dO = s.take<double>((size_t)rpad * mpad);
+    });
     if (rc) break;
-    Scratch s{c->dscratch, 0};
-    double* dXq = s.take((size_t)m * d);
-    double* dhk = s.take(p);
-    double* dKs = s.take((size_t)mpad * npad);
-    double* dP = s.take((size_t)mpad * npad);
-    double* dmean = s.take(mpad);
-    double* dZ = s.take((size_t)rpad * mpad);
-    double* dO = s.take((size_t)rpad * mpad);
     const double* Kinv = c->dKinv + (size_t)b * npad * npad;
     const double* al = c->dalpha_sol + (size_t)b * npad;
     hipError_t e = hipSuccess;
@@ -1150,9 +1111,9 @@ __global__ void __launch_bounds__(256) tri_matvec_kernel(const double* __restric
 // parent and grown on demand (rows mpad, nb matrices side by side)
 static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out) {
   bgp_ctx* w = c->child;
-  if (w && (w->cap_n < (size_t)mpad || w->max_batch < nb)) {
-    free_child(w);
-    w = c->child = nullptr;
+  if (w && (w->dyw.cap < (size_t)w->max_batch * mpad || w->max_batch < nb)) {  // (dyw holds max_batch x its row capacity)
+    bgp_free_child(c);
+    w = nullptr;
   }
   if (!w) {
     w = new bgp_ctx();
@@ -1162,18 +1123,17 @@ static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out) {
     w->d = c->d;
     w->max_batch = nb;
     const size_t B8 = 8 * ((size_t)(nb + 7) / 8);
-    if (hipMalloc(&w->dK, (size_t)nb * mpad * mpad * sizeof(double)) != hipSuccess ||
-        hipMalloc(&w->dW, (size_t)nb * (mpad / 128) * 128 * 128 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&w->dyw, (size_t)nb * mpad * sizeof(double)) != hipSuccess ||
-        hipMalloc(&w->dacc, B8 * 4 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&w->dlml, B8 * sizeof(double)) != hipSuccess || hipMalloc(&w->dstatus, B8 * sizeof(int)) != hipSuccess) {
-      bgp_set_error("hipMalloc of the %d x (%d x %d) covariance workspace failed", nb, mpad, mpad);
-      (void)hipGetLastError();
-      free_child(w);
-      return BGP_ERR_HIP;
-    }
-    w->cap_n = mpad;
     c->child = w;
+    int rc = w->dK.ensure((size_t)nb * mpad * mpad);
+    if (!rc) rc = w->dW.ensure((size_t)nb * (mpad / 128) * 128 * 128);
+    if (!rc) rc = w->dyw.ensure((size_t)nb * mpad);
+    if (!rc) rc = w->dacc.ensure(B8 * 4);
+    if (!rc) rc = w->dlml.ensure(B8);
+    if (!rc) rc = w->dstatus.ensure(B8);
+    if (rc) {
+      bgp_free_child(c);
+      return rc;
+    }
   }
   w->panels = c->panels;
   w->panels_auto = c->panels_auto;
@@ -1212,18 +1172,20 @@ extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const doub
   w->n = m;
   w->npad = mpad;
   w->nblk = mpad / 128;
-  size_t need = (size_t)m * d + 2 + (size_t)B * p + 2 + (size_t)chunk * (2 * sKs + 3 * (size_t)mpad) + (size_t)B + 64;
-  rc = bgp_ensure_scratch(c, need);
+  double *dXq, *dH, *dKs, *dP, *dmean, *dZ, *dO;
+  int* dpidx;
+  BgpScratch live(c);
+  rc = live.carve([&](BgpCarve& s) {
+    dXq = s.take<double>((size_t)m * d);
+    dH = s.take<double>((size_t)B * p);
+    dKs = s.take<double>((size_t)chunk * sKs);
+    dP = s.take<double>((size_t)chunk * sKs);
+    dmean = s.take<double>((size_t)chunk * mpad);
+    dZ = s.take<double>((size_t)chunk * mpad);
+    dO = s.take<double>((size_t)chunk * mpad);
+    dpidx = s.take<int>(B);
+  });
   if (rc) return rc;
-  Scratch s{c->dscratch, 0};
-  double* dXq = s.take((size_t)m * d);
-  double* dH = s.take((size_t)B * p);
-  double* dKs = s.take((size_t)chunk * sKs);
-  double* dP = s.take((size_t)chunk * sKs);
-  double* dmean = s.take((size_t)chunk * mpad);
-  double* dZ = s.take((size_t)chunk * mpad);
-  double* dO = s.take((size_t)chunk * mpad);
-  int* dpidx = reinterpret_cast<int*>(s.take(((size_t)B + 1) / 2 + 1));
   BGP_HIP(bgp_memcpy_async(dXq, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(dpidx, pidx, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -1265,9 +1227,9 @@ extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const doub
   return BGP_OK;
 }
 
+// (the child owns its buffers and BORROWS the parent's stream: it is deleted, never passed to bgp_ctx_destroy)
 void bgp_free_child(bgp_ctx* c) {
-  if (c && c->child) {
-    free_child(c->child);
-    c->child = nullptr;
-  }
+  if (!c) return;
+  delete c->child;
+  c->child = nullptr;
 }

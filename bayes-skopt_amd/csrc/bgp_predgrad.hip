@@ -379,16 +379,6 @@ __global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict_
   }
 }
 
-struct PgScratch {
-  double* base;
-  size_t used;
-  double* take(size_t k) {
-    double* q = base + used;
-    used += (k + 1) & ~(size_t)1;
-    return q;
-  }
-};
-
 static int pg_check(bgp_ctx* c, const char* who) {
   if (c->d > PG_DMAX || c->has_warp) {
     bgp_set_error("%s: %s", who, c->has_warp ? "warped inputs are not supported" : "d > 32 is not supported");
@@ -420,16 +410,18 @@ extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel,
   mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)B * (2 + 2 * (size_t)d))));
   if (!lds) mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 26) / ((size_t)B * 2 * npad)));
   const size_t Bm = (size_t)B * mc;
-  rc = bgp_ensure_scratch(c, mc * d + B * p + 2 * Bm + 2 * Bm * d + (lds ? 0 : Bm * 2 * npad) + 64);
+  double *dXq, *dH, *dm, *dv, *ddm, *ddv, *rows = nullptr;
+  BgpScratch live(c);
+  rc = live.carve([&](BgpCarve& s) {
+    dXq = s.take<double>(mc * d);
+    dH = s.take<double>(B * p);
+    dm = s.take<double>(Bm);
+    dv = s.take<double>(Bm);
+    ddm = s.take<double>(Bm * d);
+    ddv = s.take<double>(Bm * d);
+    if (!lds) rows = s.take<double>(Bm * 2 * npad);
+  });
   if (rc) return rc;
-  PgScratch s{c->dscratch, 0};
-  double* dXq = s.take(mc * d);
-  double* dH = s.take(B * p);
-  double* dm = s.take(Bm);
-  double* dv = s.take(Bm);
-  double* ddm = s.take(Bm * d);
-  double* ddv = s.take(Bm * d);
-  double* rows = lds ? nullptr : s.take(Bm * 2 * npad);
   const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
   for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
@@ -474,21 +466,23 @@ extern "C" int bgp_minimize_starts(bgp_ctx* c, int b, const double* h_kernel, do
   const int n = c->n, d = c->d, npad = c->npad;
   const size_t p = d + 2, Sd = (size_t)S_ * d;
   const bool lds = n <= PG_NLDS;
-  rc = bgp_ensure_scratch(c, p + 2 * Sd + 2 * (size_t)d + 2 * (size_t)S_ + 3 * ((size_t)S_ / 2 + 1) +
-                                 (lds ? 0 : (size_t)S_ * 2 * npad) + 64);
+  double *dH, *dX0, *dXo, *dlo, *dhi, *dm, *dv, *rows = nullptr;
+  int *dit, *dev, *dst;
+  BgpScratch live(c);
+  rc = live.carve([&](BgpCarve& s) {
+    dH = s.take<double>(p);
+    dX0 = s.take<double>(Sd);
+    dXo = s.take<double>(Sd);
+    dlo = s.take<double>(d);
+    dhi = s.take<double>(d);
+    dm = s.take<double>(S_);
+    dv = s.take<double>(S_);
+    dit = s.take<int>(S_);
+    dev = s.take<int>(S_);
+    dst = s.take<int>(S_);
+    if (!lds) rows = s.take<double>((size_t)S_ * 2 * npad);
+  });
   if (rc) return rc;
-  PgScratch s{c->dscratch, 0};
-  double* dH = s.take(p);
-  double* dX0 = s.take(Sd);
-  double* dXo = s.take(Sd);
-  double* dlo = s.take(d);
-  double* dhi = s.take(d);
-  double* dm = s.take(S_);
-  double* dv = s.take(S_);
-  int* dit = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
-  int* dev = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
-  int* dst = reinterpret_cast<int*>(s.take((size_t)S_ / 2 + 1));
-  double* rows = lds ? nullptr : s.take((size_t)S_ * 2 * npad);
   const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
   hipStream_t st = c->stream;
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, st));

@@ -79,11 +79,11 @@ extern "C" int bgp_ctx_set_warp(bgp_ctx* c, const double* warp) {
     c->dXeff = c->dX;
     return BGP_OK;
   }
-  const size_t nd = (size_t)c->cap_n * c->d;
-  if (!c->dXw1) BGP_HIP(hipMalloc(&c->dXw1, nd * sizeof(double)));
-  if (!c->dwarp) BGP_HIP(hipMalloc(&c->dwarp, 2 * (size_t)c->d * sizeof(double)));
+  int rc = c->dXw1.ensure(c->dy.cap * c->d);  // (the training set's row capacity: alloc_data frees it when that grows)
+  if (!rc) rc = c->dwarp.ensure(2 * (size_t)c->d);
+  if (rc) return rc;
   BGP_HIP(bgp_memcpy_async(c->dwarp, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  int rc = bgp_launch_warp(c, c->stream, c->dX, c->dwarp, c->dXw1, c->n, 1, 0);
+  rc = bgp_launch_warp(c, c->stream, c->dX, c->dwarp, c->dXw1, c->n, 1, 0);
   if (rc) return rc;
   BGP_HIP(bgp_stream_sync(c->stream));
   c->has_warp = 1;
@@ -100,11 +100,14 @@ extern "C" int bgp_beta_cdf(bgp_ctx* c, int m, const double* X, const double* wa
   BGP_REQUIRE_IDLE(c, "bgp_beta_cdf");
   BGP_HIP(hipSetDevice(c->device));
   const size_t md = (size_t)m * c->d;
-  int rc = bgp_ensure_scratch(c, 2 * md + 2 * (size_t)c->d + 8);
+  double *dXi, *dXo, *dW;
+  BgpScratch live(c);
+  int rc = live.carve([&](BgpCarve& s) {
+    dXi = s.take<double>(md);
+    dXo = s.take<double>(md);
+    dW = s.take<double>(2 * (size_t)c->d);
+  });
   if (rc) return rc;
-  double* dXi = c->dscratch;
-  double* dXo = c->dscratch + md;
-  double* dW = c->dscratch + 2 * md;
   BGP_HIP(bgp_memcpy_async(dXi, X, md * sizeof(double), hipMemcpyHostToDevice, c->stream));
   BGP_HIP(bgp_memcpy_async(dW, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   rc = bgp_launch_warp(c, c->stream, dXi, dW, dXo, m, 1, 0);
