@@ -288,7 +288,7 @@ struct PsArgs {
   unsigned long long spin_limit;  // wall_clock64 ticks (100 MHz) a single wait may last before the call is abandoned
   unsigned long long* trace;      // debugging (BGP_PS_TRACE=1): wall-clock stamps, chain: 8 per (b, J), tile: 8 per task
   // gen = 1: the Gram matrices are generated INSIDE this launch -- the first B nblk (nblk + 1) / 2 tickets of the tile list are one
-  // 128 x 128 block each (kb_gram_tile512; block (I, 0) also sets up row block I of the right-hand side), genrdy[b][I][J] tells
+  // 128 x 128 block each (kb_tile, bgp_kb.h; block (I, 0) also sets up row block I of the right-hand side), genrdy[b][I][J] tells
   // its consumer -- instead of by a Gram kernel in front of it (Matern-5/2 product form, one chain workgroup per matrix, one list)
   int gen, d;
   const double* X;      // n x d training inputs
@@ -411,7 +411,7 @@ int bgp_launch_kbuild_x(bgp_ctx* ctx, int off, int B, hipStream_t st, int full_s
                         const double* dXb, size_t xstride);
 // Cross kernel matrix k(Xq, X_train) for hyper-vector index b: out is m x ldo row-major (device).
 int bgp_launch_kcross(bgp_ctx* ctx, const double* dh_b, int m, const double* dXq, int nx, const double* dXt,
-                      double* dout, int ldo, int symmetric_diag_fix);
+                      double* dout, int ldo);
 // the same for nb hyper-vectors dH (nb x (d+2)) into dout + b * ostride
 int bgp_launch_kcross_batch(bgp_ctx* ctx, int nb, const double* dH, int m, const double* dXq, int nx, const double* dXt,
                             double* dout, int ldo, size_t ostride);

@@ -2,19 +2,6 @@
 #pragma once
 #include "bgp_common.h"
 
-static __device__ __forceinline__ double bgp_stationary(double r2, int stat) {
-  // same operation order as sklearn/kernels.py:1553-1560 and :1713-1733
-  if (stat == BGP_RBF) return exp(-0.5 * r2);
-  double dist = sqrt(r2);
-  if (stat == BGP_MATERN12) return exp(-dist);
-  if (stat == BGP_MATERN32) {
-    double t = dist * 1.7320508075688772;  // math.sqrt(3)
-    return (1.0 + t) * exp(-t);
-  }
-  double t = dist * 2.23606797749979;  // math.sqrt(5)
-  return (1.0 + t + t * t / 3.0) * exp(-t);
-}
-
 // ---- in-launch hand-off between workgroups (persistent factorisation; cdna_hip_programming.md section 6, Guideline 16) ----
 // Every shared word is accessed with relaxed AGENT-scope atomics (sc1: they bypass the per-CU L1); payload visibility
 // comes from ONE agent-scope release on the producer (after every storing wave has drained its stores and the workgroup
@@ -162,25 +149,84 @@ static __device__ __forceinline__ double kb_sqrt_pos(double x) {
   return (x == 0.0) ? 0.0 : g;
 }
 
-// Compile-time stationary kernel (same operation order as sklearn/kernels.py:1553-1560, 1713-1733;
-// the Matern-5/2 term K**2/3.0 is evaluated as t*t*(1/3): <= 1 ulp from the reference's division; exp / sqrt are the
-// domain-specific versions above: <= 1 ulp from libm's).
+// Compile-time stationary kernel S(r) from the squared scaled distance (same operation order as
+// sklearn/kernels.py:1553-1560, 1713-1733; the Matern-5/2 term K**2/3.0 is evaluated as t*t*(1/3): <= 1 ulp from the
+// reference's division; exp / sqrt are the domain-specific versions above: <= 1 ulp from libm's).
 // No implicit fused multiply-add here (hipcc's default contraction is decided per call site by the backend: two
 // kernels inlining this function could otherwise round the Matern polynomial differently).
 template <int STAT>
 static __device__ __forceinline__ double kb_stationary(double r2) {
 #pragma clang fp contract(off)
   if (STAT == BGP_RBF) return kb_exp_neg(0.5 * r2);
-  const double dist = kb_sqrt_pos(r2);
-  if (STAT == BGP_MATERN12) return kb_exp_neg(dist);
+  const double r = kb_sqrt_pos(r2);
+  if (STAT == BGP_MATERN12) return kb_exp_neg(r);
   if (STAT == BGP_MATERN32) {
-    const double t = dist * 1.7320508075688772;  // math.sqrt(3)
+    const double t = r * 1.7320508075688772;  // math.sqrt(3)
     return (1.0 + t) * kb_exp_neg(t);
   }
-  const double t = dist * 2.23606797749979;  // math.sqrt(5)
+  const double t = r * 2.23606797749979;  // math.sqrt(5)
   return (1.0 + t + t * t * 0.3333333333333333) * kb_exp_neg(t);
 }
+// ... and with fac(r) = (dS/dr) / r (the prediction gradients, bgp_predgrad.hip).  The expressions for S are the ones above,
+// to be kept character for character.  The two stand side by side, not one inside the other: the instruction streams of the
+// Gram and trailing-update kernels depend on kb_stationary being a function of its own.
+template <int STAT>
+static __device__ __forceinline__ void kb_stationary_fac(double r2, double& S, double& fac) {
+#pragma clang fp contract(off)
+  if (STAT == BGP_RBF) {
+    S = kb_exp_neg(0.5 * r2);
+    fac = -S;
+    return;
+  }
+  const double r = kb_sqrt_pos(r2);
+  if (STAT == BGP_MATERN12) {
+    S = kb_exp_neg(r);
+    fac = (r > 0.0) ? -S / r : 0.0;  // (the r = 0 rule of grad_x)
+    return;
+  }
+  if (STAT == BGP_MATERN32) {
+    const double t = r * 1.7320508075688772;  // math.sqrt(3)
+    const double e = kb_exp_neg(t);
+    S = (1.0 + t) * e;
+    fac = -3.0 * e;
+    return;
+  }
+  const double t = r * 2.23606797749979;  // math.sqrt(5)
+  const double e = kb_exp_neg(t);
+  S = (1.0 + t + t * t * 0.3333333333333333) * e;
+  fac = -(5.0 / 3.0) * ((1.0 + t) * e);
+}
 
+// THE entry of the canonical kernel matrix: every generator (the Gram / cross kernels and the launch-free kernel's tile
+// workers through kb_epilogue, the trailing update's S4GenF, the fused n <= 128 launch's pf_generate_tile, the fantasy
+// updates, the prediction gradients) takes its values from here, so that they agree bit for bit.  No implicit contraction.
+// Reference: kernel_(X_train_) + diagonal add -- sklearn/kernels.py:1708-1738 (Matern.__call__), :1553-1560 (RBF), :966 (Product),
+// :866 (Sum), :1273 (Constant), :1402 (White), sklearn/_gpr.py:585 / bask/bayesgpr.py:204 (K[diag] += alpha).
+// The constant applied to a stationary value S (S = 1: the diagonal before the noise terms): c * S or c + S.
+template <int FORM>
+static __device__ __forceinline__ double kb_with_constant(double cst, double S) {
+#pragma clang fp contract(off)
+  return (FORM == BGP_FORM_PRODUCT) ? cst * S : cst + S;
+}
+// Off-diagonal / cross value from the squared scaled distance.
+template <int STAT, int FORM>
+static __device__ __forceinline__ double kb_value(double r2, double cst) {
+  return kb_with_constant<FORM>(cst, kb_stationary<STAT>(r2));
+}
+// Entry (gi, gj) of the n x n Gram matrix inside its padded buffer.  alpha may be nullptr.
+template <int STAT, int FORM>
+static __device__ __forceinline__ double kb_gram_entry(double r2, int gi, int gj, int n, double cst, double s2,
+                                                       const double* __restrict__ alpha) {
+#pragma clang fp contract(off)
+  if (gi >= n || gj >= n) return (gi == gj) ? 1.0 : 0.0;  // identity padding: log det and z unaffected
+  if (gi == gj) {
+    // fill_diagonal(1) (kernels.py:1738) -> c*1 (+1) -> + s2 (White) -> += alpha (_gpr.py:585)
+    double v = (kb_with_constant<FORM>(cst, 1.0) + s2);
+    if (alpha) v += alpha[gi];
+    return v;
+  }
+  return kb_value<STAT, FORM>(r2, cst);
+}
 
 // (stationary, form) -> instantiation
 #define KB_DISPATCH(STATV, FORMV, CALL)                                      \

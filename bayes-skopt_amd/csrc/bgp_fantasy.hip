@@ -47,8 +47,8 @@ static void fantasy_free(bgp_ctx* c) {
 
 void bgp_fantasy_abandon(bgp_ctx* c) { fantasy_free(c); }
 
-// kp_b[k] = k_b(x_k, x_p) for the n training points (zero padding up to npad); the arithmetic of kb_epilogue's
-// cross entries (x / l, (a - b)^2 accumulated with fma in ascending dimension, kb_stationary, c * S or c + S)
+// kp_b[k] = k_b(x_k, x_p) for the n training points (zero padding up to npad): x / l, (a - b)^2 accumulated with fma in
+// ascending dimension, kb_value (bgp_device.h) -- the cross kernel's entries
 template <int STAT, int FORM>
 __global__ void __launch_bounds__(256) fant_kp_kernel(const double* __restrict__ X, int n, int npad, int d,
                                                       const double* __restrict__ Xc, int p, const double* __restrict__ H,
@@ -65,8 +65,7 @@ __global__ void __launch_bounds__(256) fant_kp_kernel(const double* __restrict__
       const double df = Xc[(size_t)p * d + t] / l - X[(size_t)k * d + t] / l;
       r2 = fma(df, df, r2);
     }
-    const double s = kb_stationary<STAT>(r2), cst = exp(h[0]);
-    v = (FORM == BGP_FORM_PRODUCT) ? cst * s : cst + s;
+    v = kb_value<STAT, FORM>(r2, exp(h[0]));
   }
   kp[(size_t)b * npad + k] = v;
 }
@@ -119,8 +118,7 @@ __global__ void __launch_bounds__(256) fant_col_kernel(const double* __restrict_
       r2 = fma(df, df, r2);
     }
   // k_b(x_i, x_p)
-  const double sp = kb_stationary<STAT>(r2);
-  const double kip = (FORM == BGP_FORM_PRODUCT) ? cst * sp : cst + sp;
+  const double kip = kb_value<STAT, FORM>(r2, cst);
   // sum_k k_b(x_k, x_i) w_b[k], generated tile by tile
   double acc = 0.0;
   const double* wb = w + (size_t)b * npad;
@@ -141,9 +139,7 @@ __global__ void __launch_bounds__(256) fant_col_kernel(const double* __restrict_
           const double df = xi[t] - xt[r * FT_DMAX + t];
           q = fma(df, df, q);
         }
-      const double s = kb_stationary<STAT>(q);
-      const double kv = (FORM == BGP_FORM_PRODUCT) ? cst * s : cst + s;
-      acc = fma(kv, wt[r], acc);
+      acc = fma(kb_value<STAT, FORM>(q, cst), wt[r], acc);
     }
   }
   if (i >= m) return;

@@ -24,8 +24,7 @@ static __device__ __forceinline__ void kb_epilogue(double (&acc)[R][8], int na, 
       double* orow = out + (size_t)(i0 + ty + (128 / R) * r) * ldo + j0 + tx;
 #pragma unroll
       for (int c = 0; c < 8; c++) {
-        const double s = kb_stationary<STAT>(acc[r][c]);
-        const double v = (FORM == BGP_FORM_PRODUCT) ? cst * s : cst + s;
+        const double v = kb_value<STAT, FORM>(acc[r][c], cst);
         orow[16 * c] = v;
         if (!GRAM) acc[r][c] = v;  // (cross builds: the caller may go on with the values, see kbuild_cross_kernel)
       }
@@ -42,11 +41,7 @@ static __device__ __forceinline__ void kb_epilogue(double (&acc)[R][8], int na, 
 #pragma unroll
       for (int c = 0; c < 8; c++) {
         const int gj = j0 + tx + 16 * c;
-        double v = 0.0;
-        if (gi < out_rows && gj < out_cols) {
-          const double sv = kb_stationary<STAT>(acc[r][c]);
-          v = (FORM == BGP_FORM_PRODUCT) ? cst * sv : cst + sv;
-        }
+        const double v = (gi < out_rows && gj < out_cols) ? kb_value<STAT, FORM>(acc[r][c], cst) : 0.0;
         out[(size_t)gi * ldo + gj] = v;
         acc[r][c] = v;
       }
@@ -57,35 +52,50 @@ static __device__ __forceinline__ void kb_epilogue(double (&acc)[R][8], int na, 
     for (int c = 0; c < 8; c++) {
       const int gj = j0 + tx + 16 * c;
       if (gj >= out_cols) continue;
-      double v;
-      if (GRAM && (gi >= na || gj >= nb)) {
-        v = (gi == gj) ? 1.0 : 0.0;  // identity padding: log det and z unaffected
-      } else if (GRAM && gi == gj) {
-        // fill_diagonal(1) (kernels.py:1738) -> c*1 (+1) -> + s2 (White) -> += alpha (_gpr.py:585)
-        const double base = (FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0;
-        v = (base + s2);
-        if (alpha) v += alpha[gi];
-      } else {
-        const double s = kb_stationary<STAT>(acc[r][c]);
-        v = (FORM == BGP_FORM_PRODUCT) ? cst * s : cst + s;
-      }
-      out[(size_t)gi * ldo + gj] = v;
+      out[(size_t)gi * ldo + gj] = kb_gram_entry<STAT, FORM>(acc[r][c], gi, gj, na, cst, s2, alpha);  // (GRAM: na == nb)
     }
   }
 }
 
-// One 128 x 128 Gram tile by a 512-thread workgroup (thread (tx, ty) of a 16 x 32 grid owns rows ty + 32 r, r < 4, columns
-// tx + 16 c, c < 8), operands staged in caller-provided LDS (xi, xj: KB_DK x BGP_TILE_LD doubles each, ell: KB_DK).  Per element
-// the arithmetic of kbuild_tile (x / l staged, (a - b)^2 accumulated with fma in ascending dimension, kb_epilogue): same bits.
-template <int STAT, int FORM>
-static __device__ __forceinline__ void kb_gram_tile512(const double* __restrict__ X, int n, int d, const double* __restrict__ h,
-                                                       const double* __restrict__ alpha, int i0, int j0, double* __restrict__ out,
-                                                       size_t ldo, int npad, double* xi, double* xj, double* ell) {
+// One input dimension of a tile: acc[r][c] = fma(df, df, acc[r][c]), df = xi[ty + (128 / R) r] - xj[tx + 16 c], with xi / xj
+// that dimension's row of the staged operands; callers walk the dimensions in ascending order.  The 8 differences of a row
+// are batched ahead of their squares (a subtract never feeds the very next instruction: see kbuild2_kernel).
+// (Keep the loop over the dimensions in the caller: the register counts of kbuild_gram_kernel and ps_kernel depend on it.)
+template <int R>
+static __device__ __forceinline__ void kb_accum(const double* xi, const double* xj, int tx, int ty, double (&acc)[R][8]) {
+  double a[R], b[8];
+#pragma unroll
+  for (int r = 0; r < R; r++) a[r] = xi[ty + (128 / R) * r];
+#pragma unroll
+  for (int c = 0; c < 8; c++) b[c] = xj[tx + 16 * c];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    double df[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) df[c] = a[r] - b[c];
+    __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+#pragma unroll
+    for (int c = 0; c < 8; c++) acc[r][c] = fma(df[c], df[c], acc[r][c]);
+    __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+  }
+}
+
+// One 128 x 128 tile out[(i0+..)][(j0+..)] = k(A_i, B_j) by a workgroup of THREADS threads: thread (tx, ty) of a
+// 16 x THREADS/16 grid owns rows ty + (128 / R) r, r < R = 2048 / THREADS, and columns tx + 16 c, c < 8.  A is (na x d), Bm is
+// (nb x d), row-major; the operands are staged, pre-divided by the length scales, in caller-provided LDS (xi, xj:
+// KB_DK rows of BGP_TILE_LD doubles each, ell: KB_DK).  GRAM != 0: A == Bm is the training set (kb_gram_entry).  The values stay in
+// acc (cross builds go on with them).
+template <int THREADS, int GRAM, int STAT, int FORM>
+static __device__ __forceinline__ void kb_tile(const double* __restrict__ A, int na, const double* __restrict__ Bm, int nb,
+                                               int d, const double* __restrict__ h, const double* __restrict__ alpha, int i0,
+                                               int j0, double* __restrict__ out, size_t ldo, int out_rows, int out_cols,
+                                               double (*xi)[BGP_TILE_LD], double (*xj)[BGP_TILE_LD], double* ell,
+                                               double (&acc)[2048 / THREADS][8]) {
+  constexpr int R = 2048 / THREADS;
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
-  double acc[4][8];
 #pragma unroll
-  for (int r = 0; r < 4; r++)
+  for (int r = 0; r < R; r++)
 #pragma unroll
     for (int c = 0; c < 8; c++) acc[r][c] = 0.0;
   for (int k0 = 0; k0 < d; k0 += KB_DK) {
@@ -93,31 +103,15 @@ static __device__ __forceinline__ void kb_gram_tile512(const double* __restrict_
     __syncthreads();
     if (tid < kc) ell[tid] = exp(h[1 + k0 + tid]);
     __syncthreads();
-    for (int idx = tid; idx < kc * 128; idx += 512) {
+    for (int idx = tid; idx < kc * 128; idx += THREADS) {
       const int row = idx / kc, k = idx - row * kc;
       const int gi = i0 + row, gj = j0 + row;
       const double l = ell[k];
-      xi[k * BGP_TILE_LD + row] = (gi < n) ? X[(size_t)gi * d + k0 + k] / l : 0.0;
-      xj[k * BGP_TILE_LD + row] = (gj < n) ? X[(size_t)gj * d + k0 + k] / l : 0.0;
+      xi[k][row] = (gi < na) ? A[(size_t)gi * d + k0 + k] / l : 0.0;
+      xj[k][row] = (gj < nb) ? Bm[(size_t)gj * d + k0 + k] / l : 0.0;
     }
     __syncthreads();
-    for (int k = 0; k < kc; k++) {
-      double a[4], b[8];
-#pragma unroll
-      for (int r = 0; r < 4; r++) a[r] = xi[k * BGP_TILE_LD + ty + 32 * r];
-#pragma unroll
-      for (int c = 0; c < 8; c++) b[c] = xj[k * BGP_TILE_LD + tx + 16 * c];
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        double df[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) df[c] = a[r] - b[c];
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-#pragma unroll
-        for (int c = 0; c < 8; c++) acc[r][c] = fma(df[c], df[c], acc[r][c]);
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-      }
-    }
+    for (int k = 0; k < kc; k++) kb_accum<R>(xi[k], xj[k], tx, ty, acc);
   }
-  kb_epilogue<1, STAT, FORM, 4>(acc, n, n, d, h, alpha, i0, j0, out, ldo, npad, npad, tx, ty);
+  kb_epilogue<GRAM, STAT, FORM, R>(acc, na, nb, d, h, alpha, i0, j0, out, ldo, out_rows, out_cols, tx, ty);
 }

@@ -1,8 +1,7 @@
 // Kernel-matrix build: tiled pairwise-distance kernel staging X tiles in LDS.
 //
-// Replaces kernel_(X_train_) + diagonal add -- sklearn/kernels.py:1708-1738 (Matern.__call__),
-// :1553-1560 (RBF), :966 (Product), :866 (Sum), :1273 (Constant), :1402 (White),
-// sklearn/_gpr.py:585 / bask/bayesgpr.py:204 (K[diag] += alpha).
+// Replaces kernel_(X_train_) + diagonal add; the entry rule and the reference lines it follows: kb_value / kb_gram_entry
+// (bgp_device.h).
 //
 // One 256-thread workgroup produces one 128x128 tile; thread (tx,ty) of the 16x16 thread grid owns
 // the 8x8 strided micro-tile rows ty+16r, cols tx+16c, so that for a fixed (r,c) the 16 lanes of a
@@ -14,59 +13,7 @@
 #include "bgp_ring.h"
 #include "bgp_kb.h"
 
-// Generic tile body: out[(i0+..)][(j0+..)] = k(A_i, B_j); A is (na x d), Bm is (nb x d), row-major.
-// GRAM != 0: A == Bm is the training set, diagonal gets c(+1) + s2 + alpha_i, padding gets identity.
-// Tiles that are fully inside the data and off the diagonal take a check-free epilogue.
-template <int GRAM, int STAT, int FORM>
-static __device__ __forceinline__ void kbuild_tile(const double* __restrict__ A, int na,
-                                                   const double* __restrict__ Bm, int nb, int d,
-                                                   const double* __restrict__ h, const double* __restrict__ alpha,
-                                                   int i0, int j0, double* __restrict__ out, size_t ldo, int out_rows,
-                                                   int out_cols, double (&acc)[8][8]) {
-  __shared__ double xi[KB_DK][BGP_TILE_LD];
-  __shared__ double xj[KB_DK][BGP_TILE_LD];
-  __shared__ double ell[KB_DK];
-  const int tid = threadIdx.x;
-  const int tx = tid & 15, ty = tid >> 4;
-#pragma unroll
-  for (int r = 0; r < 8; r++)
-#pragma unroll
-    for (int c = 0; c < 8; c++) acc[r][c] = 0.0;
-
-  for (int k0 = 0; k0 < d; k0 += KB_DK) {
-    const int kc = min(KB_DK, d - k0);
-    __syncthreads();
-    if (tid < kc) ell[tid] = exp(h[1 + k0 + tid]);
-    __syncthreads();
-    for (int idx = tid; idx < kc * 128; idx += 256) {
-      int row = idx / kc, k = idx - row * kc;
-      int gi = i0 + row, gj = j0 + row;
-      double l = ell[k];
-      xi[k][row] = (gi < na) ? A[(size_t)gi * d + k0 + k] / l : 0.0;
-      xj[k][row] = (gj < nb) ? Bm[(size_t)gj * d + k0 + k] / l : 0.0;
-    }
-    __syncthreads();
-    for (int k = 0; k < kc; k++) {
-      double a[8], b[8];
-#pragma unroll
-      for (int r = 0; r < 8; r++) a[r] = xi[k][ty + 16 * r];
-#pragma unroll
-      for (int c = 0; c < 8; c++) b[c] = xj[k][tx + 16 * c];
-#pragma unroll
-      for (int r = 0; r < 8; r++) {  // (subtracts batched ahead of their squares: see kbuild2_kernel)
-        double df[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) df[c] = a[r] - b[c];
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-#pragma unroll
-        for (int c = 0; c < 8; c++) acc[r][c] = fma(df[c], df[c], acc[r][c]);
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-      }
-    }
-  }
-  kb_epilogue<GRAM, STAT, FORM>(acc, na, nb, d, h, alpha, i0, j0, out, ldo, out_rows, out_cols, tx, ty);
-}
-
+// Tile body: kb_tile (bgp_kb.h).  GRAM tiles that are fully inside the data and off the diagonal take a check-free epilogue.
 template <int STAT, int FORM>
 __global__ void __launch_bounds__(256) kbuild_gram_kernel(const double* __restrict__ X,
                                                            const double* __restrict__ alpha,
@@ -91,9 +38,10 @@ __global__ void __launch_bounds__(256) kbuild_gram_kernel(const double* __restri
   // working right-hand side of walker b (becomes z = L^-1 y during the factorisation)
   if (ti == tj && threadIdx.x < 128) yw[(size_t)b * ld + ti * 128 + threadIdx.x] = y[ti * 128 + threadIdx.x];
   const double* Xb = X + (size_t)b * xstride;  // per-walker warped inputs (xstride == 0: shared)
+  __shared__ double xi[KB_DK][BGP_TILE_LD], xj[KB_DK][BGP_TILE_LD], ell[KB_DK];
   double acc[8][8];
-  kbuild_tile<1, STAT, FORM>(Xb, n, Xb, n, d, h, use_alpha ? alpha : nullptr, ti * 128, tj * 128, out, (size_t)ld, npad,
-                             npad, acc);
+  kb_tile<256, 1, STAT, FORM>(Xb, n, Xb, n, d, h, use_alpha ? alpha : nullptr, ti * 128, tj * 128, out, (size_t)ld, npad,
+                              npad, xi, xj, ell, acc);
 }
 
 // blockIdx.y = item of a batch: hyper-parameters h + b (d+2), output out + b ostride (the inputs are shared).
@@ -109,9 +57,10 @@ __global__ void __launch_bounds__(256) kbuild_cross_kernel(const double* __restr
                                                             const double* __restrict__ vec, size_t svec,
                                                             double* __restrict__ dpart, int mpad) {
   const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j, b = blockIdx.y;
+  __shared__ double xi[KB_DK][BGP_TILE_LD], xj[KB_DK][BGP_TILE_LD], ell[KB_DK];
   double acc[8][8];
-  kbuild_tile<0, STAT, FORM>(Xq, m, Xt, n, d, h + (size_t)b * (d + 2), nullptr, ti * 128, tj * 128,
-                             out + (size_t)b * ostride, (size_t)ldo, m, n, acc);
+  kb_tile<256, 0, STAT, FORM>(Xq, m, Xt, n, d, h + (size_t)b * (d + 2), nullptr, ti * 128, tj * 128,
+                              out + (size_t)b * ostride, (size_t)ldo, m, n, xi, xj, ell, acc);
   if (vec) {
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const double* vb = vec + (size_t)b * svec;
@@ -145,7 +94,7 @@ __global__ void __launch_bounds__(256) kbuild_cross_kernel(const double* __restr
 //   * kbuild2_kernel gives every workgroup KB2_TPW consecutive tiles of one matrix and streams their (tile, 16
 //     dimensions) operand chunks through a two-stage LDS ring with `global_load_lds_dwordx4`: the chunk after the
 //     one being accumulated is always in flight.
-// Same accumulation order (dimension ascending) and the same epilogue as kbuild_tile: identical K.
+// Same accumulation order (dimension ascending) and the same epilogue as kb_tile: identical K.
 // ------------------------------------------------------------------------------------------
 #define KB2_TPW 4
 #define KB2_WAVES 4    // 256 threads, 8 x 8 pairs per thread.  (512 threads x 4 x 8 pairs -- twice the waves per SIMD --
@@ -343,7 +292,7 @@ int bgp_lml_gen_args(const bgp_ctx* ctx, int off, S4Gen* out) {
 }
 
 int bgp_launch_kcross(bgp_ctx* ctx, const double* dh_b, int m, const double* dXq, int nx, const double* dXt,
-                      double* dout, int ldo, int /*unused*/) {
+                      double* dout, int ldo) {
   return bgp_launch_kcross_batch(ctx, 1, dh_b, m, dXq, nx, dXt, dout, ldo, 0);
 }
 

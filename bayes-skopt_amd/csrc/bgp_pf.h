@@ -183,10 +183,9 @@ static __device__ __forceinline__ void pf_wfinish(d4 acc, double* __restrict__ s
 
 #define PF_THREADS 512
 // GEN (fused small-n LML, n <= 128: SURVEY.md section 7 step 5): the workgroup GENERATES the jittered Gram matrix of
-// its walker straight into the LDS tile (same arithmetic, in the same order, as kbuild_tile: scaled inputs, squared
-// differences in dimension order, stationary kernel, exact diagonal, identity padding) instead of loading a tile
-// another launch wrote, takes y from the context and stores nothing but lml / status: ONE launch per LML batch, no
-// Gram matrix in HBM.  `gen` carries the extra inputs.
+// its walker straight into the LDS tile (one staged operand, squared differences in dimension order as in kb_accum,
+// kb_gram_entry: the Gram kernel's entries) instead of loading a tile another launch wrote, takes y from the context and
+// stores nothing but lml / status: ONE launch per LML batch, no Gram matrix in HBM.  `gen` carries the extra inputs.
 struct PfGen {
   const double* X;      // n x d training inputs (original or warped)
   const double* alpha;  // n diagonal terms
@@ -214,6 +213,8 @@ static __device__ __forceinline__ void pf_generate_tile(double* __restrict__ s, 
       xs[kk * 128 + row] = (row < n) ? g.X[(size_t)row * d + k0 + kk] / exp(h[1 + k0 + kk]) : 0.0;
     }
     __syncthreads();
+    // (kb_accum's arithmetic without its scheduling barriers: the instruction schedule of the fused launch is
+    // configuration A's, and stays as measured)
     for (int kk = 0; kk < kc; kk++) {
       double a[4], bb[8];
 #pragma unroll
@@ -229,29 +230,17 @@ static __device__ __forceinline__ void pf_generate_tile(double* __restrict__ s, 
         }
     }
   }
-  {
-#pragma clang fp contract(off)
   const double cst = exp(h[0]), s2 = exp(h[d + 1]);
+  __builtin_assume(g.alpha != nullptr);  // (the context's alpha: always there, so kb_gram_entry's test for it folds away)
 #pragma unroll
   for (int r = 0; r < 4; r++) {
     const int gi = ty + 32 * r;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
       const int gj = tx + 16 * c;
-      double v;
-      if (gi >= n || gj >= n) {
-        v = (gi == gj) ? 1.0 : 0.0;
-      } else if (gi == gj) {
-        const double base = (FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0;
-        v = (base + s2) + g.alpha[gi];
-      } else {
-        const double sv = kb_stationary<STAT>(acc[r][c]);
-        v = (FORM == BGP_FORM_PRODUCT) ? cst * sv : cst + sv;
-      }
-      s[gi * PF_LD + gj] = v;
+      s[gi * PF_LD + gj] = kb_gram_entry<STAT, FORM>(acc[r][c], gi, gj, n, cst, s2, g.alpha);
     }
   }
-}
 }
 
 // The workgroup's LDS: ONE set of function-scope arrays that pf_block and the chain kernel's own steps (pf_chain_next)

@@ -698,7 +698,7 @@ __global__ void __launch_bounds__(256) lml_grad_kernel(const double* __restrict_
           g_noise += Wij * s2;
         } else {
           const double r2 = F[r][c];
-          double S, fr;
+          double S, fr;  // (not kb_stationary_fac: runtime stat, libm exp / sqrt, default contraction -- moving would change gradient bits)
           if (stat == BGP_RBF) {
             S = exp(-0.5 * r2);
             fr = S;
@@ -883,11 +883,11 @@ extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double*
     if (rc) return rc;
   }
   BGP_HIP(hipMemsetAsync(dKc, 0, (size_t)(dend - dKc) * sizeof(double), c->stream));  // (zero padding of every matrix and vector)
-  rc = bgp_launch_kcross(c, dhk, m, dXc, n, c->dXeff, dKc, npad, 0);
+  rc = bgp_launch_kcross(c, dhk, m, dXc, n, c->dXeff, dKc, npad);
   if (rc) return rc;
-  rc = bgp_launch_kcross(c, dhk, T, dXt, n, c->dXeff, dKT, npad, 0);
+  rc = bgp_launch_kcross(c, dhk, T, dXt, n, c->dXeff, dKT, npad);
   if (rc) return rc;
-  rc = bgp_launch_kcross(c, dhk, m, dXc, T, dXt, dKti, Tpad, 0);
+  rc = bgp_launch_kcross(c, dhk, m, dXc, T, dXt, dKti, Tpad);
   if (rc) return rc;
   // P_T = K_T Kinv ; s_t = rowsum(P_T o K_T) ; u_i = rowsum((K_c Kinv) o K_c) ; G = K_c P_T^T
   bgp_launch_gemm4(c->stream, 0, dKT, Kinv, npad, Tpad, npad, npad, dPT, npad, 1, 0, 0, 0, nullptr);
@@ -1036,7 +1036,7 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
     SY(hipMemsetAsync(dZ, 0, (size_t)rpad * mpad * sizeof(double), c->stream));
     SY(bgp_memcpy2d_async(dZ, (size_t)mpad * sizeof(double), z, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
                         n_draws, hipMemcpyHostToDevice, c->stream));
-    if ((rc = bgp_launch_kcross(c, dhk, m, dXq, n, c->dXeff, dKs, npad, 0))) break;
+    if ((rc = bgp_launch_kcross(c, dhk, m, dXq, n, c->dXeff, dKs, npad))) break;
     hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, 1), dim3(256), 0, c->stream, dKs, npad, (size_t)0, al,
                        (size_t)0, (const int*)nullptr, n, m, dmean, (size_t)0);
     // P = K_* K^-1, then cov = K_** - P K_*^T in the child's matrix, lower tiles only (all the factorisation reads):
@@ -1044,7 +1044,7 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
     bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, 1, 0, 0, 0, nullptr);
     int st = 0;
     for (int attempt = 0; attempt < 2 && !rc; attempt++) {
-      if ((rc = bgp_launch_kcross(c, dhk, m, dXq, m, dXq, w->dK, mpad, 0))) break;
+      if ((rc = bgp_launch_kcross(c, dhk, m, dXq, m, dXq, w->dK, mpad))) break;
       hipLaunchKernelGGL(add_diag_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, w->dK, mpad, m,
                          std::exp(h_kernel[d + 1]));
       bgp_launch_gemm4(c->stream, 1, dP, dKs, npad, mpad, mpad, npad, w->dK, mpad, 1, 0, 0, 0, nullptr);

@@ -42,34 +42,6 @@ static __device__ __forceinline__ double pg_wave_sum(double s) {
   return s;
 }
 
-// S(r) and fac(r) = (dS/dr) / r from the squared scaled distance (kb_stationary's expressions for S)
-template <int STAT>
-static __device__ __forceinline__ void pg_stat(double r2, double& S, double& fac) {
-#pragma clang fp contract(off)
-  if (STAT == BGP_RBF) {
-    S = kb_exp_neg(0.5 * r2);
-    fac = -S;
-    return;
-  }
-  const double r = kb_sqrt_pos(r2);
-  if (STAT == BGP_MATERN12) {
-    S = kb_exp_neg(r);
-    fac = (r > 0.0) ? -S / r : 0.0;  // (the r = 0 rule of grad_x)
-    return;
-  }
-  if (STAT == BGP_MATERN32) {
-    const double t = r * 1.7320508075688772;
-    const double e = kb_exp_neg(t);
-    S = (1.0 + t) * e;
-    fac = -3.0 * e;
-    return;
-  }
-  const double t = r * 2.23606797749979;
-  const double e = kb_exp_neg(t);
-  S = (1.0 + t + t * t * 0.3333333333333333) * e;
-  fac = -(5.0 / 3.0) * ((1.0 + t) * e);
-}
-
 // dst[t] = scale il_t sum_i w_i (x_t - X_it) il_t with w_i = a_i gb_i (a == nullptr: gb_i): the contraction of dmean and dvar.  Lane
 // (t, half) of wave wv owns dimension t over the points 2 wv + half, + 2 PG_NW, ...; the two halves, then the waves in ascending
 // order.  Ends with a barrier.
@@ -115,8 +87,8 @@ static __device__ __noinline__ void pg_eval(const double* __restrict__ X, int n,
       r2 = fma(df, df, r2);
     }
     double S, fac;
-    pg_stat<STAT>(r2, S, fac);
-    const double k = (FORM == BGP_FORM_PRODUCT) ? cst * S : cst + S;
+    kb_stationary_fac<STAT>(r2, S, fac);
+    const double k = kb_with_constant<FORM>(cst, S);
     kb[i] = k;
     gb[i] = (FORM == BGP_FORM_PRODUCT) ? cst * fac : fac;
     am = fma(k, alpha[i], am);
@@ -191,7 +163,7 @@ __global__ void __launch_bounds__(PG_NT) pg_rows_kernel(const double* __restrict
     W.il[tid] = 1.0 / exp(h[1 + tid]);
   }
   const double cst = exp(h[0]);
-  const double kdiag = ((FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0) + exp(h[d + 1]);
+  const double kdiag = kb_with_constant<FORM>(cst, 1.0) + exp(h[d + 1]);
   double *kb, *gb;
   pg_rows(pg_dyn, scratch, n, npad, b * gridDim.x + i, kb, gb);
   pg_eval<STAT, FORM>(X, n, d, alphaB + (size_t)b * npad, KinvB + (size_t)b * npad * npad, npad, cst, kdiag, true, kb, gb, W);
@@ -254,7 +226,7 @@ __global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict_
   }
   for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
   const double cst = exp(h[0]);
-  const double kdiag = ((FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0) + exp(h[d + 1]);
+  const double kdiag = kb_with_constant<FORM>(cst, 1.0) + exp(h[d + 1]);
   double *kb, *gb;
   pg_rows(pg_dyn, scratch, n, npad, s, kb, gb);
   pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W);

@@ -371,16 +371,17 @@ static __device__ __forceinline__ int ps_ll_update_quad(const PsArgs& a, const d
 }
 
 // PsArgs::gen: one Gram block (I, J) of matrix b, generated where the Gram kernel in front of the launch would have written it
-// (same arithmetic per element: kb_gram_tile512); block (I, 0) also copies row block I of y into the working right-hand side.
+// (kb_tile, bgp_kb.h); block (I, 0) also copies row block I of y into the working right-hand side.
 static __device__ __forceinline__ void ps_gen_task(const PsArgs& a, int b, int I, int J) {
   const int tid = threadIdx.x;
   double* const lds = reinterpret_cast<double*>(pf_lds_raw());
-  double* const xi = lds;
-  double* const xj = xi + KB_DK * BGP_TILE_LD;
-  double* const ell = xj + KB_DK * BGP_TILE_LD;
+  double(*const xi)[BGP_TILE_LD] = reinterpret_cast<double(*)[BGP_TILE_LD]>(lds);
+  double(*const xj)[BGP_TILE_LD] = xi + KB_DK;
+  double* const ell = lds + 2 * KB_DK * BGP_TILE_LD;
   if (J == 0 && tid < 128) a.yw[(size_t)b * a.ystride + I * 128 + tid] = a.y[I * 128 + tid];
-  kb_gram_tile512<BGP_MATERN52, BGP_FORM_PRODUCT>(a.X, a.n, a.d, a.H + (size_t)b * (a.d + 2), a.alpha, I * 128, J * 128,
-                                                 a.K + (size_t)b * a.mstride, (size_t)a.ld, a.ld, xi, xj, ell);
+  double acc[4][8];
+  kb_tile<512, 1, BGP_MATERN52, BGP_FORM_PRODUCT>(a.X, a.n, a.X, a.n, a.d, a.H + (size_t)b * (a.d + 2), a.alpha, I * 128, J * 128,
+                                                  a.K + (size_t)b * a.mstride, (size_t)a.ld, a.ld, a.ld, xi, xj, ell, acc);
   ps_publish_barrier();
   if (tid == 0) ps_signal_add(a.flags + PS_GEN(a.B, a.nblk) + ((size_t)b * a.nblk + I) * a.nblk + J);
   __syncthreads();

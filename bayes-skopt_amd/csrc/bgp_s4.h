@@ -113,8 +113,8 @@ struct S4Tile {
 
 // ---- Gram generation at first touch (the trailing update of the FIRST panel group, bgp_chol.hip) ----
 // The update that touches a block of the kernel matrix first does not load it: every lane computes the Gram values of its own
-// accumulator entries -- from the k-major pre-scaled inputs xscale_kernel wrote for kbuild2_kernel, with kbuild2's arithmetic per
-// element (differences and fma in ascending dimension, kb_stationary, constant, exact diagonal, identity padding: same bits) --
+// accumulator entries -- from the k-major pre-scaled inputs xscale_kernel wrote for kbuild2_kernel, differences and fma in
+// ascending dimension as there, then kb_value / kb_gram_entry (bgp_device.h) --
 // while the first operand chunk is in flight; the Gram kernel in front of the factorisation then builds block column 0 only.
 // Why: the build is fp64-VALU bound (VALUBusy 84 %) and the update MFMA bound, and the two pipes of a SIMD work side by side for
 // different waves; and the block is neither written by one kernel nor read back by the next (2 x 2.3 GB per half-step at
@@ -204,8 +204,7 @@ struct S4GenF {
           if (j + CREL > i) continue;
 #pragma unroll
           for (int r = 0; r < 4; r++) {
-            const double sv = kb_stationary<STAT>(acc[i][j][r]);
-            acc[i][j][r] = (FORM == BGP_FORM_PRODUCT) ? cst * sv : cst + sv;
+            acc[i][j][r] = kb_value<STAT, FORM>(acc[i][j][r], cst);
           }
         }
       return;
@@ -220,19 +219,7 @@ struct S4GenF {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int gi = cur.gi0 + GK_ROWB(r0, i, lane, r);
-          double v;
-          if (gi >= g.n || gj >= g.n) {
-            v = (gi == gj) ? 1.0 : 0.0;  // identity padding: log det and z unaffected
-          } else if (gi == gj) {
-            // fill_diagonal(1) (kernels.py:1738) -> c*1 (+1) -> + s2 (White) -> += alpha (_gpr.py:585)
-            const double base = (FORM == BGP_FORM_PRODUCT) ? cst * 1.0 : cst + 1.0;
-            v = (base + s2);
-            if (g.alpha) v += g.alpha[gi];
-          } else {
-            const double sv = kb_stationary<STAT>(acc[i][j][r]);
-            v = (FORM == BGP_FORM_PRODUCT) ? cst * sv : cst + sv;
-          }
-          acc[i][j][r] = v;
+          acc[i][j][r] = kb_gram_entry<STAT, FORM>(acc[i][j][r], gi, gj, g.n, cst, s2, g.alpha);
         }
       }
   }

@@ -424,3 +424,30 @@ def test_gram_blocks_generated_inside_the_trailing_update_are_the_gram_kernels(l
     if not warp and n <= 1300:
         rows = [0, 2, 3, 4, 5]  # (row 1 has no noise: conditioned by the 1e-10 jitter alone, it is no fixed point for a tolerance)
         np.testing.assert_allclose(got[rows], O.lml_batch(X, y, np.full(n, 1e-10), H[rows], stationary, form), rtol=RTOL)
+
+
+@pytest.mark.parametrize("form", ["product", "sum"])
+@pytest.mark.parametrize("stationary", ["rbf", "matern12", "matern32", "matern52"])
+@pytest.mark.parametrize("n,d", [
+    (1, 1), (2, 1),  # almost nothing but padding and diagonal
+    (97, 3),         # ragged: 31 rows and columns of identity padding
+    (128, 2),        # no padding
+    (97, 17),        # two staging passes (16 + 1 dimensions)
+])
+def test_fused_small_n_generator_is_the_gram_kernels(lib, n, d, stationary, form):
+    """For n <= 128 ``lml`` is ONE launch that generates the kernel matrix in the LDS tile (pf_generate_tile, csrc/bgp_pf.h);
+    ``lml_gram`` of the Gram kernel's matrices factorises what ``kernel_matrix`` wrote, on the launch schedule.  Both take
+    their entries from kb_gram_entry over squared distances accumulated in the same order: the same bits."""
+    X, y = synth(max(n, 4), d, 300 + n + d)
+    X, y = X[:n], y[:n]
+    rs = np.random.RandomState(17 * n + d)
+    H = np.concatenate([[0.2], np.full(d, np.log(0.5)), [np.log(0.03)]]) + 0.2 * rs.randn(3, d + 2)
+    H[1, -1] = -np.inf  # (noise level 0: the White term drops out of the diagonal)
+    alpha = 1e-6 * (1.0 + rs.uniform(size=n))
+    ctx = lib.Context(X, y, alpha, form=form, stationary=stationary, max_batch=3)
+    got = ctx.lml(H)
+    K = np.stack([ctx.kernel_matrix(h) for h in H])
+    ref = ctx.lml_gram(K, use_alpha=False)
+    ctx.close()
+    assert np.all(np.isfinite(got)), got
+    assert np.array_equal(got, ref), (got, ref)
