@@ -346,13 +346,18 @@ class Context:
         self.mcmc_steps(plan)
         return self.mcmc_end()
 
-    def lml_warped_submit(self, H, W):
-        """Asynchronous ``lml_warped``: False when the batch cannot go asynchronously (see ``lml_submit``)."""
+    def _HW(self, H, W):
+        """The (B, p) hyper-parameters and their (B, 2d) per-walker warp parameters of a warped LML batch."""
         H = self._H(H)
         W = _c(np.atleast_2d(W))
         B = H.shape[0]
         if W.shape != (B, 2 * self.d):
             raise ValueError(f"warp parameters must be (B, 2d) = ({B}, {2 * self.d}), got {W.shape}")
+        return H, W, B
+
+    def lml_warped_submit(self, H, W):
+        """Asynchronous ``lml_warped``: False when the batch cannot go asynchronously (see ``lml_submit``)."""
+        H, W, B = self._HW(H, W)
         if B > self.max_batch or B == 0 or self._timing:
             return False
         _check(self._lib.bgp_lml_batch_warped_submit(self._h, B, _p(H), _p(W)), "bgp_lml_batch_warped_submit")
@@ -369,11 +374,7 @@ class Context:
 
     def lml_warped(self, H, W, return_status=False):
         """Per-walker warp: W is (B, 2d) log-space Beta parameters [wa_1..wa_d, wb_1..wb_d]."""
-        H = self._H(H)
-        W = _c(np.atleast_2d(W))
-        B = H.shape[0]
-        if W.shape != (B, 2 * self.d):
-            raise ValueError(f"warp parameters must be (B, 2d) = ({B}, {2 * self.d}), got {W.shape}")
+        H, W, B = self._HW(H, W)
         out = np.empty(B)
         st = np.zeros(B, dtype=np.int32)
         _check(self._lib.bgp_lml_batch_warped(self._h, B, _p(H), _p(W), _p(out), _p(st)), "bgp_lml_batch_warped")
@@ -411,22 +412,26 @@ class Context:
         _check(self._lib.bgp_kernel_matrix(self._h, _p(H), _p(K)), "bgp_kernel_matrix")
         return K
 
-    def posterior(self, H, want_L=False, want_alpha=True, want_K_inv=False):
-        H = self._H(H)
-        B, n = H.shape[0], self.n
+    def _posterior(self, name, B, head, want_L, want_alpha, want_K_inv):
+        """Outputs and the call of a posterior build ``name(ctx, B, *head, L, alpha, K_inv, lml, status)``, NULL for what is not wanted."""
+        n = self.n
         L = np.empty((B, n, n)) if want_L else None
         a = np.empty((B, n)) if want_alpha else None
         Ki = np.empty((B, n, n)) if want_K_inv else None
         lml = np.empty(B)
         st = np.zeros(B, dtype=np.int32)
         nul = C.cast(None, _dp)
-        self.resident_H = None
-        _check(self._lib.bgp_posterior_batch(self._h, B, _p(H), _p(L) if want_L else nul,
-                                             _p(a) if want_alpha else nul, _p(Ki) if want_K_inv else nul, _p(lml),
-                                             _p(st)), "bgp_posterior_batch")
-        if np.all(st == 0):
-            self.resident_H = H.copy()
+        self.resident_H = None  # (set by posterior() alone: posteriors of host matrices belong to no canonical vector)
+        _check(getattr(self._lib, name)(self._h, B, *head, _p(L) if want_L else nul, _p(a) if want_alpha else nul,
+                                        _p(Ki) if want_K_inv else nul, _p(lml), _p(st)), name)
         return {"L": L, "alpha": a, "K_inv": Ki, "lml": lml, "status": st}
+
+    def posterior(self, H, want_L=False, want_alpha=True, want_K_inv=False):
+        H = self._H(H)
+        res = self._posterior("bgp_posterior_batch", H.shape[0], (_p(H),), want_L, want_alpha, want_K_inv)
+        if np.all(res["status"] == 0):
+            self.resident_H = H.copy()
+        return res
 
     # ---- generic kernel expression trees: host-evaluated kernel matrices in, device arithmetic behind them
     def _Kstack(self, K):
@@ -448,18 +453,7 @@ class Context:
 
     def posterior_gram(self, K, use_alpha=True, want_L=False, want_alpha=True, want_K_inv=False):
         K = self._Kstack(K)
-        B, n = K.shape[0], self.n
-        L = np.empty((B, n, n)) if want_L else None
-        a = np.empty((B, n)) if want_alpha else None
-        Ki = np.empty((B, n, n)) if want_K_inv else None
-        lml = np.empty(B)
-        st = np.zeros(B, dtype=np.int32)
-        nul = C.cast(None, _dp)
-        self.resident_H = None  # (the resident posteriors belong to no canonical vector)
-        _check(self._lib.bgp_posterior_batch_gram(self._h, B, _p(K), int(bool(use_alpha)), _p(L) if want_L else nul,
-                                                  _p(a) if want_alpha else nul, _p(Ki) if want_K_inv else nul, _p(lml),
-                                                  _p(st)), "bgp_posterior_batch_gram")
-        return {"L": L, "alpha": a, "K_inv": Ki, "lml": lml, "status": st}
+        return self._posterior("bgp_posterior_batch_gram", K.shape[0], (_p(K), int(bool(use_alpha))), want_L, want_alpha, want_K_inv)
 
     def predict_gram(self, Ks, kss, Kss=None):
         """Predict for the B resident posteriors from host-evaluated ``Ks`` (B, m, n) = kernel_(Xq, X_train),

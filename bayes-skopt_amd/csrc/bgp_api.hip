@@ -429,10 +429,7 @@ extern "C" int bgp_persist_stats(bgp_ctx* c, long long* out) {
 static int ps_check(bgp_ctx* c) {
   if (!c->ps_inflight) return 0;
   c->ps_inflight = 0;
-  if (!c->ps_herr || *c->ps_herr == 0) return 0;
-  *c->ps_herr = 0;
-  bgp_ps_note_timeout(c, "the batch is redone");
-  return 1;
+  return bgp_ps_timed_out(c, c, "the batch is redone");
 }
 
 extern "C" int bgp_lml_batch_submit(bgp_ctx* c, int B, const double* h);

@@ -41,6 +41,13 @@ void bgp_xfer_forget(hipStream_t st);
     }                                                                                        \
   } while (0)
 
+// A stage that has failed has reported its error: pass its code on.
+#define BGP_TRY(call)           \
+  do {                          \
+    const int rc__ = (call);    \
+    if (rc__) return rc__;      \
+  } while (0)
+
 // ---- host <-> device transfers through pinned staging, and the active wait ----
 // Every copy between a CALLER's buffer (pageable: numpy arrays) and the device goes through the library's own pinned
 // arena.  An asynchronous copy straight from / to pageable memory makes the runtime lock and unlock the pages around it,
@@ -347,6 +354,15 @@ static inline void bgp_ps_note_timeout(bgp_ctx* c, const char* what) {
     fprintf(stderr, "libbgp: warning: the launch-free factorisation timed out (a wait outlasted BGP_PS_TIMEOUT_MS); %s on the "
                     "multi-launch path, which this context keeps %s (time-out %lld of this context; bgp_persist_stats)\n", what,
             c->ps_cooldown ? "for its next eligible calls (BGP_PS_COOLDOWN, 256)" : "from now on", c->ps_timeouts);
+}
+// Behind the synchronisation of a launch-free call: did a wait inside it time out?  `ran` is the context whose flag block and error
+// word the call used -- `c` itself, or the child that factorises a covariance for it; the word is cleared, the time-out is counted
+// on `c`, and the caller redoes the work by launches.
+static inline bool bgp_ps_timed_out(bgp_ctx* c, bgp_ctx* ran, const char* what) {
+  if (!ran->ps_herr || *ran->ps_herr == 0) return false;
+  *ran->ps_herr = 0;
+  bgp_ps_note_timeout(c, what);
+  return true;
 }
 // (call only when the batch is otherwise eligible: the cool-down counts eligible calls)
 static inline bool bgp_ps_allowed(bgp_ctx* c) {

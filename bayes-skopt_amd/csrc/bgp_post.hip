@@ -130,6 +130,46 @@ static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const
 
 static inline int pad128(int v) { return ((v + 127) / 128) * 128; }
 
+// ONE exit path for the entry points of this file (the stages below return from the middle, with BGP_HIP or a plain return): a
+// failed call waits for what it enqueued -- its kernels run over scratch that the next call may carve again --, clears the sticky HIP
+// error, and none of its downloads is unpacked into the caller's arrays later.  The success path is the body's own.
+template <class Body>
+static int post_call(bgp_ctx* c, Body&& body) {
+  const int rc = body();
+  if (rc != BGP_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    bgp_xfer_drop_pending();
+    bgp_xfer_release(c->stream);
+  }
+  return rc;
+}
+
+// `rows` rows of `w` doubles between a packed host array and device rows of stride `ld`
+static hipError_t rows_up(bgp_ctx* c, double* dev, const double* host, int w, int ld, int rows) {
+  return bgp_memcpy2d_async(dev, (size_t)ld * sizeof(double), host, (size_t)w * sizeof(double), (size_t)w * sizeof(double), rows,
+                            hipMemcpyHostToDevice, c->stream);
+}
+static hipError_t rows_down(bgp_ctx* c, double* host, const double* dev, int w, int ld, int rows) {
+  return bgp_memcpy2d_async(host, (size_t)w * sizeof(double), dev, (size_t)ld * sizeof(double), (size_t)w * sizeof(double), rows,
+                            hipMemcpyDeviceToHost, c->stream);
+}
+
+// Items per chunk of a batched call: what `budget` doubles of scratch hold at `per_item` each; round8: whole rounds of the
+// item -> XCD pinning (rowquad4_kernel) when the batch takes more than one chunk.
+static int post_chunk(int B, size_t per_item, size_t budget, bool round8) {
+  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
+  if (round8 && chunk >= 8 && chunk < B) chunk &= ~7;
+  return chunk;
+}
+
+// Query points to the device, through the context-level warp when one is set: BayesGPR.predict warps them with the current warpers
+// (bask/bayesgpr.py:630-632), PVRS compares candidates and Thompson points in the warped space (bask/acquisition.py:324-327).
+static int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows) {
+  BGP_HIP(bgp_memcpy_async(dst, src, (size_t)rows * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return c->has_warp ? bgp_launch_warp(c, c->stream, dst, c->dwarp, dst, rows, 1, 0) : BGP_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // posterior build
 // ------------------------------------------------------------------------------------------
@@ -204,6 +244,16 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
   return BGP_OK;
 }
 
+// ... as an entry point runs it: whatever was resident is gone before the build starts
+static int post_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv, double* lml,
+                      int* status, const double* Kgram = nullptr) {
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    c->post_B = 0;
+    return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram);
+  });
+}
+
 extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L, double* alpha, double* K_inv,
                                    double* lml, int* status) {
   BGP_REQUIRE_IDLE(c, "bgp_posterior_batch");
@@ -211,9 +261,7 @@ extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L
     bgp_set_error("bgp_posterior_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  c->post_B = 0;
-  return bgp_posterior_build(c, B, h, 1, L, alpha, K_inv, lml, status);
+  return post_build(c, B, h, 1, L, alpha, K_inv, lml, status);
 }
 
 // The same posterior build from HOST-evaluated kernel matrices (generic kernel expression trees, bgp_gram.hip): K is B
@@ -225,9 +273,7 @@ extern "C" int bgp_posterior_batch_gram(bgp_ctx* c, int B, const double* K, int 
     bgp_set_error("bgp_posterior_batch_gram: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  c->post_B = 0;
-  return bgp_posterior_build(c, B, nullptr, use_alpha, L, alpha, K_inv, lml, status, K);
+  return post_build(c, B, nullptr, use_alpha, L, alpha, K_inv, lml, status, K);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -258,8 +304,51 @@ struct AcqPlan {  // closed-form acquisitions evaluated on the device-resident m
   int n_samples = 1;
   double* out = nullptr;  // host, n_acq * m
 };
-static int acq_run(bgp_ctx* c, hipStream_t st, int B, int m, int mpad, const double* dmean, const double* dvar,
-                   const AcqPlan& ap, double* dT, int* dbad, double* dmumin, double* dacc);
+struct AcqScratch {  // device regions of acq_run
+  double *dT = nullptr, *dacc = nullptr, *dmumin = nullptr, *dparams = nullptr;
+  int *dbad = nullptr, *dkinds = nullptr;
+  void take(BgpCarve& s, int n_acq, int B, int mpad) {
+    dT = s.take<double>((size_t)n_acq * B * mpad);  // every acquisition of every draw
+    dacc = s.take<double>((size_t)n_acq * mpad);    // ... averaged over the draws
+    dmumin = s.take<double>(B);                     // lowest mean of every draw
+    dbad = s.take<int>((size_t)n_acq * B);          // draw has a non-finite value
+    dkinds = s.take<int>(n_acq);
+    dparams = s.take<double>(n_acq);
+  }
+};
+static int acq_run(bgp_ctx* c, int B, int m, int mpad, const double* dmean, const double* dvar, const AcqPlan& ap,
+                   const AcqScratch& as);
+
+// Where post_cov takes K_** = kernel_(Xq) from: generated by the cross kernel from the staged queries, with the white level of
+// the items' hyper-vectors on the diagonal (no white noise off it) -- or uploaded.
+struct PostKss {
+  const double *dH = nullptr, *dXq = nullptr;  // generated for the device hyper-vectors dH (nb x (d + 2)); white level: exp on the device,
+  const double* hk = nullptr;                  // ... or, for ONE item, std::exp of this host copy (bgp_sample_y: not the same bits)
+  const double* host = nullptr;                // uploaded: nb host matrices of m x m with their diagonal, zero padded here
+};
+// The predictive covariance of nb items: P = K_* K^-1 (item b's K^-1 is Kinv[pidxB ? pidxB[b] : b]), K_** into dC, then
+// dC -= P K_*^T -- mode 2: the whole square (every element is read and written by the same lane), mode 1: the lower tiles only (all a
+// factorisation reads).  Both products on the LDS-DMA ring (gemm4_kernel).  cov != NULL: the nb matrices go back to the host.
+static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* Kinv, const int* pidxB, double* dP,
+                    const PostKss& kss, int mode, double* dC, double* cov = nullptr) {
+  const int npad = c->npad, d = c->d, mpad = pad128(m);
+  const size_t sKs = (size_t)mpad * npad, sC = (size_t)mpad * mpad;
+  bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, nb, sKs, (size_t)npad * npad, sKs, pidxB);
+  if (kss.host) {
+    BGP_HIP(hipMemsetAsync(dC, 0, (size_t)nb * sC * sizeof(double), c->stream));
+    for (int b = 0; b < nb; b++) BGP_HIP(rows_up(c, dC + (size_t)b * sC, kss.host + (size_t)b * m * m, m, mpad, m));
+  } else {
+    BGP_TRY(bgp_launch_kcross_batch(c, nb, kss.dH, m, kss.dXq, m, kss.dXq, dC, mpad, sC));
+    if (kss.hk)
+      hipLaunchKernelGGL(add_diag_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, dC, mpad, m, std::exp(kss.hk[d + 1]));
+    else
+      hipLaunchKernelGGL(add_diag_batch_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dC, mpad, sC, m, kss.dH, d);
+  }
+  bgp_launch_gemm4(c->stream, mode, dP, dKs, npad, mpad, mpad, npad, dC, mpad, nb, sKs, sKs, sC, nullptr);
+  BGP_HIP(hipGetLastError());
+  for (int b = 0; cov && b < nb; b++) BGP_HIP(rows_down(c, cov + (size_t)b * m * m, dC + (size_t)b * sC, m, mpad, m));
+  return BGP_OK;
+}
 
 static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
                        double* cov, const AcqPlan* ap) {
@@ -270,41 +359,28 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   }
   BGP_HIP(hipSetDevice(c->device));
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
-  const size_t p = d + 2;
-  const size_t per_item = (size_t)mpad * npad + 2 * (size_t)mpad + (cov ? (size_t)mpad * npad + (size_t)mpad * mpad : 0);
-  const size_t budget = (size_t)1 << 30;  // doubles of scratch per chunk (8 GiB of the 288 GB)
-  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
-  if (chunk >= 8 && chunk < B) chunk &= ~7;  // whole rounds of the item -> XCD pinning (rowquad4_kernel)
+  const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
+  // (1 << 30 doubles of scratch per chunk: 8 GiB of the 288 GB)
+  const int chunk = post_chunk(B, sKs + 2 * (size_t)mpad + (cov ? sKs + sCv : 0), (size_t)1 << 30, true);
   const int n_acq = ap ? ap->n_acq : 0;
-  double *dXq, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr, *dT = nullptr, *dacc = nullptr, *dmumin = nullptr;
-  int* dbad = nullptr;
+  double *dXq, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr;
+  AcqScratch as;
   BgpScratch live(c);
-  int rc = live.carve([&](BgpCarve& s) {
+  BGP_TRY(live.carve([&](BgpCarve& s) {
     dXq = s.take<double>((size_t)m * d);
     dH = s.take<double>((size_t)B * p);
-    dKs = s.take<double>((size_t)chunk * mpad * npad);
+    dKs = s.take<double>((size_t)chunk * sKs);
     dmpart = s.take<double>((size_t)chunk * (npad / 128) * mpad);  // column-tile partials of the means
     dqB = s.take<double>((size_t)B * mpad);    // variance of every item (stays on the device for the acquisitions)
     doutB = s.take<double>((size_t)B * mpad);  // mean of every item
     if (cov) {
-      dP = s.take<double>((size_t)chunk * mpad * npad);
-      dCov = s.take<double>((size_t)chunk * mpad * mpad);
+      dP = s.take<double>((size_t)chunk * sKs);
+      dCov = s.take<double>((size_t)chunk * sCv);
     }
-    if (n_acq) {  // (acq_run keeps the parameters behind dmumin's B entries and the kinds behind dbad's n_acq * B)
-      dT = s.take<double>((size_t)n_acq * B * mpad);
-      dacc = s.take<double>((size_t)n_acq * mpad);
-      dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);
-      dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);
-    }
-  });
-  if (rc) return rc;
-  const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
-  BGP_HIP(bgp_memcpy_async(dXq, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (n_acq) as.take(s, n_acq, B, mpad);
+  }));
+  BGP_TRY(post_stage_queries(c, dXq, Xq, m));
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (c->has_warp) {  // BayesGPR.predict warps the query points with the current warpers (bask/bayesgpr.py:630-632)
-    rc = bgp_launch_warp(c, c->stream, dXq, c->dwarp, dXq, m, 1, 0);
-    if (rc) return rc;
-  }
   for (int off = 0; off < B; off += chunk) {
     const int nb = std::min(chunk, B - off);
     const double* dHc = dH + (size_t)off * p;
@@ -312,42 +388,20 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     const double* al = c->dalpha_sol + (size_t)off * npad;
     double *dq = dqB + (size_t)off * mpad, *dout = doutB + (size_t)off * mpad;
     // K_* and, from the same registers, the column-tile partials of the mean K_* alpha (added in tile order below)
-    rc = bgp_launch_kcross_matvec(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs, al, (size_t)npad, dmpart);
-    if (rc) return rc;
+    BGP_TRY(bgp_launch_kcross_matvec(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs, al, (size_t)npad, dmpart));
     hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((mpad + 255) / 256, nb), dim3(256), 0, c->stream, dmpart, npad / 128, mpad,
                        dout);
-    if (mean)
-      BGP_HIP(bgp_memcpy2d_async(mean + (size_t)off * m, (size_t)m * sizeof(double), dout, (size_t)mpad * sizeof(double),
-                               (size_t)m * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
+    if (mean) BGP_HIP(rows_down(c, mean + (size_t)off * m, dout, m, mpad, nb));
     // q_i = k_i^T K^-1 k_i  (= rowsum((K_* K^-1) o K_*), evaluated on the lower block triangle of K^-1)
-    rc = launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq);
-    if (rc) return rc;
-    if (cov) {
-      bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, nb, sKs, (size_t)npad * npad, sKs, nullptr);
-      // K_** (no white noise off the diagonal; the diagonal gets c(+1) + s2 like kernel_(X)); then cov = K_** - P K_*^T
-      // in place (every element is read and written by the same lane)
-      rc = bgp_launch_kcross_batch(c, nb, dHc, m, dXq, m, dXq, dCov, mpad, sCv);
-      if (rc) return rc;
-      hipLaunchKernelGGL(add_diag_batch_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dCov, mpad, sCv, m,
-                         dHc, d);
-      bgp_launch_gemm4(c->stream, 2, dP, dKs, npad, mpad, mpad, npad, dCov, mpad, nb, sKs, sKs, sCv, nullptr);
-      for (int b = 0; b < nb; b++)
-        BGP_HIP(bgp_memcpy2d_async(cov + (size_t)(off + b) * m * m, (size_t)m * sizeof(double), dCov + (size_t)b * sCv,
-                                 (size_t)mpad * sizeof(double), (size_t)m * sizeof(double), m, hipMemcpyDeviceToHost,
-                                 c->stream));
-    }
+    BGP_TRY(launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq));
+    if (cov) BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, PostKss{dHc, dXq}, 2, dCov, cov + (size_t)off * m * m));
     hipLaunchKernelGGL(finish_var_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, (size_t)mpad, dHc, d,
                        c->ks.form, m, dq, (size_t)mpad);  // in place
     BGP_HIP(hipGetLastError());
-    if (var)
-      BGP_HIP(bgp_memcpy2d_async(var + (size_t)off * m, (size_t)m * sizeof(double), dq, (size_t)mpad * sizeof(double),
-                               (size_t)m * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
+    if (var) BGP_HIP(rows_down(c, var + (size_t)off * m, dq, m, mpad, nb));
     // (the next chunk reuses the scratch slices: stream order keeps its launches behind these copies)
   }
-  if (n_acq) {
-    rc = acq_run(c, c->stream, B, m, mpad, doutB, dqB, *ap, dT, dbad, dmumin, dacc);
-    if (rc) return rc;
-  }
+  if (n_acq) BGP_TRY(acq_run(c, B, m, mpad, doutB, dqB, *ap, as));
   BGP_HIP(bgp_stream_sync(c->stream));
   return BGP_OK;
 }
@@ -359,7 +413,7 @@ extern "C" int bgp_predict_batch(bgp_ctx* c, int B, const double* h_kernel, int 
     bgp_set_error("bgp_predict_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  return predict_run(c, B, h_kernel, m, Xq, mean, var, cov, nullptr);
+  return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, mean, var, cov, nullptr); });
 }
 
 // var_i = max(0, kss_i - q_i) with the prior variances kernel_.diag(Xq) supplied by the host (generic kernels)
@@ -386,62 +440,47 @@ extern "C" int bgp_predict_batch_gram(bgp_ctx* c, int B, int m, const double* Ks
                   c->post_B);
     return BGP_ERR_STATE;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  const int npad = c->npad, n = c->n, mpad = pad128(m);
-  const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
-  const size_t per_item = sKs + 3 * (size_t)mpad + (cov ? sKs + sCv : 0);
-  const size_t budget = (size_t)1 << 29;
-  int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
-  if (chunk >= 8 && chunk < B) chunk &= ~7;
-  double *dKs, *dq, *dout, *dkss, *dP = nullptr, *dCov = nullptr;
-  BgpScratch live(c);
-  int rc = live.carve([&](BgpCarve& s) {
-    dKs = s.take<double>((size_t)chunk * sKs);
-    dq = s.take<double>((size_t)chunk * mpad);
-    dout = s.take<double>((size_t)chunk * mpad);
-    dkss = s.take<double>((size_t)chunk * mpad);
-    if (cov) {
-      dP = s.take<double>((size_t)chunk * sKs);
-      dCov = s.take<double>((size_t)chunk * sCv);
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    const int npad = c->npad, n = c->n, mpad = pad128(m);
+    const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
+    const int chunk = post_chunk(B, sKs + 3 * (size_t)mpad + (cov ? sKs + sCv : 0), (size_t)1 << 29, true);
+    double *dKs, *dq, *dout, *dkss, *dP = nullptr, *dCov = nullptr;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dKs = s.take<double>((size_t)chunk * sKs);
+      dq = s.take<double>((size_t)chunk * mpad);
+      dout = s.take<double>((size_t)chunk * mpad);
+      dkss = s.take<double>((size_t)chunk * mpad);
+      if (cov) {
+        dP = s.take<double>((size_t)chunk * sKs);
+        dCov = s.take<double>((size_t)chunk * sCv);
+      }
+    }));
+    for (int off = 0; off < B; off += chunk) {
+      const int nb = std::min(chunk, B - off);
+      const double* Kinv = c->dKinv + (size_t)off * npad * npad;
+      const double* al = c->dalpha_sol + (size_t)off * npad;
+      // K_* with its zero padding (rows m .. mpad, columns n .. npad)
+      BGP_HIP(hipMemsetAsync(dKs, 0, (size_t)nb * sKs * sizeof(double), c->stream));
+      for (int b = 0; b < nb; b++) BGP_HIP(rows_up(c, dKs + (size_t)b * sKs, Ks + (size_t)(off + b) * m * n, n, npad, m));
+      BGP_HIP(rows_up(c, dkss, kss + (size_t)off * m, m, mpad, nb));
+      hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, al, (size_t)npad,
+                         (const int*)nullptr, npad, m, dout, (size_t)mpad);
+      BGP_HIP(rows_down(c, mean + (size_t)off * m, dout, m, mpad, nb));
+      BGP_TRY(launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq));
+      if (cov) {
+        PostKss src;
+        src.host = Kss + (size_t)off * m * m;
+        BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, src, 2, dCov, cov + (size_t)off * m * m));
+      }
+      hipLaunchKernelGGL(finish_var_gram_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, dkss, (size_t)mpad, m, dq);
+      BGP_HIP(hipGetLastError());
+      BGP_HIP(rows_down(c, var + (size_t)off * m, dq, m, mpad, nb));
+      BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the staged host slices' arena and the scratch)
     }
+    return BGP_OK;
   });
-  if (rc) return rc;
-  for (int off = 0; off < B; off += chunk) {
-    const int nb = std::min(chunk, B - off);
-    const double* Kinv = c->dKinv + (size_t)off * npad * npad;
-    const double* al = c->dalpha_sol + (size_t)off * npad;
-    // K_* with its zero padding (rows m .. mpad, columns n .. npad)
-    BGP_HIP(hipMemsetAsync(dKs, 0, (size_t)nb * sKs * sizeof(double), c->stream));
-    for (int b = 0; b < nb; b++)
-      BGP_HIP(bgp_memcpy2d_async(dKs + (size_t)b * sKs, (size_t)npad * sizeof(double), Ks + (size_t)(off + b) * m * n,
-                                 (size_t)n * sizeof(double), (size_t)n * sizeof(double), m, hipMemcpyHostToDevice, c->stream));
-    BGP_HIP(bgp_memcpy2d_async(dkss, (size_t)mpad * sizeof(double), kss + (size_t)off * m, (size_t)m * sizeof(double),
-                               (size_t)m * sizeof(double), nb, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, al, (size_t)npad,
-                       (const int*)nullptr, npad, m, dout, (size_t)mpad);
-    BGP_HIP(bgp_memcpy2d_async(mean + (size_t)off * m, (size_t)m * sizeof(double), dout, (size_t)mpad * sizeof(double),
-                               (size_t)m * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
-    rc = launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq);
-    if (rc) return rc;
-    if (cov) {
-      bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, nb, sKs, (size_t)npad * npad, sKs, nullptr);
-      BGP_HIP(hipMemsetAsync(dCov, 0, (size_t)nb * sCv * sizeof(double), c->stream));
-      for (int b = 0; b < nb; b++)
-        BGP_HIP(bgp_memcpy2d_async(dCov + (size_t)b * sCv, (size_t)mpad * sizeof(double), Kss + (size_t)(off + b) * m * m,
-                                   (size_t)m * sizeof(double), (size_t)m * sizeof(double), m, hipMemcpyHostToDevice, c->stream));
-      bgp_launch_gemm4(c->stream, 2, dP, dKs, npad, mpad, mpad, npad, dCov, mpad, nb, sKs, sKs, sCv, nullptr);
-      for (int b = 0; b < nb; b++)
-        BGP_HIP(bgp_memcpy2d_async(cov + (size_t)(off + b) * m * m, (size_t)m * sizeof(double), dCov + (size_t)b * sCv,
-                                   (size_t)mpad * sizeof(double), (size_t)m * sizeof(double), m, hipMemcpyDeviceToHost,
-                                   c->stream));
-    }
-    hipLaunchKernelGGL(finish_var_gram_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, dkss, (size_t)mpad, m, dq);
-    BGP_HIP(hipGetLastError());
-    BGP_HIP(bgp_memcpy2d_async(var + (size_t)off * m, (size_t)m * sizeof(double), dq, (size_t)mpad * sizeof(double),
-                               (size_t)m * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
-    BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the staged host slices' arena and the scratch)
-  }
-  return BGP_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -531,23 +570,19 @@ __global__ void acq_square_kernel(double* __restrict__ v, size_t sv, int m) {
   if (i < m) v[(size_t)b * sv + i] *= v[(size_t)b * sv + i];
 }
 
-static int acq_run(bgp_ctx* c, hipStream_t st, int B, int m, int mpad, const double* dmean, const double* dvar,
-                   const AcqPlan& ap, double* dT, int* dbad, double* dmumin, double* dacc) {
-  // kinds / params ride in the tail of the draws' scratch (a few words)
-  int* dkinds = dbad + (size_t)ap.n_acq * B;
-  (void)c;
-  double* dparams = dmumin + B;  // (mumin slice was taken with B + slack below)
-  BGP_HIP(bgp_memcpy_async(dkinds, ap.kinds, (size_t)ap.n_acq * sizeof(int), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dparams, ap.params, (size_t)ap.n_acq * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(hipMemsetAsync(dbad, 0, (size_t)ap.n_acq * B * sizeof(int), st));
-  hipLaunchKernelGGL(acq_mumin_kernel, dim3(B), dim3(256), 0, st, dmean, (size_t)mpad, m, ap.y_mean, ap.y_std, dmumin);
+static int acq_run(bgp_ctx* c, int B, int m, int mpad, const double* dmean, const double* dvar, const AcqPlan& ap,
+                   const AcqScratch& as) {
+  hipStream_t st = c->stream;
+  BGP_HIP(bgp_memcpy_async(as.dkinds, ap.kinds, (size_t)ap.n_acq * sizeof(int), hipMemcpyHostToDevice, st));
+  BGP_HIP(bgp_memcpy_async(as.dparams, ap.params, (size_t)ap.n_acq * sizeof(double), hipMemcpyHostToDevice, st));
+  BGP_HIP(hipMemsetAsync(as.dbad, 0, (size_t)ap.n_acq * B * sizeof(int), st));
+  hipLaunchKernelGGL(acq_mumin_kernel, dim3(B), dim3(256), 0, st, dmean, (size_t)mpad, m, ap.y_mean, ap.y_std, as.dmumin);
   hipLaunchKernelGGL(acq_values_kernel, dim3((m + 255) / 256, B), dim3(256), 0, st, dmean, dvar, (size_t)mpad, m, B,
-                     ap.y_mean, ap.y_std, ap.n_acq, dkinds, dparams, dmumin, dT, dbad);
-  hipLaunchKernelGGL(acq_sum_kernel, dim3((m + 255) / 256, ap.n_acq), dim3(256), 0, st, dT, dbad, (size_t)mpad, m, B,
-                     ap.n_samples, dacc);
+                     ap.y_mean, ap.y_std, ap.n_acq, as.dkinds, as.dparams, as.dmumin, as.dT, as.dbad);
+  hipLaunchKernelGGL(acq_sum_kernel, dim3((m + 255) / 256, ap.n_acq), dim3(256), 0, st, as.dT, as.dbad, (size_t)mpad, m, B,
+                     ap.n_samples, as.dacc);
   BGP_HIP(hipGetLastError());
-  BGP_HIP(bgp_memcpy2d_async(ap.out, (size_t)m * sizeof(double), dacc, (size_t)mpad * sizeof(double),
-                           (size_t)m * sizeof(double), ap.n_acq, hipMemcpyDeviceToHost, st));
+  BGP_HIP(rows_down(c, ap.out, as.dacc, m, mpad, ap.n_acq));
   return BGP_OK;
 }
 
@@ -572,12 +607,11 @@ extern "C" int bgp_acq_batch(bgp_ctx* c, int B, const double* h_kernel, int m, c
     bgp_set_error("bgp_acq_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  int rc = acq_check("bgp_acq_batch", n_acq, kinds, params, n_samples, out);
-  if (rc) return rc;
+  BGP_TRY(acq_check("bgp_acq_batch", n_acq, kinds, params, n_samples, out));
   AcqPlan ap;
   ap.n_acq = n_acq, ap.kinds = kinds, ap.params = params, ap.y_mean = y_mean, ap.y_std = y_std, ap.n_samples = n_samples;
   ap.out = out;
-  return predict_run(c, B, h_kernel, m, Xq, nullptr, nullptr, nullptr, &ap);
+  return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, nullptr, nullptr, nullptr, &ap); });
 }
 
 // The same closed forms on caller-supplied (mu, std) rows: B x m each, already in y units (y_mean = 0, y_std = 1).
@@ -588,33 +622,27 @@ extern "C" int bgp_acq_values(bgp_ctx* c, int B, int m, const double* mu, const 
     bgp_set_error("bgp_acq_values: bad argument");
     return BGP_ERR_INVALID;
   }
-  int rc = acq_check("bgp_acq_values", n_acq, kinds, params, n_samples, out);
-  if (rc) return rc;
-  BGP_HIP(hipSetDevice(c->device));
-  const int mpad = pad128(m);
-  double *dmu, *dvar, *dT, *dacc, *dmumin;
-  int* dbad;
-  BgpScratch live(c);
-  rc = live.carve([&](BgpCarve& s) {
-    dmu = s.take<double>((size_t)B * mpad);
-    dvar = s.take<double>((size_t)B * mpad);
-    dT = s.take<double>((size_t)n_acq * B * mpad);
-    dacc = s.take<double>((size_t)n_acq * mpad);
-    dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);       // (+ the parameters: acq_run)
-    dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);    // (+ the kinds)
+  BGP_TRY(acq_check("bgp_acq_values", n_acq, kinds, params, n_samples, out));
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    const int mpad = pad128(m);
+    double *dmu, *dvar;
+    AcqScratch as;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dmu = s.take<double>((size_t)B * mpad);
+      dvar = s.take<double>((size_t)B * mpad);
+      as.take(s, n_acq, B, mpad);
+    }));
+    BGP_HIP(rows_up(c, dmu, mu, m, mpad, B));
+    BGP_HIP(rows_up(c, dvar, std_, m, mpad, B));
+    hipLaunchKernelGGL(acq_square_kernel, dim3((m + 255) / 256, B), dim3(256), 0, c->stream, dvar, (size_t)mpad, m);
+    AcqPlan ap;
+    ap.n_acq = n_acq, ap.kinds = kinds, ap.params = params, ap.n_samples = n_samples, ap.out = out;
+    BGP_TRY(acq_run(c, B, m, mpad, dmu, dvar, ap, as));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
   });
-  if (rc) return rc;
-  BGP_HIP(bgp_memcpy2d_async(dmu, (size_t)mpad * sizeof(double), mu, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
-                           B, hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy2d_async(dvar, (size_t)mpad * sizeof(double), std_, (size_t)m * sizeof(double),
-                           (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(acq_square_kernel, dim3((m + 255) / 256, B), dim3(256), 0, c->stream, dvar, (size_t)mpad, m);
-  AcqPlan ap;
-  ap.n_acq = n_acq, ap.kinds = kinds, ap.params = params, ap.n_samples = n_samples, ap.out = out;
-  rc = acq_run(c, c->stream, B, m, mpad, dmu, dvar, ap, dT, dbad, dmumin, dacc);
-  if (rc) return rc;
-  BGP_HIP(bgp_stream_sync(c->stream));
-  return BGP_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -789,38 +817,38 @@ extern "C" int bgp_lml_grad_batch(bgp_ctx* c, int B, const double* h, double* lm
     bgp_set_error("bgp_lml_grad_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  c->post_B = 0;
-  const size_t p = c->d + 2;
-  std::vector<int> st(B, 0);
-  int rc = bgp_posterior_build(c, B, h, 1, nullptr, nullptr, nullptr, lml, st.data());
-  if (rc) return rc;
-  c->post_B = 0;  // the resident K^-1 belong to a gradient evaluation, not to a posterior
-  const int ntiles = c->nblk * (c->nblk + 1) / 2;
-  double *dgrad, *dH, *dgpart;
-  BgpScratch live(c);
-  rc = live.carve([&](BgpCarve& s) {
-    dgrad = s.take<double>((size_t)B * p);
-    dH = s.take<double>((size_t)B * p);
-    dgpart = s.take<double>((size_t)B * p * ntiles);
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    c->post_B = 0;
+    const size_t p = c->d + 2;
+    std::vector<int> st(B, 0);
+    BGP_TRY(bgp_posterior_build(c, B, h, 1, nullptr, nullptr, nullptr, lml, st.data()));
+    c->post_B = 0;  // the resident K^-1 belong to a gradient evaluation, not to a posterior
+    const int ntiles = c->nblk * (c->nblk + 1) / 2;
+    double *dgrad, *dH, *dgpart;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dgrad = s.take<double>((size_t)B * p);
+      dH = s.take<double>((size_t)B * p);
+      dgpart = s.take<double>((size_t)B * p * ntiles);
+    }));
+    BGP_HIP(hipMemsetAsync(dgpart, 0, (size_t)B * p * ntiles * sizeof(double), c->stream));
+    BGP_HIP(bgp_memcpy_async(dH, h, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(lml_grad_kernel, dim3(8 * ((B + 7) / 8) * ntiles), dim3(256), 0, c->stream, c->dXeff, dH, c->dKinv,
+                       c->dalpha_sol, dgpart, c->n, c->d, c->npad, c->nblk, c->ks.form, c->ks.stationary, B);
+    BGP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(grad_reduce_kernel, dim3(B), dim3(((int)p + 63) / 64 * 64), 0, c->stream, dgpart, dgrad, ntiles,
+                       (int)p);
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(bgp_memcpy_async(grad, dgrad, (size_t)B * p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    for (int b = 0; b < B; b++) {
+      if (st[b] != 0)
+        for (size_t k = 0; k < p; k++) grad[(size_t)b * p + k] = 0.0;  // sklearn/_gpr.py:589: (-inf, zeros)
+      if (status) status[b] = st[b];
+    }
+    return BGP_OK;
   });
-  if (rc) return rc;
-  BGP_HIP(hipMemsetAsync(dgpart, 0, (size_t)B * p * ntiles * sizeof(double), c->stream));
-  BGP_HIP(bgp_memcpy_async(dH, h, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(lml_grad_kernel, dim3(8 * ((B + 7) / 8) * ntiles), dim3(256), 0, c->stream, c->dXeff, dH, c->dKinv,
-                     c->dalpha_sol, dgpart, c->n, c->d, c->npad, c->nblk, c->ks.form, c->ks.stationary, B);
-  BGP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3(B), dim3(((int)p + 63) / 64 * 64), 0, c->stream, dgpart, dgrad, ntiles,
-                     (int)p);
-  BGP_HIP(hipGetLastError());
-  BGP_HIP(bgp_memcpy_async(grad, dgrad, (size_t)B * p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  BGP_HIP(bgp_stream_sync(c->stream));
-  for (int b = 0; b < B; b++) {
-    if (st[b] != 0)
-      for (size_t k = 0; k < p; k++) grad[(size_t)b * p + k] = 0.0;  // sklearn/_gpr.py:589: (-inf, zeros)
-    if (status) status[b] = st[b];
-  }
-  return BGP_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -852,56 +880,46 @@ extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double*
     bgp_set_error("bgp_pvrs: no resident posterior (call bgp_posterior_batch / bgp_pvrs_prepare first)");
     return BGP_ERR_STATE;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), Tpad = pad128(T);
-  const size_t p = d + 2;
-  double *dXc, *dXt, *dhk, *dKc, *dKT, *dPT, *dG, *dKti, *du, *dcov, *dst, *dend;
-  BgpScratch live(c);
-  int rc = live.carve([&](BgpCarve& s) {
-    dXc = s.take<double>((size_t)m * d);
-    dXt = s.take<double>((size_t)T * d);
-    dhk = s.take<double>(p);
-    dKc = s.take<double>((size_t)mpad * npad);   // k(cand, train)
-    dKT = s.take<double>((size_t)Tpad * npad);   // k(thompson, train)
-    dPT = s.take<double>((size_t)Tpad * npad);   // K_T Kinv
-    dG = s.take<double>((size_t)mpad * Tpad);    // K_c Kinv K_T^T
-    dKti = s.take<double>((size_t)mpad * Tpad);  // k(cand, thompson)
-    du = s.take<double>(mpad);
-    dcov = s.take<double>(mpad);
-    dst = s.take<double>(Tpad);
-    dend = s.take<double>(0);
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), Tpad = pad128(T);
+    const size_t p = d + 2;
+    double *dXc, *dXt, *dhk, *dKc, *dKT, *dPT, *dG, *dKti, *du, *dcov, *dst, *dend;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dXc = s.take<double>((size_t)m * d);
+      dXt = s.take<double>((size_t)T * d);
+      dhk = s.take<double>(p);
+      dKc = s.take<double>((size_t)mpad * npad);   // k(cand, train)
+      dKT = s.take<double>((size_t)Tpad * npad);   // k(thompson, train)
+      dPT = s.take<double>((size_t)Tpad * npad);   // K_T Kinv
+      dG = s.take<double>((size_t)mpad * Tpad);    // K_c Kinv K_T^T
+      dKti = s.take<double>((size_t)mpad * Tpad);  // k(cand, thompson)
+      du = s.take<double>(mpad);
+      dcov = s.take<double>(mpad);
+      dst = s.take<double>(Tpad);
+      dend = s.take<double>(0);
+    }));
+    const double* Kinv = c->dKinv;
+    BGP_TRY(post_stage_queries(c, dXc, Xcand, m));
+    BGP_TRY(post_stage_queries(c, dXt, Xthompson, T));
+    BGP_HIP(bgp_memcpy_async(dhk, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(hipMemsetAsync(dKc, 0, (size_t)(dend - dKc) * sizeof(double), c->stream));  // (zero padding of every matrix and vector)
+    BGP_TRY(bgp_launch_kcross(c, dhk, m, dXc, n, c->dXeff, dKc, npad));
+    BGP_TRY(bgp_launch_kcross(c, dhk, T, dXt, n, c->dXeff, dKT, npad));
+    BGP_TRY(bgp_launch_kcross(c, dhk, m, dXc, T, dXt, dKti, Tpad));
+    // P_T = K_T Kinv ; s_t = rowsum(P_T o K_T) ; u_i = rowsum((K_c Kinv) o K_c) ; G = K_c P_T^T
+    bgp_launch_gemm4(c->stream, 0, dKT, Kinv, npad, Tpad, npad, npad, dPT, npad, 1, 0, 0, 0, nullptr);
+    BGP_TRY(launch_rowquad(c, dKT, npad, 0, Kinv, npad, 0, nullptr, Tpad, npad, 1, dst));
+    BGP_TRY(launch_rowquad(c, dKc, npad, 0, Kinv, npad, 0, nullptr, mpad, npad, 1, du));
+    bgp_launch_gemm4(c->stream, 0, dKc, dPT, npad, mpad, Tpad, npad, dG, Tpad, 1, 0, 0, 0, nullptr);
+    hipLaunchKernelGGL(pvrs_combine_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, dG, Tpad, dKti, Tpad, du,
+                       dst, kernel_diag_value(c, h_kernel), m, T, dcov);
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(bgp_memcpy_async(covs, dcov, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
   });
-  if (rc) return rc;
-  const double* Kinv = c->dKinv;
-  BGP_HIP(bgp_memcpy_async(dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(dXt, Xthompson, (size_t)T * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(dhk, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (c->has_warp) {  // candidates and Thompson points are compared in the warped space (bask/acquisition.py:324-327)
-    rc = bgp_launch_warp(c, c->stream, dXc, c->dwarp, dXc, m, 1, 0);
-    if (rc) return rc;
-    rc = bgp_launch_warp(c, c->stream, dXt, c->dwarp, dXt, T, 1, 0);
-    if (rc) return rc;
-  }
-  BGP_HIP(hipMemsetAsync(dKc, 0, (size_t)(dend - dKc) * sizeof(double), c->stream));  // (zero padding of every matrix and vector)
-  rc = bgp_launch_kcross(c, dhk, m, dXc, n, c->dXeff, dKc, npad);
-  if (rc) return rc;
-  rc = bgp_launch_kcross(c, dhk, T, dXt, n, c->dXeff, dKT, npad);
-  if (rc) return rc;
-  rc = bgp_launch_kcross(c, dhk, m, dXc, T, dXt, dKti, Tpad);
-  if (rc) return rc;
-  // P_T = K_T Kinv ; s_t = rowsum(P_T o K_T) ; u_i = rowsum((K_c Kinv) o K_c) ; G = K_c P_T^T
-  bgp_launch_gemm4(c->stream, 0, dKT, Kinv, npad, Tpad, npad, npad, dPT, npad, 1, 0, 0, 0, nullptr);
-  rc = launch_rowquad(c, dKT, npad, 0, Kinv, npad, 0, nullptr, Tpad, npad, 1, dst);
-  if (rc) return rc;
-  rc = launch_rowquad(c, dKc, npad, 0, Kinv, npad, 0, nullptr, mpad, npad, 1, du);
-  if (rc) return rc;
-  bgp_launch_gemm4(c->stream, 0, dKc, dPT, npad, mpad, Tpad, npad, dG, Tpad, 1, 0, 0, 0, nullptr);
-  hipLaunchKernelGGL(pvrs_combine_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, dG, Tpad, dKti, Tpad, du,
-                     dst, kernel_diag_value(c, h_kernel), m, T, dcov);
-  BGP_HIP(hipGetLastError());
-  BGP_HIP(bgp_memcpy_async(covs, dcov, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  BGP_HIP(bgp_stream_sync(c->stream));
-  return BGP_OK;
 }
 
 extern "C" int bgp_pvrs_prepare(bgp_ctx* c, const double* h_kernel, int has_alpha_vec, int* status) {
@@ -912,9 +930,7 @@ extern "C" int bgp_pvrs_prepare(bgp_ctx* c, const double* h_kernel, int has_alph
     bgp_set_error("bgp_pvrs_prepare: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  c->post_B = 0;
-  return bgp_posterior_build(c, 1, h_kernel, has_alpha_vec ? 1 : 0, nullptr, nullptr, nullptr, nullptr, status);
+  return post_build(c, 1, h_kernel, has_alpha_vec ? 1 : 0, nullptr, nullptr, nullptr, nullptr, status);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -954,6 +970,43 @@ __global__ void add_mean_rows_kernel(double* __restrict__ out, int ldo, const do
 }
 
 static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out);
+
+// Child workspace for the Cholesky of nb covariance matrices of m x m (it shares the stream); cached on the context and grown on demand
+// (an m = 10 000 candidate grid needs 0.8 GB: re-allocating it per call costs more than the factorisation)
+static int post_child(bgp_ctx* c, int m, int nb, bgp_ctx** out) {
+  const int mpad = pad128(m);
+  BGP_TRY(ensure_child(c, mpad, nb, out));
+  (*out)->n = m;
+  (*out)->npad = mpad;
+  (*out)->nblk = mpad / 128;
+  return BGP_OK;
+}
+
+// Cholesky of the child's nb matrices in place (rhs and statuses cleared in front of it), the statuses on their way to the host right
+// behind it.  allow_launch_free: where bgp_lml_enqueue_dev's rule takes the shape, ONE launch-free kernel (a single covariance of 79
+// block columns at 10 000 candidates is the longest launch chain of a tell: 12.6 -> 10.9 ms per call, same draws) -- then the call waits
+// for it, and should a wait inside it have timed out, `rebuild` restores the matrices, they are factorised by launches, and the context
+// stays on them (bgp_ps_note_timeout).
+template <class Rebuild>
+static int post_factor_child(bgp_ctx* c, bgp_ctx* w, int nb, bool allow_launch_free, int* status, Rebuild&& rebuild) {
+  for (;;) {
+    BGP_HIP(hipMemsetAsync(w->dyw, 0, (size_t)nb * w->npad * sizeof(double), c->stream));
+    BGP_HIP(hipMemsetAsync(w->dstatus, 0, (size_t)nb * sizeof(int), c->stream));
+    // (after a time-out bgp_ps_allowed refuses, and the redo counts as one eligible call of the cool-down)
+    const bool ps = allow_launch_free && bgp_persist_fits(w, nb) &&
+                    (c->persist == 1 || (c->persist == -1 && bgp_persist_auto_rule(w->nblk, nb))) && bgp_ps_allowed(c);
+    if (ps) {
+      c->ps_calls++;
+      w->persist = 1;
+    }
+    BGP_TRY(ps ? bgp_launch_cholesky_persist(w, nb, 0) : bgp_launch_cholesky(w, nb, 0));
+    BGP_HIP(bgp_memcpy_async(status, w->dstatus, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (!ps) return BGP_OK;
+    BGP_HIP(bgp_stream_sync(c->stream));
+    if (!bgp_ps_timed_out(c, w, "the covariance is rebuilt and factorised")) return BGP_OK;
+    BGP_TRY(rebuild());
+  }
+}
 
 // out[r] = mean + L z[r] for ALL draws r of one posterior: one wave per row of the lower factor, which is read once
 // (the draws' normal vectors stay in L2); rows of z / out have stride ldz.  Fixed order: bitwise reproducible.
@@ -996,21 +1049,15 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
     bgp_set_error("bgp_sample_y: posterior %d not resident (%d resident)", b, c->post_B);
     return BGP_ERR_STATE;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), rpad = pad128(n_draws);
-  const size_t p = d + 2;
-  // child workspace for the m x m Cholesky (shares the stream); cached on the context and grown on demand
-  // (an m = 10 000 candidate grid needs 0.8 GB: re-allocating it per call costs more than the factorisation)
-  bgp_ctx* w = nullptr;
-  int rc = ensure_child(c, mpad, 1, &w);
-  if (rc) return rc;
-  w->n = m;
-  w->npad = mpad;
-  w->nblk = mpad / 128;
-  do {
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), rpad = pad128(n_draws);
+    const size_t p = d + 2;
+    bgp_ctx* w = nullptr;
+    BGP_TRY(post_child(c, m, 1, &w));
     double *dXq, *dhk, *dKs, *dP, *dmean, *dZ, *dO;
     BgpScratch live(c);
-    rc = live.carve([&](BgpCarve& s) {
+    BGP_TRY(live.carve([&](BgpCarve& s) {
       dXq = s.take<double>((size_t)m * d);
       dhk = s.take<double>(p);
       dKs = s.take<double>((size_t)mpad * npad);
@@ -1018,79 +1065,39 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
       dmean = s.take<double>(mpad);
       dZ = s.take<double>((size_t)rpad * mpad);
       dO = s.take<double>((size_t)rpad * mpad);
-    });
-    if (rc) break;
+    }));
     const double* Kinv = c->dKinv + (size_t)b * npad * npad;
     const double* al = c->dalpha_sol + (size_t)b * npad;
-    hipError_t e = hipSuccess;
-#define SY(call)                       \
-  if ((e = (call)) != hipSuccess) {    \
-    bgp_set_error("bgp_sample_y: %s failed: %s", #call, hipGetErrorString(e)); \
-    rc = BGP_ERR_HIP;                  \
-    break;                             \
-  }
-    SY(bgp_memcpy_async(dXq, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    SY(bgp_memcpy_async(dhk, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (c->has_warp && (rc = bgp_launch_warp(c, c->stream, dXq, c->dwarp, dXq, m, 1, 0))) break;
-    SY(hipMemsetAsync(dKs, 0, (size_t)mpad * npad * sizeof(double), c->stream));
-    SY(hipMemsetAsync(dZ, 0, (size_t)rpad * mpad * sizeof(double), c->stream));
-    SY(bgp_memcpy2d_async(dZ, (size_t)mpad * sizeof(double), z, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
-                        n_draws, hipMemcpyHostToDevice, c->stream));
-    if ((rc = bgp_launch_kcross(c, dhk, m, dXq, n, c->dXeff, dKs, npad))) break;
+    BGP_TRY(post_stage_queries(c, dXq, Xq, m));
+    BGP_HIP(bgp_memcpy_async(dhk, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(hipMemsetAsync(dKs, 0, (size_t)mpad * npad * sizeof(double), c->stream));
+    BGP_HIP(hipMemsetAsync(dZ, 0, (size_t)rpad * mpad * sizeof(double), c->stream));
+    BGP_HIP(rows_up(c, dZ, z, m, mpad, n_draws));
+    BGP_TRY(bgp_launch_kcross(c, dhk, m, dXq, n, c->dXeff, dKs, npad));
     hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, 1), dim3(256), 0, c->stream, dKs, npad, (size_t)0, al,
                        (size_t)0, (const int*)nullptr, n, m, dmean, (size_t)0);
-    // P = K_* K^-1, then cov = K_** - P K_*^T in the child's matrix, lower tiles only (all the factorisation reads):
-    // both products on the LDS-DMA ring (gemm4_kernel)
-    bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, 1, 0, 0, 0, nullptr);
-    int st = 0;
-    for (int attempt = 0; attempt < 2 && !rc; attempt++) {
-      if ((rc = bgp_launch_kcross(c, dhk, m, dXq, m, dXq, w->dK, mpad))) break;
-      hipLaunchKernelGGL(add_diag_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, w->dK, mpad, m,
-                         std::exp(h_kernel[d + 1]));
-      bgp_launch_gemm4(c->stream, 1, dP, dKs, npad, mpad, mpad, npad, w->dK, mpad, 1, 0, 0, 0, nullptr);
+    // cov = K_** - P K_*^T in the child's matrix (white level from the host's exp), + jitter, identity padding
+    auto build_cov = [&]() -> int {
+      BGP_TRY(post_cov(c, 1, m, dKs, Kinv, nullptr, dP, PostKss{dhk, dXq, h_kernel}, 1, w->dK));
       hipLaunchKernelGGL(cov_prepare_kernel, dim3(1024), dim3(256), 0, c->stream, w->dK, m, mpad, jitter);
-      SY(hipMemsetAsync(w->dyw, 0, (size_t)mpad * sizeof(double), c->stream));
-      SY(hipMemsetAsync(w->dstatus, 0, sizeof(int), c->stream));
-      // the covariance's factorisation -- ONE matrix of 79 block columns at 10 000 candidates, the longest launch chain of
-      // a tell -- on the launch-free path (12.6 -> 10.9 ms per call, same draws); should a wait time out, the covariance
-      // is rebuilt and factorised by launches, and the context stays on them
-      const bool ps = bgp_persist_fits(w, 1) && (c->persist == 1 || (c->persist == -1 && bgp_persist_auto_rule(w->nblk, 1))) &&
-                      bgp_ps_allowed(c);
-      if (ps) {
-        c->ps_calls++;
-        w->persist = 1;
-        if ((rc = bgp_launch_cholesky_persist(w, 1, 0))) break;
-      } else if ((rc = bgp_launch_cholesky(w, 1, 0))) {
-        break;
-      }
-      SY(bgp_memcpy_async(&st, w->dstatus, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      SY(bgp_stream_sync(c->stream));
-      if (ps && w->ps_herr && *w->ps_herr != 0) {
-        *w->ps_herr = 0;
-        bgp_ps_note_timeout(c, "the covariance is rebuilt and factorised");
-        continue;
-      }
-      break;
-    }
-    if (rc) break;
+      return BGP_OK;
+    };
+    int st = 0;
+    BGP_TRY(build_cov());
+    BGP_TRY(post_factor_child(c, w, 1, true, &st, build_cov));
+    BGP_HIP(bgp_stream_sync(c->stream));
     if (st != 0) {
       bgp_set_error("bgp_sample_y: predictive covariance not positive definite at pivot %d (jitter %.3g)", st, jitter);
-      rc = BGP_ERR_NOTPD;
-      break;
+      return BGP_ERR_NOTPD;
     }
     // out = mean + L z for every draw (the factor's strict upper triangle is never read)
     hipLaunchKernelGGL(tri_matmul_draws_kernel, dim3((m + 3) / 4), dim3(256), 0, c->stream, w->dK, mpad, dZ, mpad, n_draws,
                        dmean, m, dO);
-    SY(hipGetLastError());
-    SY(bgp_memcpy2d_async(out, (size_t)m * sizeof(double), dO, (size_t)mpad * sizeof(double),
-                        (size_t)m * sizeof(double), n_draws, hipMemcpyDeviceToHost, c->stream));
-    SY(bgp_stream_sync(c->stream));
-#undef SY
-  } while (0);
-  (void)hipStreamSynchronize(c->stream);
-  if (rc) bgp_xfer_drop_pending();  // (a failed call unpacks nothing into the caller's buffers later)
-  bgp_xfer_release(c->stream);
-  return rc;
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(rows_down(c, out, dO, m, mpad, n_draws));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
+  });
 }
 
 // out_b = mean_b + L_b z_b for the lower factors left by the batched Cholesky (one wave per row, fixed order)
@@ -1159,72 +1166,51 @@ extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const doub
       bgp_set_error("bgp_sample_y_batch: posterior %d not resident (%d resident)", pidx[i], c->post_B);
       return BGP_ERR_STATE;
     }
-  BGP_HIP(hipSetDevice(c->device));
-  const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
-  const size_t p = d + 2;
-  const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
-  const size_t per_item = 2 * sKs + sCv + 3 * (size_t)mpad;  // K_*, P, cov (child), mean / z / out
-  const size_t budget = (size_t)1 << 30;                     // doubles per chunk (8 GiB)
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
-  bgp_ctx* w = nullptr;
-  int rc = ensure_child(c, mpad, chunk, &w);
-  if (rc) return rc;
-  w->n = m;
-  w->npad = mpad;
-  w->nblk = mpad / 128;
-  double *dXq, *dH, *dKs, *dP, *dmean, *dZ, *dO;
-  int* dpidx;
-  BgpScratch live(c);
-  rc = live.carve([&](BgpCarve& s) {
-    dXq = s.take<double>((size_t)m * d);
-    dH = s.take<double>((size_t)B * p);
-    dKs = s.take<double>((size_t)chunk * sKs);
-    dP = s.take<double>((size_t)chunk * sKs);
-    dmean = s.take<double>((size_t)chunk * mpad);
-    dZ = s.take<double>((size_t)chunk * mpad);
-    dO = s.take<double>((size_t)chunk * mpad);
-    dpidx = s.take<int>(B);
+  return post_call(c, [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
+    const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
+    // per item: K_*, P, cov (child), mean / z / out; 1 << 30 doubles per chunk (8 GiB)
+    const int chunk = post_chunk(B, 2 * sKs + sCv + 3 * (size_t)mpad, (size_t)1 << 30, false);
+    bgp_ctx* w = nullptr;
+    BGP_TRY(post_child(c, m, chunk, &w));
+    double *dXq, *dH, *dKs, *dP, *dmean, *dZ, *dO;
+    int* dpidx;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dXq = s.take<double>((size_t)m * d);
+      dH = s.take<double>((size_t)B * p);
+      dKs = s.take<double>((size_t)chunk * sKs);
+      dP = s.take<double>((size_t)chunk * sKs);
+      dmean = s.take<double>((size_t)chunk * mpad);
+      dZ = s.take<double>((size_t)chunk * mpad);
+      dO = s.take<double>((size_t)chunk * mpad);
+      dpidx = s.take<int>(B);
+    }));
+    BGP_TRY(post_stage_queries(c, dXq, Xq, m));
+    BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(dpidx, pidx, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    for (int off = 0; off < B; off += chunk) {
+      const int nb = std::min(chunk, B - off);
+      const double* dHc = dH + (size_t)off * p;
+      const int* dpc = dpidx + off;
+      BGP_HIP(hipMemsetAsync(dZ, 0, (size_t)nb * mpad * sizeof(double), c->stream));
+      BGP_HIP(rows_up(c, dZ, z + (size_t)off * m, m, mpad, nb));
+      BGP_TRY(bgp_launch_kcross_batch(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs));
+      hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, c->dalpha_sol,
+                         (size_t)npad, dpc, n, m, dmean, (size_t)mpad);
+      // cov = K_** - P K_*^T in place in the child's matrices, + jitter, identity padding
+      BGP_TRY(post_cov(c, nb, m, dKs, c->dKinv, dpc, dP, PostKss{dHc, dXq}, 1, w->dK));
+      hipLaunchKernelGGL(cov_prepare_kernel, dim3(256, nb), dim3(256), 0, c->stream, w->dK, m, mpad, jitter);
+      // (by launches: nothing waits inside a chunk, so there is nothing to rebuild)
+      BGP_TRY(post_factor_child(c, w, nb, false, status + off, [] { return (int)BGP_OK; }));
+      hipLaunchKernelGGL(tri_matvec_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, w->dK, mpad, dZ, dmean, m, dO);
+      BGP_HIP(hipGetLastError());
+      BGP_HIP(rows_down(c, out + (size_t)off * m, dO, m, mpad, nb));
+    }
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
   });
-  if (rc) return rc;
-  BGP_HIP(bgp_memcpy_async(dXq, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(dpidx, pidx, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (c->has_warp) {
-    rc = bgp_launch_warp(c, c->stream, dXq, c->dwarp, dXq, m, 1, 0);
-    if (rc) return rc;
-  }
-  for (int off = 0; off < B; off += chunk) {
-    const int nb = std::min(chunk, B - off);
-    const double* dHc = dH + (size_t)off * p;
-    const int* dpc = dpidx + off;
-    BGP_HIP(hipMemsetAsync(dZ, 0, (size_t)nb * mpad * sizeof(double), c->stream));
-    BGP_HIP(bgp_memcpy2d_async(dZ, (size_t)mpad * sizeof(double), z + (size_t)off * m, (size_t)m * sizeof(double),
-                             (size_t)m * sizeof(double), nb, hipMemcpyHostToDevice, c->stream));
-    rc = bgp_launch_kcross_batch(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs);
-    if (rc) return rc;
-    hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, c->dalpha_sol,
-                       (size_t)npad, dpc, n, m, dmean, (size_t)mpad);
-    // P = K_* K^-1
-    bgp_launch_gemm4(c->stream, 0, dKs, c->dKinv, npad, mpad, npad, npad, dP, npad, nb, sKs, (size_t)npad * npad, sKs, dpc);
-    // cov = K_** - P K_*^T in place in the child's matrices, + jitter, identity padding
-    rc = bgp_launch_kcross_batch(c, nb, dHc, m, dXq, m, dXq, w->dK, mpad, sCv);
-    if (rc) return rc;
-    hipLaunchKernelGGL(add_diag_batch_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, w->dK, mpad, sCv, m, dHc,
-                       d);
-    bgp_launch_gemm4(c->stream, 1, dP, dKs, npad, mpad, mpad, npad, w->dK, mpad, nb, sKs, sKs, sCv, nullptr);
-    hipLaunchKernelGGL(cov_prepare_kernel, dim3(256, nb), dim3(256), 0, c->stream, w->dK, m, mpad, jitter);
-    BGP_HIP(hipMemsetAsync(w->dyw, 0, (size_t)nb * mpad * sizeof(double), c->stream));
-    BGP_HIP(hipMemsetAsync(w->dstatus, 0, (size_t)nb * sizeof(int), c->stream));
-    rc = bgp_launch_cholesky(w, nb, 0);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tri_matvec_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, w->dK, mpad, dZ, dmean, m, dO);
-    BGP_HIP(hipGetLastError());
-    BGP_HIP(bgp_memcpy_async(status + off, w->dstatus, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    BGP_HIP(bgp_memcpy2d_async(out + (size_t)off * m, (size_t)m * sizeof(double), dO, (size_t)mpad * sizeof(double),
-                             (size_t)m * sizeof(double), nb, hipMemcpyDeviceToHost, c->stream));
-  }
-  BGP_HIP(bgp_stream_sync(c->stream));
-  return BGP_OK;
 }
 
 // (the child owns its buffers and BORROWS the parent's stream: it is deleted, never passed to bgp_ctx_destroy)

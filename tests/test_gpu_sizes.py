@@ -171,8 +171,8 @@ def test_batched_predict_equals_item_by_item(lib):
 def test_batched_sample_y_equals_item_by_item(lib, bask):
     """BayesGPR.sample_y(sample_mean=False): one batched posterior build over the drawn chain rows + one batched
     covariance Cholesky (bgp_sample_y_batch) -- the same draws as one posterior build + one bgp_sample_y per draw
-    (same factors bit for bit; the final L z is a wave-per-row dot product here and a tile GEMM there, so the last
-    bit may differ)."""
+    (same factors bit for bit; the final L z is a wave-per-row dot product of one draw here (tri_matvec_kernel) and a
+    wave-per-row pass over all draws of the posterior there (tri_matmul_draws_kernel), so the last bit may differ)."""
     n, d, m = 120, 2, 201
     X, y = synth(n, d, 11)
     gp = bask.BayesGPR(kernel=bask.construct_default_kernel(list(range(d))), random_state=3)
