@@ -88,6 +88,10 @@ SIGNATURES = {
     "bgp_fantasy_moments": (C.c_int, [_vp, _dp, _dp]),
     "bgp_fantasy_end": (C.c_int, [_vp]),
     "bgp_fantasy_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bgp_paths_begin": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "bgp_paths_eval": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
+    "bgp_paths_end": (C.c_int, [_vp]),
+    "bgp_paths_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
@@ -252,6 +256,7 @@ class Context:
         _check(self._lib.bgp_ctx_update_data(self._h, n, _p(X), _p(y), _p(alpha_diag)), "bgp_ctx_update_data")
         self.n = n
         self.resident_H = None
+        self._paths_P = 0  # (bgp_ctx_update_data drops the pathwise draws)
 
     def _H(self, H):
         H = _c(np.atleast_2d(H))
@@ -608,6 +613,45 @@ class Context:
                                              _p(hi), float(gtol), int(max_iter), _p(x), _p(mean), _p(var), _p(iters), _p(evals),
                                              _p(status)), "bgp_minimize_starts")
         return {"x": x, "mean": mean, "var": var, "iters": iters, "evals": evals, "status": status}
+
+    # ---- pathwise posterior function draws (bgp_paths_*)
+    def paths_begin(self, pidx, H_kernel, log_s2, omega, phase, w, eps):
+        """``bgp_paths_begin``: P paths over the resident posteriors ``pidx`` (P,) with kernel parameters ``H_kernel`` (P, d + 2;
+        white level -inf), the posteriors' log white levels ``log_s2`` (P,) and the host-drawn ``omega`` (P, F, d), ``phase``
+        (P, F), ``w`` (P, F + 1), ``eps`` (P, n)."""
+        H = self._H(H_kernel)
+        P = H.shape[0]
+        omega = _c(omega)
+        if omega.ndim != 3 or omega.shape[0] != P or omega.shape[2] != self.d:
+            raise ValueError(f"omega must be (P, F, d) = ({P}, F, {self.d}), got {omega.shape}")
+        F = omega.shape[1]
+        pidx = np.ascontiguousarray(pidx, dtype=np.int32)
+        log_s2, phase, w, eps = _c(log_s2), _c(phase), _c(w), _c(eps)
+        if pidx.shape != (P,) or log_s2.shape != (P,) or phase.shape != (P, F) or w.shape != (P, F + 1) or eps.shape != (P, self.n):
+            raise ValueError("pidx / log_s2 must be (P,), phase (P, F), w (P, F + 1) and eps (P, n)")
+        _check(self._lib.bgp_paths_begin(self._h, P, _p(pidx), _p(H), _p(log_s2), F, _p(omega), _p(phase), _p(w), _p(eps)),
+               "bgp_paths_begin")
+        self._paths_P = P
+
+    def paths_eval(self, Xq, want_grad=False):
+        """``bgp_paths_eval``: (values (P, m), gradients (P, m, d) | None) of the open paths at the rows of ``Xq``."""
+        Xq = _c(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"query points must have {self.d} columns, got {Xq.shape[1]}")
+        P, m = getattr(self, "_paths_P", 0), Xq.shape[0]
+        out = np.empty((P, m))
+        dout = np.empty((P, m, self.d)) if want_grad else None
+        _check(self._lib.bgp_paths_eval(self._h, m, _p(Xq), _p(out), _p(dout) if want_grad else C.cast(None, _dp)), "bgp_paths_eval")
+        return out, dout
+
+    def paths_end(self):
+        self._paths_P = 0
+        _check(self._lib.bgp_paths_end(self._h), "bgp_paths_end")
+
+    def paths_stats(self):
+        out = (C.c_longlong * 2)()
+        _check(self._lib.bgp_paths_stats(self._h, out), "bgp_paths_stats")
+        return {"begins": int(out[0]), "evals": int(out[1])}
 
     def sample_y(self, b, h_kernel, Xq, z, jitter=0.0):
         H = self._H(h_kernel)

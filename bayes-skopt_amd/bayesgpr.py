@@ -32,7 +32,9 @@ from .kernels import RBF as _RBF
 from .sampler import EnsembleSampler
 from .utils import geometric_median, guess_priors, validate_zeroone
 
-__all__ = ["BayesGPR"]
+__all__ = ["BayesGPR", "PosteriorPaths"]
+
+MVN_MODES = ("auto", "reference", "cholesky", "pathwise")
 
 
 class BayesGPR(RegressorMixin, BaseEstimator):
@@ -51,6 +53,11 @@ class BayesGPR(RegressorMixin, BaseEstimator):
       variates; the only practical choice for thousands of query points, where the SVD takes minutes);
     * ``"auto"`` (default): ``"reference"`` up to ``MVN_REFERENCE_MAX_POINTS`` (512) query points,
       ``"cholesky"`` beyond.  The generator is consumed identically in both modes.
+    * ``"pathwise"`` (opt-in, never chosen by ``"auto"``): the draws are ``sample_paths(...)(X)`` -- Matheron's rule on random
+      Fourier features, O(F + n) per query point and no m x m covariance: the mode for Thompson-type
+      draws over thousands of candidates.  Same mean and covariance as ``predict``; a single path is Gaussian only in the
+      limit of many features.  Where it cannot run (warped inputs, generic kernel trees, d > 32, ``noise=True``) the call
+      takes what ``"auto"`` would take and says so once on stderr.
 
     ``resident_sampler`` (default True): ``sample`` / ``fit`` run the ensemble sampler with its walkers, proposals,
     log-priors, accept tests and chain resident on the device (``bgp_mcmc_begin_ex`` / ``_steps`` / ``_end``: no transfer
@@ -96,8 +103,8 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         # exact single-ensemble sharding over the ranks of an initialised process group
         # (distributed.shard_log_prob; every rank must be constructed with the same random_state/data)
         self.shard_ensemble = bool(shard_ensemble)
-        if mvn not in ("auto", "reference", "cholesky"):
-            raise ValueError("mvn must be 'auto', 'reference' or 'cholesky', got %r" % (mvn,))
+        if mvn not in MVN_MODES:
+            raise ValueError("mvn must be 'auto', 'reference', 'cholesky' or 'pathwise', got %r" % (mvn,))
         self.mvn = mvn
         # the ensemble sampler's whole run on the device (bgp_mcmc_run) where the priors and the kernel allow it; False: the
         # host-driven loop (one LML batch per half-step), whose priors are numpy's to the last bit
@@ -877,11 +884,28 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                 scratch._ctx_obj = None
         return picks, np.array(values).reshape(q - 1, X.shape[0]), "fallback", info
 
-    def _mvn_mode(self, m, mvn=None):
-        """'reference' (numpy's SVD draw on the host from the device-built mean / covariance) or 'cholesky' (device)."""
+    def _pathwise_obstacle(self):
+        """Why pathwise draws cannot run on this estimator (None: they can)."""
+        if self.warp_inputs:
+            return "warped inputs"
+        if not self._post.canonical:
+            return "a generic kernel tree"
+        if self._X_train_.shape[1] > 32:
+            return "more than 32 input dimensions"
+        return None
+
+    def _mvn_mode(self, m, mvn=None, noise=False):
+        """'reference' (numpy's SVD draw on the host from the device-built mean / covariance), 'cholesky' (device) or
+        'pathwise' (``sample_paths``; only when asked for, and only where it can run)."""
         mode = self.__dict__.get("mvn", "auto") if mvn is None else mvn
-        if mode not in ("auto", "reference", "cholesky"):
-            raise ValueError("mvn must be 'auto', 'reference' or 'cholesky', got %r" % (mode,))
+        if mode not in MVN_MODES:
+            raise ValueError("mvn must be 'auto', 'reference', 'cholesky' or 'pathwise', got %r" % (mode,))
+        if mode == "pathwise":
+            why = "noisy draws (noise=True)" if noise else self._pathwise_obstacle()
+            if why is None:
+                return mode
+            _pathwise_tell_once(why)
+            mode = "auto"
         if mode == "auto":
             mode = "reference" if m <= self.MVN_REFERENCE_MAX_POINTS else "cholesky"
         if not self._post.canonical:
@@ -899,7 +923,10 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         ``MVN_REFERENCE_MAX_POINTS`` query points)."""
         rng = check_random_state(random_state)
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        mode = self._mvn_mode(X.shape[0], mvn)
+        mode = self._mvn_mode(X.shape[0], mvn, noise)
+        if mode == "pathwise":
+            with self.sample_paths(n_paths=n_samples, sample_mean=sample_mean, random_state=rng) as paths:
+                return paths(X)
         if sample_mean:
             cm = nullcontext(self) if noise else self.noise_set_to_zero()
             with cm:
@@ -923,7 +950,11 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         chosen chain row with the noise off -- same generator consumption here (row index, then the normal vector,
         per draw), one batched device call for all draws.  Returns (n_draws, m)."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        if self._mvn_mode(X.shape[0]) == "reference":
+        mode = self._mvn_mode(X.shape[0])
+        if mode == "pathwise":
+            with self.sample_paths(n_paths=n_draws, random_state=rng) as paths:
+                return np.ascontiguousarray(paths(X).T)
+        if mode == "reference":
             # row index and MVN draw alternate on the generator, as in the reference's loop: the rows cannot be chosen
             # ahead of the draws, so every draw is one device predict (mean, covariance) + one host SVD
             out = np.empty((n_draws, X.shape[0]))
@@ -936,6 +967,45 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             rows.append(self.chain_[rng.choice(len(self.chain_), size=1, replace=True)[0]])
             Z.append(rng.standard_normal((1, X.shape[0])))
         return self._draw_rows(np.array(rows), X, np.vstack(Z), noise=False)
+
+    def sample_paths(self, n_paths=1, sample_mean=False, n_features=1024, random_state=0):
+        """``n_paths`` posterior function draws as FUNCTIONS (a ``PosteriorPaths``): Matheron's rule on ``n_features`` random
+        Fourier features per path.  ``paths(X)`` is (m, n_paths) in y units -- the shape ``sample_y``
+        returns --, ``paths.gradient(X)`` (m, n_paths, d); the object can be evaluated anywhere, any number of times, with
+        consistent values.  ``sample_mean=True``: every path belongs to the median GP; otherwise each path takes one chain
+        row drawn with replacement (ONE batched posterior build over the distinct rows).  The paths are the latent function
+        (noise off).  The generator is consumed in this order: all row indices first (``choice``, none with
+        ``sample_mean``); then per path the omega normals (F x d), for Matern kernels F chi-square variates with 2 nu
+        degrees of freedom, F phases (uniform on [0, 2 pi)), F + 1 weights and n noise normals.  Runs on a device context of
+        its own: the estimator's resident posterior is not disturbed.  Canonical kernels in up to 32 dimensions without input
+        warping; ``ValueError`` otherwise."""
+        why = None if getattr(self, "_X_train_", None) is None else self._pathwise_obstacle()
+        if why is not None:
+            raise ValueError("sample_paths does not support %s" % why)
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("sample_paths before fit is not supported on the MI355X path")
+        n_paths, F = int(n_paths), int(n_features)
+        if n_paths < 1 or not 1 <= F <= 65536:
+            raise ValueError("sample_paths needs n_paths >= 1 and 1 <= n_features <= 65536")
+        rng = check_random_state(random_state)
+        n_theta = len(self.kernel_.theta)
+        if sample_mean:
+            thetas = np.tile(np.asarray(self._post_theta, dtype=np.float64)[None, :n_theta], (n_paths, 1))
+        else:
+            thetas = self.chain_[rng.choice(len(self.chain_), size=n_paths, replace=True)][:, :n_theta]
+        H = self._canonical(thetas)
+        n, d = self._X_train_.shape
+        omega, phase, w, eps = draw_path_variates(rng, n_paths, F, d, n, self._plan.stationary)
+        uniq, inverse = np.unique(H, axis=0, return_inverse=True)  # repeated chain rows share one posterior build
+        ctx = _lib.Context(self._X_train_, self.y_train_, self._alpha_diag(), form=self._plan.form,
+                           stationary=self._plan.stationary, max_batch=self._ctx.max_batch, device=self.device)
+        try:
+            raise_if_not_pd(ctx.posterior(uniq, want_alpha=False)["status"], self.kernel_)
+            ctx.paths_begin(np.asarray(inverse, dtype=np.int32).ravel(), noise_off(H), H[:, -1], omega, phase, w, eps)
+        except BaseException:
+            ctx.close()
+            raise
+        return PosteriorPaths(ctx, float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0]), n_paths, d)
 
     def _draw_rows_reference(self, rows, X, rng, noise):
         """The reference's per-sample loop (``bask/bayesgpr.py:679-706``) with the device doing what the theta setter
@@ -1025,6 +1095,85 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                 ctx.close()
             except Exception:
                 pass
+
+
+MATERN_NU = {"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}
+
+
+def draw_path_variates(rng, n_paths, F, d, n, stationary):
+    """The random numbers of ``n_paths`` pathwise draws, in the documented order -- per path: omega normals (F, d), for a Matern
+    kernel F chi-square variates with 2 nu degrees of freedom (omega rows times sqrt(2 nu / chi2): the multivariate t that is
+    the spectral density of the unit-length-scale Matern kernel; nu = 1/2: Cauchy tails), F phases on [0, 2 pi), F + 1 weights,
+    n noise normals.  Returns omega (P, F, d), phase (P, F), w (P, F + 1), eps (P, n)."""
+    omega, phase = np.empty((n_paths, F, d)), np.empty((n_paths, F))
+    w, eps = np.empty((n_paths, F + 1)), np.empty((n_paths, n))
+    nu = MATERN_NU.get(stationary)
+    for p in range(n_paths):
+        z = rng.standard_normal((F, d))
+        if nu is not None:
+            z = z * np.sqrt(2.0 * nu / rng.chisquare(2.0 * nu, size=F))[:, None]
+        omega[p] = z
+        phase[p] = rng.uniform(0.0, 2.0 * np.pi, size=F)
+        w[p] = rng.standard_normal(F + 1)
+        eps[p] = rng.standard_normal(n)
+    return omega, phase, w, eps
+
+
+class PosteriorPaths:
+    """Posterior function draws of a ``BayesGPR`` (``sample_paths``), resident on a device context of their own
+    (``bgp_paths_*``).  ``paths(X)``: (m, n_paths) in y units; ``paths.gradient(X)``: (m, n_paths, d).  A value does not depend
+    on the other rows of the call: evaluating twice, or on a superset, gives the same bits.  ``close()`` (or leaving the
+    ``with`` block) frees the device state."""
+
+    def __init__(self, ctx, y_mean, y_std, n_paths, d):
+        self._ctx, self._y_mean, self._y_std = ctx, y_mean, y_std
+        self.n_paths, self.d = n_paths, d
+
+    def _X(self, X):
+        if self._ctx is None:
+            raise RuntimeError("the paths have been closed")
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if X.shape[1] != self.d:
+            raise ValueError("query points must have %d columns, got %d" % (self.d, X.shape[1]))
+        return X
+
+    def __call__(self, X):
+        X = self._X(X)
+        out, _ = self._ctx.paths_eval(X)
+        return (self._y_std * out + self._y_mean).T
+
+    def gradient(self, X):
+        X = self._X(X)
+        _, dout = self._ctx.paths_eval(X, want_grad=True)
+        return np.ascontiguousarray(np.transpose(self._y_std * dout, (1, 0, 2)))
+
+    def close(self):
+        ctx, self._ctx = self._ctx, None
+        if ctx is not None:
+            ctx.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_pathwise_told = []
+
+
+def _pathwise_tell_once(why):
+    """One line on stderr, once per process: mvn="pathwise" asked for where the pathwise draws cannot run."""
+    if not _pathwise_told:
+        _pathwise_told.append(True)
+        print("[bayes_skopt_amd] mvn='pathwise': not available for %s; drawing as mvn='auto' does" % why, file=sys.stderr,
+              flush=True)
 
 
 _fantasy_told = []

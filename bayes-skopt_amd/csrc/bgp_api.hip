@@ -349,6 +349,7 @@ extern "C" int bgp_ctx_update_data(bgp_ctx* c, int n, const double* X, const dou
     return BGP_ERR_INVALID;
   }
   BGP_HIP(hipSetDevice(c->device));
+  bgp_paths_abandon(c);  // (pathwise draws belong to the training set they were conditioned on)
   return upload_data(c, n, X, y, alpha_diag);
 }
 
@@ -356,6 +357,7 @@ extern "C" void bgp_ctx_destroy(bgp_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   bgp_fantasy_abandon(c);
+  bgp_paths_abandon(c);
   bgp_mcmc_abandon(c);  // (a sampler run left open: its work is drained, its block freed)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   bgp_free_child(c);

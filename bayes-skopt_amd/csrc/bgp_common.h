@@ -197,6 +197,8 @@ struct bgp_ctx {
   int pending_warped = 0;       // the pending batch carries per-walker warps (redo path of bgp_lml_batch_wait)
   struct bgp_fantasy_state* fantasy = nullptr;  // an open batch proposal (bgp_fantasy_begin .. bgp_fantasy_end; bgp_fantasy.hip)
   long long fant_stats[2] = {0, 0};             // fantasy begins / steps run on this context (bgp_fantasy_stats)
+  struct bgp_paths_state* paths = nullptr;      // pathwise posterior draws (bgp_paths_begin .. bgp_paths_end; bgp_paths.hip)
+  long long paths_stats[2] = {0, 0};            // paths begins / evals run on this context (bgp_paths_stats)
   struct bgp_mcmc_state* mcmc = nullptr;  // an open device-resident sampler run (bgp_mcmc_begin .. bgp_mcmc_end; bgp_mcmc.hip)
   int ps_forbid = 0;            // the device-resident sampler redoes a run after a time-out: launches only, on every rank
   int ps_resident = 0;          // the device-resident sampler is enqueuing: no per-call copy of the error word (its kernels read it)
@@ -375,6 +377,7 @@ int bgp_lml_redo_if_abandoned(bgp_ctx* ctx, int B);
 int bgp_lml_enqueue_dev(bgp_ctx* ctx, int nb, int warped);  // bgp_api.hip: Gram build + factorisation + LML of c->dh[0 .. nb), on the device only
 int bgp_ensure_warp_buffers(bgp_ctx* ctx);                  // bgp_api.hip: the per-walker warp buffers of a warped LML batch exist
 void bgp_fantasy_abandon(bgp_ctx* ctx);  // bgp_fantasy.hip: drop an open batch proposal (context teardown)
+void bgp_paths_abandon(bgp_ctx* ctx);  // bgp_paths.hip: drop the pathwise draws (context teardown, new training data)
 void bgp_mcmc_abandon(bgp_ctx* ctx);  // bgp_mcmc.hip: drop an open sampler run (context teardown, failed calls)
 // the launch-free call of a batch whose results are discarded anyway: forget it (no time-out is counted, nothing is redone)
 static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
@@ -383,6 +386,21 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 }
 int bgp_persist_fits(bgp_ctx* ctx, int B);
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
+
+// ONE exit path for the entry points of bgp_post.hip and bgp_paths.hip (their stages return from the middle, with BGP_HIP or a plain
+// return): a failed call waits for what it enqueued -- its kernels run over scratch that the next call may carve again --, clears the
+// sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success path is the body's own.
+template <class Body>
+static inline int post_call(bgp_ctx* c, Body&& body) {
+  const int rc = body();
+  if (rc != BGP_OK) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+    bgp_xfer_drop_pending();
+    bgp_xfer_release(c->stream);
+  }
+  return rc;
+}
 
 // The context's scratch, carved by ONE layout per call (bgp_mem.h; every region on 16 bytes).  A carve may free and re-allocate
 // dscratch, so the pointers of an earlier one would dangle: while a BgpScratch that has carved is in scope, another carve of the

@@ -130,20 +130,7 @@ static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const
 
 static inline int pad128(int v) { return ((v + 127) / 128) * 128; }
 
-// ONE exit path for the entry points of this file (the stages below return from the middle, with BGP_HIP or a plain return): a
-// failed call waits for what it enqueued -- its kernels run over scratch that the next call may carve again --, clears the sticky HIP
-// error, and none of its downloads is unpacked into the caller's arrays later.  The success path is the body's own.
-template <class Body>
-static int post_call(bgp_ctx* c, Body&& body) {
-  const int rc = body();
-  if (rc != BGP_OK) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-    bgp_xfer_drop_pending();
-    bgp_xfer_release(c->stream);
-  }
-  return rc;
-}
+// (post_call, the ONE exit path of the entry points of this file: bgp_common.h)
 
 // `rows` rows of `w` doubles between a packed host array and device rows of stride `ld`
 static hipError_t rows_up(bgp_ctx* c, double* dev, const double* host, int w, int ld, int rows) {

@@ -250,6 +250,34 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
                         double* mean_out, double* var_out, int* iters, int* evals, int* status);
 
 /*
+ * Pathwise posterior function draws (Matheron's rule on random Fourier features): what BayesGPR.sample_y
+ * (bask/bayesgpr.py:637-718) draws as a joint normal over the query set -- an m x m covariance and its factor per draw --, as
+ * FUNCTIONS that cost O(F + n) per query row and can be evaluated anywhere, any number of times, consistently.  Serves the
+ * Thompson draws of evaluate_acquisitions (bask/acquisition.py:132-136) and PVRS's Thompson points (bask/acquisition.py:328).
+ * Path p (normalised-y units): resident posterior pidx[p]; kernel parameters h_kernel[p] (d + 2, white level -inf as in
+ * bgp_predict_batch: a path is the latent function); s2[p] = the LOG white level of that posterior (-inf: none); host-drawn
+ * omega[p] (F x d, from the spectral density of the unit-length-scale stationary part: N(0, I) for RBF, N(0, I) rows times
+ * sqrt(2 nu / chi2_{2 nu}) for Matern nu), phase[p] (F, U[0, 2 pi)), w[p] (F + 1 standard normals, the last one the constant
+ * term of the sum form) and eps[p] (n standard normals).  With A = sqrt(2 cS / F), cS = c (product form) or 1 (sum form):
+ *   f0(x) = A sum_{j<F, ascending} w_j cos(phase_j + sum_k (x_k / l_k) omega_jk)  [+ sqrt(c) w_F, sum form]
+ *   r = y - f0(X) - sqrt(alpha_diag + s2) eps ;  v = K^-1 r ;  f(x) = f0(x) + sum_{i, ascending} k(x, X_i) v_i
+ *   df/dx_k = -A sum_j w_j sin(arg_j) omega_jk / l_k + sum_i v_i G_ik      (G as in bgp_predict_grad_batch)
+ * bgp_paths_begin: build the state of P paths (1 .. 65 535) of F features (1 .. 65 536) -- omega / l, phase, A w, the constant
+ *   term, v, copies of the training inputs and kernel parameters -- in one owned allocation; afterwards the paths do not read the
+ *   resident posteriors (a later bgp_posterior_batch changes no bit of a path).  Needs d <= 32 and no context-level warp
+ *   (BGP_ERR_INVALID), resident posteriors and every pidx among them (BGP_ERR_STATE).  Replaces an earlier state.
+ * bgp_paths_eval: the P paths at m query rows: out P*m, dout P*m*d (may be NULL; the values are the same bits either way).  The
+ *   value at (path, row) does not depend on which rows or paths share the call.  BGP_ERR_STATE without a state.
+ * bgp_paths_end drops the state; bgp_ctx_update_data and bgp_ctx_destroy drop it too.
+ * bgp_paths_stats: out[0] = begins, out[1] = evals run on this context.
+ */
+int bgp_paths_begin(bgp_ctx* ctx, int P, const int* pidx, const double* h_kernel, const double* s2, int F,
+                    const double* omega, const double* phase, const double* w, const double* eps);
+int bgp_paths_eval(bgp_ctx* ctx, int m, const double* Xq, double* out, double* dout);
+int bgp_paths_end(bgp_ctx* ctx);
+int bgp_paths_stats(bgp_ctx* ctx, long long* out2);
+
+/*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
  * the host (z: n_draws*m), via a Cholesky factor of cov (+jitter) instead of numpy's SVD.
  * Replaces: sklearn sample_y (sklearn/_gpr.py:522-526) reached from BayesGPR.sample_y
