@@ -3,7 +3,8 @@
 Plain numpy in ``np.longdouble`` (x87 extended: 64-bit mantissa, eps = 2^-63 ~ 1.1e-19, 2048 times finer than fp64).  It
 restates, from the definitions in ``gp_oracle.py``'s docstring (canonical vector ``h = [log c, log l_1..l_d, log s2]``,
 product form ``c*S(r) + s2*I``, sum form ``c + S(r) + s2*I``), the Gram build, the Cholesky factor, triangular solves, the
-LML and its gradient, the posterior factors, predict, PVRS covs, the ``sample_y`` transform for a fixed z and warped inputs.
+LML and its gradient, the posterior factors, predict, PVRS covs, the ``sample_y`` transform for a fixed z, warped inputs and
+fantasy conditioning on chosen candidates (every prefix refactorised).
 Only the tests import it; the product never does.  ``gp_oracle.py`` (fp64, scipy/LAPACK) stays the parity oracle; this
 module is what both are measured against in ``tests/test_cpu_precision.py`` and ``tests/test_gpu_precision.py``.
 
@@ -341,6 +342,45 @@ def sample_y(X, y, alpha_diag, h, Xq, z, jitter, stationary="matern52", form="pr
     C[np.diag_indices_from(C)] += LD(jitter)
     Lc = cholesky(C)
     return p["mean"][None, :] + np.asarray(z, dtype=np.float64).astype(LD) @ Lc.T, p
+
+
+def fantasy(X, y, alpha_diag, h, Xc, picks, lies, base_alpha, stationary="matern52", form="product"):
+    """Latent mean and variance at every candidate ``Xc`` after conditioning on ``Xc[picks[:j+1]]`` with fantasy observations,
+    for each prefix j of ``picks`` -- WITHOUT the rank-1 identities of the device path: every prefix refactorises the augmented
+    set ``vstack([X, Xc[picks[:j+1]]])`` (``lml`` / ``predict(noise_zero=True)``), alpha vector ``concat(alpha, base_alpha)``,
+    targets ``concat(y, lies)``.  ``gram`` puts s2 on every diagonal entry, so a fantasy observation's variance is
+    ``base_alpha + exp(h[-1])``.  ``lies`` (q,) normalised values, or None for the kriging believer: the lie of step j is the
+    conditioned mean at ``picks[j]`` before that step (kept in long double), so the means do not move.
+
+    Returns mean, var (q, m); mean0, var0 (m,) before any step; per prefix ``mean_scale`` = max_i sum_j |K*_ij a_j| on the
+    augmented set and ``kappa`` of the augmented Gram matrix; ``prior_var`` (latent); ``lies`` as used."""
+    require()
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    Xc = np.atleast_2d(np.asarray(Xc, dtype=np.float64))
+    n, d = X.shape
+    ad = np.broadcast_to(np.asarray(alpha_diag, dtype=np.float64), (n,))
+    yl = np.asarray(y, dtype=np.float64).astype(LD)
+    picks = [int(p) for p in picks]
+    q, m = len(picks), Xc.shape[0]
+    p0 = predict(X, y, ad, h, Xc, stationary, form, noise_zero=True)
+    out = {"mean": np.empty((q, m), dtype=LD), "var": np.empty((q, m), dtype=LD), "mean0": p0["mean"], "var0": p0["var"],
+           "mean_scale": np.empty(q), "kappa": np.empty(q), "prior_var": prior_var(h, d, form, noise=False),
+           "lies": np.empty(q, dtype=LD)}
+    before = p0["mean"]
+    for j in range(q):
+        out["lies"][j] = before[picks[j]] if lies is None else LD(float(lies[j]))
+        Xa = np.vstack([X, Xc[picks[: j + 1]]])
+        aa = np.concatenate([ad, np.full(j + 1, float(base_alpha))])
+        ya = np.concatenate([yl, out["lies"][: j + 1]])
+        post = lml(Xa, ya.astype(np.float64), aa, h, stationary, form)
+        post["alpha"] = cho_solve(post["L"], ya)  # (the believer's lies are long-double numbers: not rounded to fp64)
+        pr = predict(Xa, None, aa, h, Xc, stationary, form, noise_zero=True, post=post)
+        out["mean"][j], out["var"][j] = pr["mean"], pr["var"]
+        Ks = gram(Xc, h, stationary, form, Y=Xa)
+        out["mean_scale"][j] = float(np.abs(Ks * post["alpha"][None, :]).sum(axis=1).max())
+        out["kappa"][j] = kappa(post["K"])
+        before = pr["mean"]
+    return out
 
 
 def warp_inputs(X, w, dps=40):

@@ -7,7 +7,11 @@ tests/test_gpu_precision.py, against the extended-precision reference (oracle/hp
   misses the reference by at least 10 tol on the LML, alpha and the gradient, so a single-precision slip fails it; so do
   fp32 inputs for the predictive mean and variance, fp32 augmented Gram matrices for PVRS and an fp32 predictive
   covariance for sample_y.
-  (Rounding the inputs of a one-point problem changes nothing: that check is skipped at n = 1.)"""
+  (Rounding the inputs of a one-point problem changes nothing: that check is skipped at n = 1.)
+
+Fantasy conditioning (FANTASY_CASES) is qualified the same way with the fp64 replica of the device recurrences
+(``_precision.fantasy64``) in LAPACK's place: reachable at every step, and fp32 inputs, the dropped sum over the earlier steps
+and a fantasy noise without base_alpha each miss by 10 tol."""
 import numpy as np
 import pytest
 
@@ -31,6 +35,56 @@ def test_every_family_reaches_a_ragged_tile_beyond_the_first_block():
     for st, fm in P.FAMILIES:
         ns = {c["n"] for c in P.LML_CASES if (c["stationary"], c["form"]) == (st, fm)}
         assert len(ns) >= 3 and any(n > 128 and n % 128 for n in ns), (st, fm, sorted(ns))
+
+
+def test_fantasy_cases_cover_every_family_and_the_device_edges():
+    """Every kernel family conditions at least once; a ragged 64-point tile, a ragged 256-candidate block, the staging limit
+    d = 32, fewer draws than resident posteriors, both lie kinds, both alpha kinds, six steps, and forced picks at index 0,
+    m - 1, in the second 256-block and on a training point all appear."""
+    cs = P.FANTASY_CASES
+    assert {(c["stationary"], c["form"]) for c in cs} == set(P.FAMILIES)
+    assert any(c["n"] % 64 for c in cs) and any(c["m"] % 256 for c in cs) and any(c["d"] == 32 for c in cs)
+    assert {1, 63, 64, 65, 129, 257} <= {c["n"] for c in cs} and {2, 255, 256, 257, 513} <= {c["m"] for c in cs}
+    assert {1, 17, 31, 32} <= {c["d"] for c in cs} and {1, 3} <= {c["Bf"] for c in cs}
+    assert any(c["Bf"] < c["B"] for c in cs) and {c["kb"] for c in cs} == {False, True}
+    assert {c["vec_alpha"] for c in cs} == {False, True} and max(len(c["picks"]) for c in cs) == 6
+    assert any(c["base_alpha"] >= 1e-3 and not c["kb"] for c in cs)
+    for c in cs:
+        assert len(set(c["picks"])) == len(c["picks"]) < c["m"] and all(0 <= p < c["m"] for p in c["picks"])
+    assert any(0 in c["picks"] for c in cs) and any(c["m"] - 1 in c["picks"] for c in cs)
+    assert any(256 <= p for c in cs for p in c["picks"]) and any(c["twin"] is not None for c in cs)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in P.FANTASY_CASES])
+def test_fantasy_conditioning(cid):
+    c = P.ALL[cid]
+    X, y, alpha, H, _kap = P.problem(cid)
+    Xc, picks, lies = P.fantasy_inputs(cid)
+    n, st, fm, ba = len(X), c["stationary"], c["form"], c["base_alpha"]
+    worst_reach, worst_bite = 0.0, np.inf
+    for b in range(c["Bf"]):
+        ref = P.ref_fantasy(cid, b)
+        args = (y, alpha, H[b], Xc, picks, lies, ba, st, fm)
+        mean, var = P.fantasy64(X, *args)
+        slips = {"fp32 inputs": P.fantasy64(P.to32(X), y, alpha, H[b], P.to32(Xc), picks, lies, ba, st, fm),
+                 "no sum over the earlier steps": P.fantasy64(X, *args, drop_prev=True)}
+        if ba >= 1e-3:
+            slips["noise without base_alpha"] = P.fantasy64(X, *args, noise=float(np.exp(H[b, -1])))
+        for j in range(len(picks)):
+            tols = (P.tol("fant_mean", ref["kappa"][j], n + j), P.tol("fant_var", ref["kappa"][j], n + j))
+            errs = P.fantasy_errs(mean[j], var[j], ref, j)
+            r = max(e / t for e, t in zip(errs, tols))
+            assert r <= 1 / MARGIN, (cid, b, j, errs, tols)
+            worst_reach = max(worst_reach, r)
+            for name, (ms, vs) in slips.items():
+                if name.startswith("no sum") and j == 0:
+                    continue  # (the first step has no earlier one)
+                bm, bv = (e / t for e, t in zip(P.fantasy_errs(ms[j], vs[j], ref, j), tols))
+                # (the kriging believer leaves the means alone: only fp32 inputs reach them)
+                bite = bv if c["kb"] and not name.startswith("fp32") else min(bm, bv)
+                assert bite >= MARGIN, (cid, b, j, name, bm, bv)
+                worst_bite = min(worst_bite, bite)
+    _report(cid, worst_reach, worst_bite)
 
 
 @pytest.mark.parametrize("cid", [c["id"] for c in P.LML_CASES + P.SCHED_CASES])

@@ -2,7 +2,8 @@
 (tests/_precision.py::tol -- the one tolerance function; tests/test_cpu_precision.py shows fp64 LAPACK meets it with a 10x
 margin and a single-precision slip misses it by 10x): the LML on every tile edge, dimension-staging edge and kernel family,
 every factorisation schedule, the warped LML and posterior, the LML gradient, the posterior factors, predict, PVRS and the
-sample_y transform.  Every test prints its worst err / tol (``pytest -s``); lines start with ``PRECISION``."""
+sample_y transform.  Every test prints its worst err / tol (``pytest -s``); lines start with ``PRECISION``.
+The moments after fantasy conditioning (``fant_mean`` / ``fant_var``) meet the same model in tests/test_gpu_fantasy.py."""
 import json
 import os
 import subprocess
