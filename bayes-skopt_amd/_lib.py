@@ -92,6 +92,7 @@ SIGNATURES = {
     "bgp_paths_eval": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "bgp_paths_end": (C.c_int, [_vp]),
     "bgp_paths_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bgp_paths_minimize": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
@@ -643,6 +644,27 @@ class Context:
         dout = np.empty((P, m, self.d)) if want_grad else None
         _check(self._lib.bgp_paths_eval(self._h, m, _p(Xq), _p(out), _p(dout) if want_grad else C.cast(None, _dp)), "bgp_paths_eval")
         return out, dout
+
+    def paths_minimize(self, X0, lo, hi, gtol=1e-5, max_iter=200, want_grad=False):
+        """``bgp_paths_minimize``: minimise every open path over the box [lo, hi] from its own starts ``X0`` (P, S, d), one
+        workgroup per (start, path) in one launch.  Returns a dict: x (P, S, d; inside the box exactly), fun (P, S; normalised
+        units) and grad (P, S, d | None): the search's evaluator at x; iters, evals, status (P, S; 0 converged to ``gtol``, 1
+        ``max_iter`` reached, 2 no decrease found).  ``max_iter=0`` evaluates the clipped starts."""
+        X0 = _c(X0)
+        P = getattr(self, "_paths_P", 0)
+        if X0.ndim != 3 or X0.shape[2] != self.d or (P and X0.shape[0] != P):
+            raise ValueError(f"X0 must be (P, S, d) = ({P}, S, {self.d}), got {X0.shape}")
+        S = X0.shape[1]
+        shape = (max(P, X0.shape[0]), S)
+        lo = _c(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.d,)))
+        hi = _c(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.d,)))
+        x, fun = np.empty(shape + (self.d,)), np.empty(shape)
+        grad = np.empty(shape + (self.d,)) if want_grad else None
+        iters, evals, status = (np.zeros(shape, dtype=np.int32) for _ in range(3))
+        _check(self._lib.bgp_paths_minimize(self._h, S, _p(X0), _p(lo), _p(hi), float(gtol), int(max_iter), _p(x), _p(fun),
+                                            _p(grad) if want_grad else C.cast(None, _dp), _p(iters), _p(evals), _p(status)),
+               "bgp_paths_minimize")
+        return {"x": x, "fun": fun, "grad": grad, "iters": iters, "evals": evals, "status": status}
 
     def paths_end(self):
         self._paths_P = 0

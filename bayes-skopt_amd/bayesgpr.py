@@ -1122,8 +1122,9 @@ def draw_path_variates(rng, n_paths, F, d, n, stationary):
 class PosteriorPaths:
     """Posterior function draws of a ``BayesGPR`` (``sample_paths``), resident on a device context of their own
     (``bgp_paths_*``).  ``paths(X)``: (m, n_paths) in y units; ``paths.gradient(X)``: (m, n_paths, d).  A value does not depend
-    on the other rows of the call: evaluating twice, or on a superset, gives the same bits.  ``close()`` (or leaving the
-    ``with`` block) frees the device state."""
+    on the other rows of the call: evaluating twice, or on a superset, gives the same bits.  ``paths.minimize(...)``: every
+    path's minimiser over a box, searched on the device.  ``close()`` (or leaving the ``with`` block) frees the device
+    state."""
 
     def __init__(self, ctx, y_mean, y_std, n_paths, d):
         self._ctx, self._y_mean, self._y_std = ctx, y_mean, y_std
@@ -1146,6 +1147,44 @@ class PosteriorPaths:
         X = self._X(X)
         _, dout = self._ctx.paths_eval(X, want_grad=True)
         return np.ascontiguousarray(np.transpose(self._y_std * dout, (1, 0, 2)))
+
+    def minimize(self, bounds=(0.0, 1.0), n_candidates=2000, n_starts=8, X0=None, random_state=0, gtol=1e-5, max_iter=200):
+        """The minimiser of every path over the box ``bounds`` = (low, high) (scalars or d values each), searched on the device:
+        one workgroup per (start, path) runs a bounded quasi-Newton iteration on the path and its analytic gradient
+        (``bgp_paths_minimize``) until the projected gradient is below ``gtol`` (y units) or ``max_iter``
+        iterations.  ``X0=None``: ``n_candidates`` uniform points of the box are drawn -- the generator is consumed by ONE
+        ``uniform(size=(n_candidates, d))`` call, nothing else --, all paths are evaluated there in ONE call, and each path
+        starts from its ``n_starts`` lowest rows (stable argsort, so ties keep the row order).  ``X0``: (S, d) starts shared
+        by all paths, or (n_paths, S, d); no generator is used.  Returns a dict: ``x`` (n_paths, d) the best end point per path and
+        ``fun`` (n_paths,) its value in y units -- never above the path's lowest candidate row --; per start ``x_all``
+        (n_paths, S, d), ``fun_all``, ``status`` (0 converged, 1 ``max_iter``, 2 no decrease), ``iters``, ``evals``
+        (n_paths, S); ``best`` (n_paths,) the index of the best start."""
+        if self._ctx is None:
+            raise RuntimeError("the paths have been closed")
+        d, P = self.d, self.n_paths
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(bounds[0], dtype=np.float64), (d,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(bounds[1], dtype=np.float64), (d,)))
+        if not np.all(lo <= hi):
+            raise ValueError("minimize needs low <= high in every dimension")
+        if X0 is None:
+            n_candidates, n_starts = int(n_candidates), int(n_starts)
+            if not 1 <= n_starts <= n_candidates:
+                raise ValueError("minimize needs 1 <= n_starts <= n_candidates")
+            cand = lo + (hi - lo) * check_random_state(random_state).uniform(size=(n_candidates, d))
+            f, _ = self._ctx.paths_eval(cand)
+            X0 = np.stack([cand[np.argsort(f[p], kind="stable")[:n_starts]] for p in range(P)])
+        else:
+            X0 = np.asarray(X0, dtype=np.float64)
+            if X0.ndim == 2:
+                X0 = np.broadcast_to(X0[None], (P,) + X0.shape)
+            if X0.ndim != 3 or X0.shape[0] != P or X0.shape[1] < 1 or X0.shape[2] != d:
+                raise ValueError("X0 must be (S, d) or (n_paths, S, d) with S >= 1 and d = %d, got %r" % (d, X0.shape))
+        out = self._ctx.paths_minimize(X0, lo, hi, gtol=float(gtol) / self._y_std, max_iter=max_iter)
+        fun_all = self._y_std * out["fun"] + self._y_mean
+        best = np.argmin(fun_all, axis=1)
+        rows = np.arange(P)
+        return {"x": out["x"][rows, best], "fun": fun_all[rows, best], "x_all": out["x"], "fun_all": fun_all,
+                "status": out["status"], "iters": out["iters"], "evals": out["evals"], "best": best}
 
     def close(self):
         ctx, self._ctx = self._ctx, None

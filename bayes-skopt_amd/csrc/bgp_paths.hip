@@ -14,10 +14,13 @@
 // fp64 VALU work in the shape of fant_col_kernel (bgp_fantasy.hip): one query row per thread, its inputs in registers, tiles of 64
 // features / 64 training points staged in LDS and read as broadcasts.  Every sum has a fixed ascending order, no atomics: the value
 // at (path, row) does not depend on which rows or paths share the call.
+// bgp_paths_minimize minimises every path from its own starts: one workgroup per (start, path) evaluates ONE
+// path at ONE point with all its threads (pm_eval) and carries the projected BFGS of bgp_bfgs.h itself.
 #include <memory>
 
 #include "bgp_common.h"
 #include "bgp_device.h"
+#include "bgp_bfgs.h"
 
 #define PT_TF 64       // features per LDS tile of the feature kernel
 #define PT_TP 64       // training points per LDS tile of the update kernel
@@ -195,6 +198,148 @@ __global__ void __launch_bounds__(256) paths_upd_kernel(const double* __restrict
   }
 }
 
+// ---- the minimiser of a path ----------------------------------------------------------------------------
+#define PM_RS (PG_DMAX + 1)  // stride of a wave's partial sums
+
+struct PmWork {               // LDS of one evaluation
+  double x[PG_DMAX];          // the query point
+  double il[PG_DMAX];         // 1 / length scale
+  double ell[PG_DMAX];        // length scale
+  double tile[PG_NT];         // A w_j sin(arg_j) of a tile of features, then v_i cf fac_i of a tile of training points
+  double red[PG_NW * PM_RS];  // wave partials of the value (column 0) and of the update's gradient (columns 1 ..)
+  double redf[PG_NW * PM_RS]; // wave partials of the feature gradient (columns 1 ..)
+  double f, df[PG_DMAX];
+};
+
+// The path at W.x: f into W.f, df/dx into W.df, by the whole workgroup of PG_NT threads.  Features and training points are taken in
+// tiles of PG_NT: thread j of a tile forms its term of the value (arg_j as paths_feat_kernel forms it: from the phase, fma in
+// ascending k) and leaves the gradient's weight in W.tile; after a barrier lane (t, half) of wave wv owns dimension t over the tile's
+// entries 2 wv + half, + 2 PG_NW, ... (pg_wsum's split), in registers that live across the tiles.  Value: a butterfly inside every
+// wave, then the wave partials in ascending order; gradient: the two halves, then the waves in ascending order.  No atomics, no F- or
+// n-sized row.  Called by every thread; starts with a barrier (W.x may have been written just before); W.f / W.df are visible to
+// every thread on return.
+template <int STAT, int FORM>
+static __device__ __forceinline__ void pm_eval(const double* __restrict__ X, int n, int d, int F, const double* __restrict__ Om,
+                                            const double* __restrict__ Ph, const double* __restrict__ Aw, double c0,
+                                            const double* __restrict__ V, double cst, PmWork& W) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, t = lane & 31, r0 = 2 * wv + (lane >> 5);
+  const bool own = t < d;
+  __syncthreads();
+  const double xl = own ? W.x[t] : 0.0, ill = own ? W.il[t] : 0.0;
+  double val = 0.0, gf = 0.0, gu = 0.0;
+  for (int j0 = 0; j0 < F; j0 += PG_NT) {
+    const int jc = min(PG_NT, F - j0), j = j0 + tid;
+    if (tid < jc) {
+      const double* om = Om + (size_t)j * d;
+      double a = Ph[j];
+      for (int k = 0; k < d; k++) a = fma(W.x[k], om[k], a);
+      const double aw = Aw[j];
+      val = fma(aw, cos(a), val);
+      W.tile[tid] = aw * sin(a);
+    }
+    __syncthreads();
+    if (own)
+      for (int r = r0; r < jc; r += 2 * PG_NW) gf = fma(W.tile[r], Om[(size_t)(j0 + r) * d + t], gf);
+    __syncthreads();  // (the tile is rewritten next)
+  }
+  for (int i0 = 0; i0 < n; i0 += PG_NT) {
+    const int ic = min(PG_NT, n - i0), i = i0 + tid;
+    if (tid < ic) {
+      const double* xi = X + (size_t)i * d;
+      double r2 = 0.0;
+      for (int k = 0; k < d; k++) {
+        const double df = (W.x[k] - xi[k]) * W.il[k];
+        r2 = fma(df, df, r2);
+      }
+      double S, fac;
+      kb_stationary_fac<STAT>(r2, S, fac);
+      const double v = V[i];
+      val = fma(kb_with_constant<FORM>(cst, S), v, val);
+      W.tile[tid] = v * ((FORM == BGP_FORM_PRODUCT) ? cst * fac : fac);
+    }
+    __syncthreads();
+    if (own)
+      for (int r = r0; r < ic; r += 2 * PG_NW) gu = fma(W.tile[r], (xl - X[(size_t)(i0 + r) * d + t]) * ill, gu);
+    __syncthreads();  // (the tile is rewritten next)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o, 64);
+  gf += __shfl_xor(gf, 32, 64);
+  gu += __shfl_xor(gu, 32, 64);
+  if (lane == 0) W.red[wv * PM_RS] = val;
+  if (lane < d) {
+    W.redf[wv * PM_RS + 1 + lane] = gf;
+    W.red[wv * PM_RS + 1 + lane] = gu;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < PG_NW; w++) s += W.red[w * PM_RS];
+    W.f = s + c0;
+  }
+  if (tid < d) {
+    double sf = 0.0, su = 0.0;
+    for (int w = 0; w < PG_NW; w++) sf += W.redf[w * PM_RS + 1 + tid], su += W.red[w * PM_RS + 1 + tid];
+    W.df[tid] = -sf + su / W.ell[tid];
+  }
+  __syncthreads();
+}
+
+// One workgroup per (start, path): blockIdx.x = start, blockIdx.y = path; item o = path * S + start of every array.  The objective
+// is the path itself (normalised-y units).  f_out / g_out: the evaluator's own values at X_out; where the search's last evaluation
+// was not at X_out (a failed line search) one closing evaluation is made and counted.
+template <int STAT, int FORM>
+__global__ void __launch_bounds__(PG_NT) pm_min_kernel(const double* __restrict__ X, int n, int d, int F,
+                                                       const double* __restrict__ H, const double* __restrict__ Om,
+                                                       const double* __restrict__ Ph, const double* __restrict__ Aw,
+                                                       const double* __restrict__ C0, const double* __restrict__ V,
+                                                       const double* __restrict__ X0, const double* __restrict__ lo_,
+                                                       const double* __restrict__ hi_, double gtol, int max_iter,
+                                                       double* __restrict__ X_out, double* __restrict__ f_out,
+                                                       double* __restrict__ g_out, int* __restrict__ iters, int* __restrict__ evals,
+                                                       int* __restrict__ status) {
+#pragma clang fp contract(off)
+  __shared__ PmWork W;
+  __shared__ PgBfgs Bf;
+  const int tid = threadIdx.x, p = blockIdx.y;
+  const size_t o = (size_t)p * gridDim.x + blockIdx.x;
+  const double* h = H + (size_t)p * (d + 2);
+  if (tid < d) {
+    Bf.lo[tid] = lo_[tid];
+    Bf.hi[tid] = hi_[tid];
+    double v = X0[o * d + tid];
+    v = v < Bf.lo[tid] ? Bf.lo[tid] : (v > Bf.hi[tid] ? Bf.hi[tid] : v);
+    Bf.x[tid] = v;
+    W.x[tid] = v;
+    W.ell[tid] = exp(h[1 + tid]);
+    W.il[tid] = 1.0 / W.ell[tid];
+  }
+  const double cst = exp(h[0]), c0 = C0[p];
+  const double *Omp = Om + (size_t)p * F * d, *Php = Ph + (size_t)p * F, *Awp = Aw + (size_t)p * F, *Vp = V + (size_t)p * n;
+  auto eval = [&] { pm_eval<STAT, FORM>(X, n, d, F, Omp, Php, Awp, c0, Vp, cst, W); };
+  int it, nev;
+  const int st = pg_bfgs(Bf, W.x, d, gtol, max_iter, eval, [&] { return W.f; }, [&](int t) { return W.df[t]; }, it, nev);
+  bool there = true;  // the last evaluation was made at the end point
+  for (int t = 0; t < d; t++) there = there && W.x[t] == Bf.x[t];
+  if (!there) {
+    __syncthreads();
+    if (tid < d) W.x[tid] = Bf.x[tid];
+    eval();
+    nev++;
+  }
+  if (tid < d) {
+    X_out[o * d + tid] = Bf.x[tid];
+    if (g_out) g_out[o * d + tid] = W.df[tid];
+  }
+  if (tid == 0) {
+    f_out[o] = W.f;
+    iters[o] = it;
+    evals[o] = nev;
+    status[o] = st;
+  }
+}
+
 static int paths_launch_feat(bgp_ctx* c, const bgp_paths_state* s, const double* dXq, int m, double* out, size_t so, double* dout) {
   const dim3 grid((m + 255) / 256, s->P);
   if (dout)
@@ -356,6 +501,75 @@ extern "C" int bgp_paths_eval(bgp_ctx* c, int m, const double* Xq, double* out, 
     return BGP_ERR_INVALID;
   }
   return post_call(c, [&] { return paths_eval_run(c, m, Xq, out, dout); });
+}
+
+static int paths_min_run(bgp_ctx* c, int S, const double* X0, const double* lo, const double* hi, double gtol, int max_iter,
+                         double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status) {
+  BGP_HIP(hipSetDevice(c->device));
+  const bgp_paths_state* s = c->paths;
+  const int P = s->P, d = s->d, n = s->n;
+  // chunks of starts: staged starts, end points, values, gradients and counters of P sc items under the budget of bgp_paths_eval
+  size_t sc = std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)P * (3 + 3 * (size_t)d)));
+  sc = std::min(sc, (size_t)S);
+  const size_t Ps = (size_t)P * sc;
+  double *dX0, *dXo, *dlo, *dhi, *df, *dg = nullptr;
+  int *dit, *dev, *dst;
+  BgpScratch live(c);
+  int rc = live.carve([&](BgpCarve& k) {
+    dX0 = k.take<double>(Ps * d);
+    dXo = k.take<double>(Ps * d);
+    dlo = k.take<double>(d);
+    dhi = k.take<double>(d);
+    df = k.take<double>(Ps);
+    if (g_out) dg = k.take<double>(Ps * d);
+    dit = k.take<int>(Ps);
+    dev = k.take<int>(Ps);
+    dst = k.take<int>(Ps);
+  });
+  if (rc) return rc;
+  hipStream_t q = c->stream;
+  BGP_HIP(bgp_memcpy_async(dlo, lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, q));
+  BGP_HIP(bgp_memcpy_async(dhi, hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, q));
+  for (size_t s0 = 0; s0 < (size_t)S; s0 += sc) {
+    const int ss = (int)std::min(sc, (size_t)S - s0);  // (the chunk's items are packed: item = path * ss + start)
+    const size_t w1 = (size_t)ss * sizeof(double), wd = w1 * d, wi = (size_t)ss * sizeof(int);
+    BGP_HIP(bgp_memcpy2d_async(dX0, wd, X0 + s0 * d, (size_t)S * d * sizeof(double), wd, P, hipMemcpyHostToDevice, q));
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((pm_min_kernel<S, F>), dim3(ss, P), dim3(PG_NT), 0, q, s->dX, n, d, s->F, s->dH, s->dOm, s->dPh,
+                                   s->dAw, s->dC0, s->dV, dX0, dlo, dhi, gtol, max_iter, dXo, df, dg, dit, dev, dst));
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(bgp_memcpy2d_async(X_out + s0 * d, (size_t)S * d * sizeof(double), dXo, wd, wd, P, hipMemcpyDeviceToHost, q));
+    BGP_HIP(bgp_memcpy2d_async(f_out + s0, (size_t)S * sizeof(double), df, w1, w1, P, hipMemcpyDeviceToHost, q));
+    if (g_out) BGP_HIP(bgp_memcpy2d_async(g_out + s0 * d, (size_t)S * d * sizeof(double), dg, wd, wd, P, hipMemcpyDeviceToHost, q));
+    BGP_HIP(bgp_memcpy2d_async(iters + s0, (size_t)S * sizeof(int), dit, wi, wi, P, hipMemcpyDeviceToHost, q));
+    BGP_HIP(bgp_memcpy2d_async(evals + s0, (size_t)S * sizeof(int), dev, wi, wi, P, hipMemcpyDeviceToHost, q));
+    BGP_HIP(bgp_memcpy2d_async(status + s0, (size_t)S * sizeof(int), dst, wi, wi, P, hipMemcpyDeviceToHost, q));
+    BGP_HIP(bgp_stream_sync(q));  // (the next chunk reuses the buffers)
+  }
+  return BGP_OK;
+}
+
+extern "C" int bgp_paths_minimize(bgp_ctx* c, int S, const double* X0, const double* lo, const double* hi, double gtol,
+                                  int max_iter, double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status) {
+  BGP_REQUIRE_IDLE(c, "bgp_paths_minimize");
+  if (!c) {
+    bgp_set_error("bgp_paths_minimize: NULL ctx");
+    return BGP_ERR_INVALID;
+  }
+  if (!c->paths) {
+    bgp_set_error("bgp_paths_minimize: no paths state (call bgp_paths_begin first)");
+    return BGP_ERR_STATE;
+  }
+  if (!X0 || !lo || !hi || !X_out || !f_out || !iters || !evals || !status || S < 1 || max_iter < 0 || !(gtol >= 0.0)) {
+    bgp_set_error("bgp_paths_minimize: bad argument (S >= 1, max_iter >= 0, gtol >= 0)");
+    return BGP_ERR_INVALID;
+  }
+  for (int t = 0; t < c->paths->d; t++)
+    if (!(lo[t] <= hi[t])) {
+      bgp_set_error("bgp_paths_minimize: empty box in dimension %d", t);
+      return BGP_ERR_INVALID;
+    }
+  return post_call(c, [&] { return paths_min_run(c, S, X0, lo, hi, gtol, max_iter, X_out, f_out, g_out, iters, evals, status); });
 }
 
 extern "C" int bgp_paths_end(bgp_ctx* c) {

@@ -18,14 +18,11 @@
 // does not depend on what shares its launch.
 #include "bgp_common.h"
 #include "bgp_device.h"
+#include "bgp_bfgs.h"
 
-#define PG_NT 512                 // threads of a workgroup
-#define PG_NW (PG_NT / 64)        // its waves
-#define PG_DMAX 32                // input dimensions (the limit of the fantasy fast path): a dimension per lane of half a wave
+// (PG_NT threads in PG_NW waves, PG_DMAX dimensions, the line-search cap PG_LS_MAX: bgp_bfgs.h)
 #define PG_NLDS 3072              // training points whose k / g rows fit the workgroup's LDS (2 x 24 KB); beyond: device scratch rows
 #define PG_RS (PG_DMAX + 1)       // stride of a wave's partial sums
-#define PG_LS_MAX 30              // cap of the backtracking line search
-#define PG_HS (PG_DMAX + 1)       // row stride of the inverse-Hessian approximation in LDS (32 x 33 doubles: 8.25 KB)
 
 struct PgWork {                   // LDS of one evaluation
   double x[PG_DMAX];              // the query point
@@ -196,8 +193,8 @@ static __device__ __forceinline__ double pg_gradient(const PgWork& W, int t, dou
   return g;
 }
 
-// One workgroup per start: projected BFGS (dense inverse Hessian in LDS, active set read off the projected gradient, Armijo
-// backtracking along the projected path).  status 0: |projected gradient|_inf <= gtol; 1: max_iter reached; 2: no decrease found.
+// One workgroup per start: the projected BFGS of bgp_bfgs.h on pg_eval.  status 0: |projected gradient|_inf <= gtol; 1: max_iter
+// reached; 2: no decrease found.
 template <int STAT, int FORM>
 __global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict__ X, int n, int d, int npad,
                                                        const double* __restrict__ alpha, const double* __restrict__ Kinv,
@@ -210,138 +207,31 @@ __global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict_
 #pragma clang fp contract(off)
   extern __shared__ double pg_dyn[];
   __shared__ PgWork W;
-  __shared__ double Hm[PG_DMAX * PG_HS];
-  __shared__ double x[PG_DMAX], g[PG_DMAX], p[PG_DMAX], sv[PG_DMAX], yv[PG_DMAX], Hy[PG_DMAX], lo[PG_DMAX], hi[PG_DMAX];
-  __shared__ int act[PG_DMAX];
+  __shared__ PgBfgs Bf;
   const int tid = threadIdx.x, s = blockIdx.x;
   const bool wantv = kappa != 0.0;
   if (tid < d) {
-    lo[tid] = lo_[tid];
-    hi[tid] = hi_[tid];
+    Bf.lo[tid] = lo_[tid];
+    Bf.hi[tid] = hi_[tid];
     double v = X0[(size_t)s * d + tid];
-    v = v < lo[tid] ? lo[tid] : (v > hi[tid] ? hi[tid] : v);
-    x[tid] = v;
+    v = v < Bf.lo[tid] ? Bf.lo[tid] : (v > Bf.hi[tid] ? Bf.hi[tid] : v);
+    Bf.x[tid] = v;
     W.x[tid] = v;
     W.il[tid] = 1.0 / exp(h[1 + tid]);
   }
-  for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
   const double cst = exp(h[0]);
   const double kdiag = kb_with_constant<FORM>(cst, 1.0) + exp(h[d + 1]);
   double *kb, *gb;
   pg_rows(pg_dyn, scratch, n, npad, s, kb, gb);
-  pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W);
-  double f = pg_objective(W, y_mean, y_std, kappa);
-  if (tid < d) g[tid] = pg_gradient(W, tid, y_std, kappa);
-  __syncthreads();
-  // (every thread follows the same control flow: all decisions are taken on values read from LDS)
-  int st = 1, it = 0, nev = 1;
-  bool fresh = true;  // Hm is the identity
-  for (; it < max_iter; it++) {
-    if (tid < d) act[tid] = (x[tid] <= lo[tid] && g[tid] > 0.0) || (x[tid] >= hi[tid] && g[tid] < 0.0);
-    __syncthreads();
-    double pgn = 0.0;
-    for (int t = 0; t < d; t++)
-      if (!act[t]) pgn = fmax(pgn, fabs(g[t]));
-    if (pgn <= gtol) {
-      st = 0;
-      break;
-    }
-    if (tid < d) {
-      double pt = 0.0;
-      if (!act[tid])
-        for (int u = 0; u < d; u++)
-          if (!act[u]) pt = fma(-Hm[tid * PG_HS + u], g[u], pt);
-      p[tid] = pt;
-    }
-    __syncthreads();
-    double gp = 0.0, pn = 0.0;
-    for (int t = 0; t < d; t++) gp = fma(g[t], p[t], gp), pn = fma(p[t], p[t], pn);
-    if (!(gp < 0.0)) {  // not a descent direction: forget the curvature, steepest descent on the free variables
-      __syncthreads();
-      for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
-      if (tid < d) p[tid] = act[tid] ? 0.0 : -g[tid];
-      fresh = true;
-      __syncthreads();
-      gp = 0.0, pn = 0.0;
-      for (int t = 0; t < d; t++) gp = fma(g[t], p[t], gp), pn = fma(p[t], p[t], pn);
-    }
-    double a = 1.0;
-    if (fresh) {
-      const double r = 1.0 / sqrt(pn);
-      a = r < 1.0 ? r : 1.0;
-    }
-    bool accepted = false;
-    double fn = f;
-    for (int ls = 0; ls < PG_LS_MAX; ls++) {
-      if (tid < d) {
-        double v = fma(a, p[tid], x[tid]);
-        v = v < lo[tid] ? lo[tid] : (v > hi[tid] ? hi[tid] : v);
-        W.x[tid] = v;
-      }
-      pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W);
-      nev++;
-      fn = pg_objective(W, y_mean, y_std, kappa);
-      double dd = 0.0;  // the decrease the gradient predicts along the projected step
-      for (int t = 0; t < d; t++) dd = fma(g[t], W.x[t] - x[t], dd);
-      if (dd < 0.0 && fn <= f + 1e-4 * dd) {
-        accepted = true;
-        break;
-      }
-      a *= 0.5;
-      __syncthreads();  // (W.x is rewritten next)
-    }
-    if (!accepted) {
-      if (!fresh) {  // once more from this iterate along the steepest descent (counts as an iteration)
-        __syncthreads();
-        for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? 1.0 : 0.0;
-        fresh = true;
-        __syncthreads();
-        continue;
-      }
-      st = 2;
-      break;
-    }
-    __syncthreads();
-    if (tid < d) {
-      const double gn = pg_gradient(W, tid, y_std, kappa);
-      sv[tid] = W.x[tid] - x[tid];
-      yv[tid] = gn - g[tid];
-      x[tid] = W.x[tid];
-      g[tid] = gn;
-    }
-    f = fn;
-    __syncthreads();
-    double sy = 0.0, yy = 0.0, ss = 0.0;
-    for (int t = 0; t < d; t++) sy = fma(sv[t], yv[t], sy), yy = fma(yv[t], yv[t], yy), ss = fma(sv[t], sv[t], ss);
-    if (sy > 1e-10 * sqrt(ss * yy)) {
-      if (fresh) {  // the first pair scales the identity
-        const double sc = sy / yy;
-        for (int idx = tid; idx < PG_DMAX * PG_HS; idx += PG_NT) Hm[idx] = (idx / PG_HS == idx % PG_HS) ? sc : 0.0;
-        __syncthreads();
-      }
-      if (tid < d) {
-        double v = 0.0;
-        for (int u = 0; u < d; u++) v = fma(Hm[tid * PG_HS + u], yv[u], v);
-        Hy[tid] = v;
-      }
-      __syncthreads();
-      double yHy = 0.0;
-      for (int t = 0; t < d; t++) yHy = fma(yv[t], Hy[t], yHy);
-      const double rho = 1.0 / sy, c2 = (sy + yHy) * rho * rho;
-      for (int idx = tid; idx < d * d; idx += PG_NT) {
-        const int t = idx / d, u = idx - t * d;
-        Hm[t * PG_HS + u] = Hm[t * PG_HS + u] + (c2 * (sv[t] * sv[u]) - rho * (Hy[t] * sv[u] + sv[t] * Hy[u]));
-      }
-      fresh = false;
-      __syncthreads();
-    }
-  }
+  int it, nev;
+  const int st = pg_bfgs(
+      Bf, W.x, d, gtol, max_iter, [&] { pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, wantv, kb, gb, W); },
+      [&] { return pg_objective(W, y_mean, y_std, kappa); }, [&](int t) { return pg_gradient(W, t, y_std, kappa); }, it, nev);
   // the moments at the end point, variance included: the bits bgp_predict_grad_batch returns there
-  __syncthreads();
-  if (tid < d) W.x[tid] = x[tid];
+  if (tid < d) W.x[tid] = Bf.x[tid];
   pg_eval<STAT, FORM>(X, n, d, alpha, Kinv, npad, cst, kdiag, true, kb, gb, W);
   nev++;
-  if (tid < d) X_out[(size_t)s * d + tid] = x[tid];
+  if (tid < d) X_out[(size_t)s * d + tid] = Bf.x[tid];
   if (tid == 0) {
     mean_out[s] = W.mean;
     var_out[s] = W.var;

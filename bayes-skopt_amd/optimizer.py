@@ -6,6 +6,7 @@ function over ``n_points`` random candidates with the device predict / PVRS kern
 The post-hoc diagnostics ``probability_of_optimality`` / ``expected_optimality_gap`` /
 ``optimum_intervals`` (``bask/optimizer.py:447-689``) run on the device ``sample_y``.
 """
+import sys
 import warnings
 
 import numpy as np
@@ -16,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi
+from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi, inverse_unrounded
 
 __all__ = ["Optimizer"]
 
@@ -305,17 +306,64 @@ class Optimizer:
         cdf = np.asarray(self.probability_of_optimality(list(grid), **kw), dtype=np.float64)
         return float(np.sum(np.diff(cdf) * grid[1:]))
 
+    def _optimum_samples_transformed(self, n_samples, only_mean, n_features, n_candidates, n_starts, random_state):
+        """(locations (n_samples, d) in the transformed unit box, values (n_samples,) in y units) of ``optimum_samples``."""
+        if self.space.is_partly_categorical:
+            raise ValueError("optimum_samples does not support any categorical values")
+        rng = check_random_state(random_state)
+        with self.gp.sample_paths(n_paths=n_samples, sample_mean=only_mean, n_features=n_features, random_state=rng) as paths:
+            out = paths.minimize(bounds=(0.0, 1.0), n_candidates=n_candidates, n_starts=n_starts, random_state=rng)
+        return out["x"], out["fun"]
+
+    def optimum_samples(self, n_samples=200, only_mean=True, n_features=1024, n_candidates=2000, n_starts=8, random_state=None):
+        """Samples of the optimum: ``n_samples`` posterior function draws (``BayesGPR.sample_paths``; ``only_mean``: all of the
+        median GP, otherwise one chain row each) and the continuous minimiser of every draw over the whole space, searched on
+        the device from the draw's ``n_starts`` lowest of ``n_candidates`` uniform points (``PosteriorPaths.minimize``, DESIGN.md
+        section 15).  ONE generator made from ``random_state`` serves ``sample_paths`` first, then the candidates.  Returns
+        ``(X_opt, values)``: X_opt (n_samples, d) in the original space, un-rounded as ``expected_optimum``'s point, and the
+        draws' minima (n_samples,) in y units.  ``ValueError`` where ``sample_paths`` raises it (warped inputs, generic kernel
+        trees, more than 32 dimensions) and for partly categorical spaces."""
+        Xt, values = self._optimum_samples_transformed(n_samples, only_mean, n_features, n_candidates, n_starts, random_state)
+        return np.array([inverse_unrounded(self.space, xt) for xt in Xt]), values
+
     def optimum_intervals(self, hdi_prob=0.95, multimodal=True, opt_samples=200, space_samples=500, only_mean=True,
-                          random_state=None):
+                          random_state=None, method="argmin"):
         """Highest density intervals of the optimum's location per dimension by Thompson sampling
-        (``bask/optimizer.py:622-689``); ``utils.hdi`` restates the two arviz estimators."""
+        (``bask/optimizer.py:622-689``); ``utils.hdi`` restates the two arviz estimators.  ``method="argmin"`` (default): the
+        reference's samples, the argmin row of every joint draw over ``space_samples`` random points.  ``method="pathwise"``:
+        the continuous minimisers of ``opt_samples`` function draws (``optimum_samples`` with ``space_samples`` candidates per
+        draw); where the pathwise draws cannot run (warped inputs, generic kernel trees, more than 32 dimensions) the call takes
+        ``"argmin"`` and says so once on stderr."""
+        if method not in ("argmin", "pathwise"):
+            raise ValueError(f"method must be 'argmin' or 'pathwise', got {method!r}")
         if self.space.is_partly_categorical:
             raise NotImplementedError("Highest density interval not implemented for categorical parameters.")
+        if method == "pathwise":
+            why = self.gp._pathwise_obstacle()
+            if why is None:
+                X_opt, _ = self._optimum_samples_transformed(opt_samples, only_mean, 1024, space_samples,
+                                                             min(8, space_samples), random_state)
+                return self._intervals_of(X_opt, hdi_prob, multimodal)
+            _intervals_tell_once(why)
         X = self.space.transform(self.space.rvs(n_samples=space_samples, random_state=random_state))
         optimum_samples = self.gp.sample_y(X, sample_mean=only_mean, n_samples=opt_samples, random_state=random_state)
         X_opt = X[np.argmin(optimum_samples, axis=0)]
+        return self._intervals_of(X_opt, hdi_prob, multimodal)
+
+    def _intervals_of(self, X_opt, hdi_prob, multimodal):
         intervals = []
         for i, col in enumerate(X_opt.T):
             raw_interval = hdi(col, hdi_prob=hdi_prob, multimodal=multimodal)
             intervals.append(self.space.dimensions[i].inverse_transform(raw_interval))
         return intervals
+
+
+_intervals_told = []
+
+
+def _intervals_tell_once(why):
+    """One line on stderr, once per process: optimum_intervals(method="pathwise") asked for where the paths cannot run."""
+    if not _intervals_told:
+        _intervals_told.append(True)
+        print("[bayes_skopt_amd] optimum_intervals(method='pathwise'): not available for %s; taking method='argmin'" % why,
+              file=sys.stderr, flush=True)

@@ -191,6 +191,15 @@ def _host_optimum(res, kappa, n_random_starts, random_state):
     return [float(v) for v in best_x], float(best_fun)
 
 
+def inverse_unrounded(space, xt):
+    """A point of the transformed unit box in the original space, un-rounded: integer dimensions by their affine map
+    (``expected_minimum`` returns un-rounded values too), every other dimension by its own inverse transform."""
+    from .space import Integer
+
+    return [float(xt[j] * (dim.high - dim.low) + dim.low) if isinstance(dim, Integer) else float(dim.inverse_transform(xt[j]))
+            for j, dim in enumerate(space.dimensions)]
+
+
 def expected_optimum(res, kappa=0.0, n_random_starts=20, random_state=None, gtol=1e-5, max_iter=200):
     """Minimum of ``mean + kappa std`` of the surrogate (``kappa = 0``: the predictive mean, as ``expected_minimum``; ``kappa``
     > 0: an upper confidence bound of the optimum), searched on the device: every start -- ``[res.x] + space.rvs(n_random_starts,
@@ -202,8 +211,6 @@ def expected_optimum(res, kappa=0.0, n_random_starts=20, random_state=None, gtol
     ``x_transformed`` with their normalised ``mean`` / ``var``, ``best`` and ``path``.  Warped inputs, generic kernel trees and more than 32 dimensions take the host
     loop (``expected_minimum``, or the same loop over ``predict(return_std=True)``), ``path == "host"``, and say so once."""
     from sklearn.utils import check_random_state
-
-    from .space import Integer
 
     space = res.space
     if space.is_partly_categorical:
@@ -226,9 +233,7 @@ def expected_optimum(res, kappa=0.0, n_random_starts=20, random_state=None, gtol
     y_mean, y_std = float(np.ravel(reg.y_train_mean_)[0]), float(np.ravel(reg.y_train_std_)[0])
     fun = y_mean + y_std * out["mean"] + kappa * (y_std * np.sqrt(out["var"]))
     best = int(np.argmin(fun))
-    xt = out["x"][best]
-    x = [float(xt[j] * (dim.high - dim.low) + dim.low) if isinstance(dim, Integer) else float(dim.inverse_transform(xt[j]))
-         for j, dim in enumerate(space.dimensions)]
+    x = inverse_unrounded(space, out["x"][best])
     info = {"path": "device", "status": out["status"], "iters": out["iters"], "evals": out["evals"], "fun": fun,
             "x_transformed": out["x"], "mean": out["mean"], "var": out["var"], "best": best}
     return x, float(fun[best]), info

@@ -270,12 +270,26 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
  *   value at (path, row) does not depend on which rows or paths share the call.  BGP_ERR_STATE without a state.
  * bgp_paths_end drops the state; bgp_ctx_update_data and bgp_ctx_destroy drop it too.
  * bgp_paths_stats: out[0] = begins, out[1] = evals run on this context.
+ * bgp_paths_minimize: minimise every open path over the box [lo, hi] (d doubles each) from its OWN S starts,
+ *   X0 P*S*d path-major, clipped into the box.  The objective is the path itself (normalised-y units).  ONE launch per chunk of
+ *   starts, one workgroup per (start, path): a whole-workgroup evaluator of one path at one point (the identities above, every
+ *   reduction in a fixed order, no atomics) drives the projected BFGS of bgp_minimize_starts -- the same device function -- with
+ *   Armijo backtracking (at most max_iter iterations of at most 30 trial points).  Per (path, start), item p*S + s: X_out (inside
+ *   the box exactly), f_out and g_out (P*S*d, may be NULL): the search's own evaluator at X_out; iters; evals (evaluations of the
+ *   path, a closing one at X_out included where the last trial point was not X_out); status -- 0: the inf-norm of the projected
+ *   gradient is <= gtol, 1: max_iter reached, 2: the line search found no decrease.  max_iter = 0 is a pure evaluation of the clipped
+ *   starts (iters 0, evals 1).  A (path, start) result does not depend on what shares the call.  S >= 1, max_iter >= 0, gtol >= 0
+ *   (BGP_ERR_INVALID); BGP_ERR_STATE without a state.  Does not read the resident posteriors.  The staged outputs are chunked over S
+ *   under the 2^24-double budget of bgp_paths_eval.
+ *   Replaces: the argmin over 500 random rows of a joint draw in Optimizer.optimum_intervals (bask/optimizer.py:622-689).
  */
 int bgp_paths_begin(bgp_ctx* ctx, int P, const int* pidx, const double* h_kernel, const double* s2, int F,
                     const double* omega, const double* phase, const double* w, const double* eps);
 int bgp_paths_eval(bgp_ctx* ctx, int m, const double* Xq, double* out, double* dout);
 int bgp_paths_end(bgp_ctx* ctx);
 int bgp_paths_stats(bgp_ctx* ctx, long long* out2);
+int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, const double* hi, double gtol, int max_iter,
+                       double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status);
 
 /*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
