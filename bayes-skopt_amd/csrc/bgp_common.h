@@ -164,8 +164,10 @@ struct bgp_ctx {
   BgpDev<double> dh;         // max_batch * (d+2)       canonical hyper-parameters
   BgpDev<double> dlml;       // max_batch
   BgpDev<int> dstatus;       // max_batch
-  // resident posteriors (K^-1 full symmetric npad x npad each, alpha = K^-1 y)
+  // resident posteriors (K^-1 full symmetric npad x npad each, alpha = K^-1 y; L^-1 lower triangular with zeros above, for
+  // the predictive covariances that a Cholesky factorisation reads: bgp_sample_y, bgp_sample_y_batch)
   BgpDev<double> dKinv;
+  BgpDev<double> dLinv;
   BgpDev<double> dalpha_sol;
   // resident posterior state
   int post_B = 0;            // number of resident posteriors (0 = none)
@@ -428,9 +430,10 @@ void bgp_free_child(bgp_ctx* ctx);
 // make the matrix workspace at least `doubles` large (and the per-item side buffers consistent)
 int bgp_grow_workspace(bgp_ctx* ctx, size_t doubles);
 // posterior build on the augmented matrices; use_alpha == 0 drops alpha_diag (PVRS quirk).  Kgram != nullptr: the B kernel
-// matrices come from the host (n x n each, bgp_gram.hip) instead of the device Gram build, h is not read
+// matrices come from the host (n x n each, bgp_gram.hip) instead of the device Gram build, h is not read.  want_Linv: L^-1
+// stays resident beside K^-1 (the draws read it; the LML gradient does not)
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
-                        double* lml, int* status, const double* Kgram = nullptr);
+                        double* lml, int* status, const double* Kgram = nullptr, bool want_Linv = true);
 // host kernel matrices -> working matrices (bgp_gram.hip)
 int bgp_gram_load(bgp_ctx* c, int nb, const double* K, int augmented, int use_alpha);
 

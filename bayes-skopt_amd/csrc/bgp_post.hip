@@ -12,7 +12,7 @@
 //   K_* = k(Xq, X)  (tiled cross-kernel build);  mean = K_* alpha;
 //   var = k_** - rowsum((K_* K^-1) o K_*)   -- one NT tile GEMM on the fp64 MFMA with the row-dot
 //   fused into its epilogue (K^-1 symmetric, so K_* K^-1 = K_* (K^-1)^T is an NT product);
-//   cov = K_** - (K_* K^-1) K_*^T.
+//   cov = K_** - (K_* K^-1) K_*^T for predict(return_cov); K_** - (K_* L^-T)(K_* L^-T)^T where a Cholesky reads it (the draws).
 #include "bgp_common.h"
 #include "bgp_device.h"
 #include "bgp_gemm.h"
@@ -33,17 +33,20 @@ __global__ void aug_init_kernel(double* __restrict__ Kbuf, double* __restrict__ 
 // K^-1 (full symmetric npad x npad) and alpha out of the augmented workspace.
 __global__ void __launch_bounds__(256) extract_kinv_kernel(const double* __restrict__ Kbuf,
                                                             const double* __restrict__ yw,
-                                                            double* __restrict__ Kinv, double* __restrict__ alpha,
-                                                            int npad, int boff) {
+                                                            double* __restrict__ Kinv, double* __restrict__ Linv,
+                                                            double* __restrict__ alpha, int npad, int boff) {
   const int b = blockIdx.y;
   const size_t ld = 2 * (size_t)npad;
   const double* M = Kbuf + (size_t)b * ld * ld;
   double* out = Kinv + (size_t)(boff + b) * npad * npad;
+  double* outL = Linv ? Linv + (size_t)(boff + b) * npad * npad : nullptr;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (size_t)npad * npad;
        idx += (size_t)gridDim.x * blockDim.x) {
     const int i = (int)(idx / npad), j = (int)(idx - (size_t)i * npad);
     const int hi = i > j ? i : j, lo = i > j ? j : i;
     out[idx] = -M[(size_t)(npad + hi) * ld + npad + lo];
+    // the bottom-left block of the augmented factor is [I] L^-T: its transpose is L^-1
+    if (outL) outL[idx] = j <= i ? M[(size_t)(npad + j) * ld + i] : 0.0;
   }
   if (blockIdx.x == 0)
     for (int i = threadIdx.x; i < npad; i += blockDim.x)
@@ -160,20 +163,21 @@ static int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int ro
 // ------------------------------------------------------------------------------------------
 // posterior build
 // ------------------------------------------------------------------------------------------
-static int ensure_resident(bgp_ctx* c, int B) {
+static int ensure_resident(bgp_ctx* c, int B, bool want_Linv) {
   // K^-1 needs B npad^2 doubles, alpha B npad: the two capacities are tracked separately (a context reused through
   // bgp_ctx_update_data may see n shrink and B grow: B=1 at npad=1024 and B=64 at npad=128 need the same K^-1
   // bytes but 8x the alpha bytes)
-  const int rc = c->dKinv.ensure((size_t)B * c->npad * c->npad);
+  int rc = c->dKinv.ensure((size_t)B * c->npad * c->npad);
+  if (!rc && want_Linv) rc = c->dLinv.ensure((size_t)B * c->npad * c->npad);
   return rc ? rc : c->dalpha_sol.ensure((size_t)B * c->npad);
 }
 
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
-                        double* lml, int* status, const double* Kgram) {
+                        double* lml, int* status, const double* Kgram, bool want_Linv) {
   const int npad = c->npad, n = c->n;
   const size_t p = c->d + 2;
   const size_t ld = 2 * (size_t)npad;
-  int rc = ensure_resident(c, B);
+  int rc = ensure_resident(c, B, want_Linv);
   if (rc) return rc;
   // augmented matrices are 4x the LML workspace per item
   int chunk = (int)(c->dK.cap / (ld * ld));
@@ -198,7 +202,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
     rc = bgp_launch_cholesky(c, nb, 1);
     if (rc) return rc;
     hipLaunchKernelGGL(extract_kinv_kernel, dim3(256, nb), dim3(256), 0, c->stream, c->dK, c->dyw, c->dKinv,
-                       c->dalpha_sol, npad, off);
+                       want_Linv ? (double*)c->dLinv : nullptr, c->dalpha_sol, npad, off);
     BGP_HIP(hipGetLastError());
     if (lml) BGP_HIP(bgp_memcpy_async(lml + off, c->dlml, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (status) BGP_HIP(bgp_memcpy_async(status + off, c->dstatus, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -314,10 +318,14 @@ struct PostKss {
   const double* host = nullptr;                // uploaded: nb host matrices of m x m with their diagonal, zero padded here
 };
 // The predictive covariance of nb items: P = K_* K^-1 (item b's K^-1 is Kinv[pidxB ? pidxB[b] : b]), K_** into dC, then
-// dC -= P K_*^T -- mode 2: the whole square (every element is read and written by the same lane), mode 1: the lower tiles only (all a
+// dC -= P K_*^T -- or, with ``factor``, Kinv holds L^-1 instead: P = K_* L^-T, dC -= P P^T.  The product with the explicit
+// inverse carries kappa(K) eps |K^-1| into the covariance, which a Cholesky factorisation of it then amplifies by the
+// covariance's own condition number (16 tol on the draws at kappa 7e4 / 2e5); the factor's inverse carries sqrt(kappa) and
+// the subtraction is a difference of squares.  The draws use the factor; predict(return_cov) keeps the inverse, so that its
+// diagonal stays the variance's own arithmetic.  Mode 2: the whole square (every element is read and written by the same lane), mode 1: the lower tiles only (all a
 // factorisation reads).  Both products on the LDS-DMA ring (gemm4_kernel).  cov != NULL: the nb matrices go back to the host.
 static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* Kinv, const int* pidxB, double* dP,
-                    const PostKss& kss, int mode, double* dC, double* cov = nullptr) {
+                    const PostKss& kss, int mode, double* dC, double* cov = nullptr, bool factor = false) {
   const int npad = c->npad, d = c->d, mpad = pad128(m);
   const size_t sKs = (size_t)mpad * npad, sC = (size_t)mpad * mpad;
   bgp_launch_gemm4(c->stream, 0, dKs, Kinv, npad, mpad, npad, npad, dP, npad, nb, sKs, (size_t)npad * npad, sKs, pidxB);
@@ -331,7 +339,7 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
     else
       hipLaunchKernelGGL(add_diag_batch_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dC, mpad, sC, m, kss.dH, d);
   }
-  bgp_launch_gemm4(c->stream, mode, dP, dKs, npad, mpad, mpad, npad, dC, mpad, nb, sKs, sKs, sC, nullptr);
+  bgp_launch_gemm4(c->stream, mode, dP, factor ? dP : dKs, npad, mpad, mpad, npad, dC, mpad, nb, sKs, sKs, sC, nullptr);
   BGP_HIP(hipGetLastError());
   for (int b = 0; cov && b < nb; b++) BGP_HIP(rows_down(c, cov + (size_t)b * m * m, dC + (size_t)b * sC, m, mpad, m));
   return BGP_OK;
@@ -809,7 +817,7 @@ extern "C" int bgp_lml_grad_batch(bgp_ctx* c, int B, const double* h, double* lm
     c->post_B = 0;
     const size_t p = c->d + 2;
     std::vector<int> st(B, 0);
-    BGP_TRY(bgp_posterior_build(c, B, h, 1, nullptr, nullptr, nullptr, lml, st.data()));
+    BGP_TRY(bgp_posterior_build(c, B, h, 1, nullptr, nullptr, nullptr, lml, st.data(), nullptr, false));
     c->post_B = 0;  // the resident K^-1 belong to a gradient evaluation, not to a posterior
     const int ntiles = c->nblk * (c->nblk + 1) / 2;
     double *dgrad, *dH, *dgpart;
@@ -1053,7 +1061,7 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
       dZ = s.take<double>((size_t)rpad * mpad);
       dO = s.take<double>((size_t)rpad * mpad);
     }));
-    const double* Kinv = c->dKinv + (size_t)b * npad * npad;
+    const double* Linv = c->dLinv + (size_t)b * npad * npad;
     const double* al = c->dalpha_sol + (size_t)b * npad;
     BGP_TRY(post_stage_queries(c, dXq, Xq, m));
     BGP_HIP(bgp_memcpy_async(dhk, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1063,9 +1071,9 @@ extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, co
     BGP_TRY(bgp_launch_kcross(c, dhk, m, dXq, n, c->dXeff, dKs, npad));
     hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, 1), dim3(256), 0, c->stream, dKs, npad, (size_t)0, al,
                        (size_t)0, (const int*)nullptr, n, m, dmean, (size_t)0);
-    // cov = K_** - P K_*^T in the child's matrix (white level from the host's exp), + jitter, identity padding
+    // cov = K_** - P P^T, P = K_* L^-T, in the child's matrix (white level from the host's exp), + jitter, identity padding
     auto build_cov = [&]() -> int {
-      BGP_TRY(post_cov(c, 1, m, dKs, Kinv, nullptr, dP, PostKss{dhk, dXq, h_kernel}, 1, w->dK));
+      BGP_TRY(post_cov(c, 1, m, dKs, Linv, nullptr, dP, PostKss{dhk, dXq, h_kernel}, 1, w->dK, nullptr, true));
       hipLaunchKernelGGL(cov_prepare_kernel, dim3(1024), dim3(256), 0, c->stream, w->dK, m, mpad, jitter);
       return BGP_OK;
     };
@@ -1186,8 +1194,8 @@ extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const doub
       BGP_TRY(bgp_launch_kcross_batch(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs));
       hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, c->dalpha_sol,
                          (size_t)npad, dpc, n, m, dmean, (size_t)mpad);
-      // cov = K_** - P K_*^T in place in the child's matrices, + jitter, identity padding
-      BGP_TRY(post_cov(c, nb, m, dKs, c->dKinv, dpc, dP, PostKss{dHc, dXq}, 1, w->dK));
+      // cov = K_** - P P^T, P = K_* L^-T, in place in the child's matrices, + jitter, identity padding
+      BGP_TRY(post_cov(c, nb, m, dKs, c->dLinv, dpc, dP, PostKss{dHc, dXq}, 1, w->dK, nullptr, true));
       hipLaunchKernelGGL(cov_prepare_kernel, dim3(256, nb), dim3(256), 0, c->stream, w->dK, m, mpad, jitter);
       // (by launches: nothing waits inside a chunk, so there is nothing to rebuild)
       BGP_TRY(post_factor_child(c, w, nb, false, status + off, [] { return (int)BGP_OK; }));

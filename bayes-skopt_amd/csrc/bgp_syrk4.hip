@@ -173,8 +173,8 @@ void bgp_launch_trsm4(hipStream_t st, int B, double* dK, double* dW, double* dyw
 
 // ------------------------------------------------------------------------------------------
 // General NT product on the same ring for the posterior consumers (sample_y, predictive covariances):
-//     MODE 0:  C  = A B^T          (C not read)             P = K_* K^-1
-//     MODE 1:  C -= A B^T  on the tiles with ti >= tj only   cov = K_** - P K_*^T when only a Cholesky reads it
+//     MODE 0:  C  = A B^T          (C not read)             P = K_* K^-1, or P = K_* L^-T with B = L^-1 (the draws)
+//     MODE 1:  C -= A B^T  on the tiles with ti >= tj only   cov = K_** - P P^T when only a Cholesky reads it (A and B alias)
 //     MODE 2:  C -= A B^T  on every tile                     the full predictive covariance of predict(return_cov)
 // A (M x K) and B (N x K) share the leading dimension ldx, C (M x N) has ldc; M, N multiples of 64, K of 16.
 // 64 x 64 tiles, four waves of 32 x 32; blockIdx.y = item of a batch (strides sA, sB, sC; pidxB maps item -> B slot).

@@ -3,8 +3,9 @@
 Plain numpy in ``np.longdouble`` (x87 extended: 64-bit mantissa, eps = 2^-63 ~ 1.1e-19, 2048 times finer than fp64).  It
 restates, from the definitions in ``gp_oracle.py``'s docstring (canonical vector ``h = [log c, log l_1..l_d, log s2]``,
 product form ``c*S(r) + s2*I``, sum form ``c + S(r) + s2*I``), the Gram build, the Cholesky factor, triangular solves, the
-LML and its gradient, the posterior factors, predict, PVRS covs, the ``sample_y`` transform for a fixed z, warped inputs and
-fantasy conditioning on chosen candidates (every prefix refactorised).
+LML and its gradient, the posterior factors, predict, the closed-form acquisitions averaged over draws (Phi, phi from mpmath),
+PVRS covs, the ``sample_y`` transform for a fixed z, warped inputs, fantasy conditioning on chosen candidates (every prefix
+refactorised), and the posterior / predict of a given fp64 kernel matrix (generic kernels).
 Only the tests import it; the product never does.  ``gp_oracle.py`` (fp64, scipy/LAPACK) stays the parity oracle; this
 module is what both are measured against in ``tests/test_cpu_precision.py`` and ``tests/test_gpu_precision.py``.
 
@@ -335,13 +336,105 @@ def pvrs_covs(X_train, alpha_vec, h, X_cand, thompson_points, stationary="matern
     return out
 
 
-def sample_y(X, y, alpha_diag, h, Xq, z, jitter, stationary="matern52", form="product", noise_zero=True):
-    """mean + chol(cov + jitter I) z for fixed z (rows of z are draws): (n_draws, m)."""
+def sample_y_factor(X, y, alpha_diag, h, Xq, jitter, stationary="matern52", form="product", noise_zero=True):
+    """(mean, chol(cov + jitter I), predict result) of the ``sample_y`` transform: what draws of one posterior at one set of
+    query points share."""
     p = predict(X, y, alpha_diag, h, Xq, stationary, form, noise_zero=noise_zero, return_cov=True)
     C = p["cov"]
     C[np.diag_indices_from(C)] += LD(jitter)
-    Lc = cholesky(C)
-    return p["mean"][None, :] + np.asarray(z, dtype=np.float64).astype(LD) @ Lc.T, p
+    return p["mean"], cholesky(C), p
+
+
+def sample_y(X, y, alpha_diag, h, Xq, z, jitter, stationary="matern52", form="product", noise_zero=True, factor=None):
+    """mean + chol(cov + jitter I) z for fixed z (rows of z are draws): (n_draws, m).  ``factor``: a ``sample_y_factor``
+    result of the same arguments to reuse."""
+    mean, Lc, p = factor if factor is not None else sample_y_factor(X, y, alpha_diag, h, Xq, jitter, stationary, form,
+                                                                     noise_zero)
+    return mean[None, :] + np.asarray(z, dtype=np.float64).astype(LD) @ Lc.T, p
+
+
+def posterior_gram(K, alpha_diag, y):
+    """Posterior factors from a GIVEN fp64 kernel matrix (generic kernels: the host evaluates K, the device factorises
+    K + diag(alpha)): the entries of K are taken as exact and everything behind them is long double."""
+    require()
+    K = np.asarray(K, dtype=np.float64)
+    Kl = K.astype(LD)
+    Kl[np.diag_indices_from(Kl)] += np.broadcast_to(np.asarray(alpha_diag, dtype=np.float64), (len(K),)).astype(LD)
+    L = cholesky(Kl)
+    a = cho_solve(L, np.asarray(y, dtype=np.float64).astype(LD))
+    return {"K": Kl, "L": L, "alpha": a, "K_inv": inverse_from_factor(L)}
+
+
+def predict_gram(post, Ks, kss, Kss=None):
+    """Mean, variance (and covariance) from given fp64 ``Ks`` (m, n), ``kss`` (m,), ``Kss`` (m, m) and a ``posterior_gram``
+    result."""
+    Ks = np.asarray(Ks, dtype=np.float64).astype(LD)
+    V = solve_lower(post["L"], Ks.T)
+    out = {"mean": Ks @ post["alpha"], "var": np.asarray(kss, dtype=np.float64).astype(LD) - np.einsum("ij,ij->j", V, V)}
+    if Kss is not None:
+        out["cov"] = np.asarray(Kss, dtype=np.float64).astype(LD) - V.T @ V
+    return out
+
+
+ACQ_DPS = 40  # (the precision ``warp_inputs`` evaluates the Beta CDF at)
+
+
+def _mp_to_ld(v):
+    import mpmath
+
+    return LD(mpmath.nstr(v, 30, min_fixed=-1, max_fixed=-1))
+
+
+def normal_cdf_pdf(x):
+    """Phi(x) and phi(x) of a long-double array from mpmath at ACQ_DPS digits, rounded to long double."""
+    require()
+    import mpmath
+
+    x = np.asarray(x, dtype=LD)
+    Phi, phi = np.empty(x.shape, dtype=LD), np.empty(x.shape, dtype=LD)
+    with mpmath.workdps(ACQ_DPS):
+        for idx in np.ndindex(x.shape):
+            v = mpmath.mpf(np.format_float_scientific(x[idx], precision=24, unique=False))
+            Phi[idx], phi[idx] = _mp_to_ld(mpmath.ncdf(v)), _mp_to_ld(mpmath.npdf(v))
+    return Phi, phi
+
+
+def acquisitions(mean, var, y_mean, y_std, kinds, params, n_samples):
+    """Closed-form acquisitions averaged over the draws, from the long-double moments ``mean``, ``var`` (B, m) of ``predict``:
+    per draw ``mu = y_std mean + y_mean``, ``sd = sqrt(max(var, 0)) y_std``; "EI" ``(x Phi(x) + phi(x)) sd`` with
+    ``x = (y_opt - mu) / sd`` (``y_opt`` the parameter, or the draw's lowest ``mu`` when it is NaN; 0 where sd is not
+    positive), "LCB" ``param sd - mu``, "MEAN" ``-mu``, "STD" ``sd``; added in draw order, each over ``n_samples``.
+    Returns values (n_acq, m) and per draw ``mu``, ``sd`` (B, m), ``y_opt`` (n_acq, B; NaN for the other kinds), ``x``,
+    ``Phi``, ``phi`` (n_acq, B, m; zeros for the other kinds) for the tolerance model."""
+    require()
+    mean, var = np.atleast_2d(np.asarray(mean, dtype=LD)), np.atleast_2d(np.asarray(var, dtype=LD))
+    B, m = mean.shape
+    ys, ym, ns = LD(float(y_std)), LD(float(y_mean)), LD(int(n_samples))
+    mu, sd = ys * mean + ym, np.sqrt(np.maximum(var, LD(0))) * ys
+    out = np.zeros((len(kinds), m), dtype=LD)
+    info = {"mu": mu, "sd": sd, "y_opt": np.full((len(kinds), B), np.nan, dtype=LD),
+            "x": np.zeros((len(kinds), B, m), dtype=LD), "Phi": np.zeros((len(kinds), B, m), dtype=LD),
+            "phi": np.zeros((len(kinds), B, m), dtype=LD)}
+    for k, (kind, par) in enumerate(zip(kinds, params)):
+        for b in range(B):
+            if kind == "MEAN":
+                v = -mu[b]
+            elif kind == "STD":
+                v = sd[b]
+            elif kind == "LCB":
+                v = LD(float(par)) * sd[b] - mu[b]
+            elif kind == "EI":
+                yo = mu[b].min() if np.isnan(par) else LD(float(par))
+                pos = sd[b] > 0
+                x = np.zeros(m, dtype=LD)
+                x[pos] = (yo - mu[b][pos]) / sd[b][pos]
+                Phi, phi = normal_cdf_pdf(x)
+                v = np.where(pos, (x * Phi + phi) * sd[b], LD(0))
+                info["y_opt"][k, b], info["x"][k, b], info["Phi"][k, b], info["phi"][k, b] = yo, x, Phi, phi
+            else:
+                raise ValueError(kind)
+            out[k] += v / ns
+    return out, info
 
 
 def fantasy(X, y, alpha_diag, h, Xc, picks, lies, base_alpha, stationary="matern52", form="product"):

@@ -11,6 +11,9 @@ Every error is measured against the scale that a correct fp64 computation can lo
 * grad     max_k |d g_k| / (0.5 sum_ij |W_ij dK_ij/dh_k|),  W = a a^T - K^-1   (components can cancel to ~0)
 * mean     max |d m_i| / max_i sum_j |K*_ij a_j|;   var  max |d var| (and |d cov|) / prior variance
 * pvrs     max |d cov_i| / max |cov_i|;   sample  max |d f| / max |f|
+* acq      per candidate and acquisition |d a_ki| against the first-order image of the mean / var tolerances of the draws
+             (``ref_acq``: no scale of its own; the batched cases PREDB_CASES carry mean / var per item b with that item's
+             kappa, ``mean_scale(cid, b)`` and ``prior_var(cid, nz, b)``)
 * fant_mean, fant_var   the mean / var metrics on the latent moments after each fantasy-conditioning step, scale, kappa and n
              those of the training set augmented by the chosen candidates (``fantasy_errs``)
 * warped   + CDF_REL * sens, sens = the quantity's error with the inputs rounded to fp32 divided by 2^-24: the first-order
@@ -31,6 +34,8 @@ CDF_REL = 1e-11  # device Beta CDF vs mpmath: within 2e-12 relative (x5 margin)
 # fp64 error is ~1e-16 absolute whatever kappa (a dot product with alpha), hence its small constant.  sample's constant is
 # the loosest: the draws go through chol(cov + jitter I) of a covariance that is itself the remainder of a cancellation, at
 # the larger of two condition numbers (``sample_kappa``); fp32 there still misses by >= 10 tol.
+# (SAMPLEB_CASES: the device forms that covariance from the inverse of the FACTOR, K_** - (K_* L^-T)(K_* L^-T)^T; with the
+# explicit K^-1 the draws miss this tolerance by up to 26 tol in fp64 -- tests/test_cpu_precision.py prints both.)
 #
 # fant_mean / fant_var: the latent moments after fantasy conditioning (FANTASY_CASES), kappa and n of the AUGMENTED set.  The
 # conditioned mean carries the error of the GEMV on the explicit inverse (u (lie - mu_p) / sqrt(s)), which a plain K* alpha
@@ -43,6 +48,11 @@ CDF_REL = 1e-11  # device Beta CDF vs mpmath: within 2e-12 relative (x5 margin)
 # base_alpha (1e-3) by >= 1e6 tol.  One case was changed to get there: a picked candidate equal to a training point lifts kappa of the augmented
 # matrix to lambda_max / noise, 2e5 for matern12 / sum at n = 257, where fp32 inputs bit the mean by only 4 tol; that case
 # lost its twin, and the twins sit in the cases whose kappa is at that level already or where the margin holds.
+#
+# acq (PREDB_CASES, ``ref_acq``) has no constant: its tolerance is the first-order image of the mean / var tolerances above and
+# holds both margins as derived -- worst reach 0.059 tol (n = m = 256, matern32 / product: the STD line, i.e. the variance's
+# own reach); fp32 inputs move the LEAST-moved acquisition of a case, under either noise setting, by 17 tol at the
+# single-candidate case and by >= 210 tol elsewhere.  No candidate of any case is left out.
 C = {"lml": 0.5, "alpha": 4.0, "K_inv": 4.0, "L": 4.0, "mean": 0.02, "var": 4.0, "grad": 2.0, "pvrs": 2.0, "sample": 16.0,
      "fant_mean": 0.09, "fant_var": 3.0}
 FLOOR = {"lml": 4e-13, "alpha": 2e-12, "K_inv": 2e-12, "L": 2e-12, "mean": 1e-13, "var": 4e-12, "grad": 1e-12,
@@ -260,8 +270,87 @@ def _fantasy_cases():
 
 
 FANTASY_CASES = _fantasy_cases()
+
+
+def _predb_cases():
+    """Batched predict, predictive covariance and the acquisition pass over B resident posteriors: the smallest shapes that
+    enter each index branch of the tile kernels behind them (128-tiles; mpad / npad = the size padded to 128).  ``cov``: the
+    covariance is asked for; ``n_samples``: the divisor of the acquisition average (the draws are the B items)."""
+    rows = [  # n, d, m, B, family, vec_alpha, cov, n_samples
+        # mpad = 640: covariance in two column panels (8 + 2); row quadratic form with < 8 items and 10 row tiles; one staging pass
+        (129, 16, 513, 3, ("rbf", "product"), False, True, 3),
+        # npad = 640: K_* K^-1 in two panels; 10 column tiles (three panels, narrow last); second staging pass of one dimension
+        (577, 17, 129, 3, ("matern32", "sum"), True, True, 5),
+        # exactly one round of item -> XCD pinning; third staging pass
+        (257, 33, 127, 8, ("matern12", "product"), False, False, 8),
+        # 9 items in 16 slots; m = 1
+        (127, 1, 1, 9, ("matern52", "sum"), True, False, 12),
+        # 7 items (< 8) with 12 row tiles; 8 column tiles (last panel full)
+        (385, 32, 641, 7, ("matern12", "sum"), False, False, 7),
+        # n = 1
+        (1, 3, 257, 3, ("rbf", "sum"), False, True, 3),
+        # every cross tile interior (check-free epilogue)
+        (256, 2, 256, 1, ("matern32", "product"), True, True, 4),
+        # both sides > 512
+        (640, 5, 385, 3, ("matern52", "product"), True, True, 3),
+    ]
+    out = []
+    for j, (n, d, m, B, (st, fm), vec, cov, ns) in enumerate(rows):
+        out.append(dict(id="predb%d_n%d_d%d_m%d_B%d_%s_%s" % (j, n, d, m, B, st, fm), n=n, d=d, m=m, B=B, stationary=st, form=fm,
+                        vec_alpha=vec, cov=cov, n_samples=ns, seed=1300 + j))
+    # (the m = 1 case changed its seed, the constants stayed.  Seed 1303 put the fp64 variance at 0.103 tol, kappa 1e5 on
+    # matern52 / sum in one dimension, where tol / 10 is asked, and its single query point lay between two of 127 training
+    # points on a line, where rounding the inputs to fp32 moves the variance by < 4 tol.  1305 is the first seed from 1304 up
+    # that holds every margin on every item and acquisition: the point lies outside the training set at 1.066, reach 0.026 tol,
+    # fp32 inputs miss by >= 109 tol (mean), 136 tol (variance), 16 tol (the least-moved acquisition, MEAN: the nine draws'
+    # signed errors meet the sum of their nine tolerances).  Of seeds 1304 .. 1362, four hold them all.)
+    out[3]["seed"] = 1305
+    return out
+
+
+PREDB_CASES = _predb_cases()
+# the Gram form (posterior_gram / predict_gram on host-evaluated fp64 matrices) runs on these two
+GRAM_CASES = [PREDB_CASES[1], PREDB_CASES[4]]
+
+PVRSB_CASES = [
+    dict(id="pvrs_n129_d17_nc257_nt129", n=129, d=17, stationary="matern12", form="sum", B=1, vec_alpha=True, seed=802,
+         nc=257, nt=129),
+    dict(id="pvrs_n257_d33_nc1_nt130", n=257, d=33, stationary="matern32", form="product", B=1, vec_alpha=False, seed=803,
+         nc=1, nt=130),
+    dict(id="pvrs_n257_d3_nc513_nt5", n=257, d=3, stationary="rbf", form="sum", B=1, vec_alpha=True, seed=804, nc=513, nt=5),
+    # VarianceReduction: the Thompson points are the candidates
+    dict(id="pvrs_n60_d2_varred", n=60, d=2, stationary="matern52", form="product", B=1, vec_alpha=False, seed=805, nc=12,
+         nt=12, tp_is_cand=True),
+    # context-level warp (WARP_CASES[0]'s problem): training, candidate and Thompson points through the Beta CDF
+    dict(id="pvrs_warp_n100_d2", n=100, d=2, stationary="matern52", form="product", B=1, vec_alpha=False, seed=700, nc=12,
+         nt=5, warp=True),
+]
+
+# sample_y (``draws`` rows of z on resident posterior 0) and sample_y_batch (item i on posterior ``pidx[i]`` with its own
+# h_kernel and z; ``latent[i]``: the white level leaves item i's kernel) over 3 resident posteriors, d = 2 so that the
+# covariances are genuinely correlated.  The last one is the isolation case: a duplicated query row and no jitter, so the
+# latent items' covariances are singular; only the ``regular`` items are compared.
+SAMPLEB_CASES = [
+    dict(id="sampleb_n129_m513", n=129, d=2, m=513, stationary="matern32", form="product", B=3, vec_alpha=False, seed=1400,
+         draws=17, pidx=[2, 0, 2, 1, 0], latent=[True] * 5, regular=[0, 1, 2, 3, 4], jitter=1e-8, dup_query=False),
+    dict(id="sampleb_n257_m129", n=257, d=2, m=129, stationary="matern52", form="sum", B=3, vec_alpha=True, seed=1401,
+         draws=33, pidx=[0, 1, 2, 2, 1, 0, 1, 1, 2], latent=[True] * 9, regular=list(range(9)), jitter=1e-8,
+         dup_query=False),
+    dict(id="sampleb_isolation_n65_m130", n=65, d=2, m=130, stationary="matern52", form="product", B=3, vec_alpha=False,
+         seed=1402, draws=0, pidx=[0, 1, 2, 1, 0], latent=[True, False, True, False, True], regular=[1, 3], jitter=0.0,
+         dup_query=True),
+]
+
+# The chunk loop of the batched predict: the scratch of one item is mpad (npad + 2) = 2^20 + 2^14 doubles, so the 2^30-double
+# budget holds 1008 items (rounded down to a multiple of 8) and 1025 items run as chunks of 1008 + 17.  ``items``: compared bit
+# for bit with a call on posteriors rebuilt from those rows alone (both sides of the chunk boundary, the last two);
+# ``ref_items`` meet the long-double reference on the first ``ref_rows`` query rows.
+CHUNK_CASE = dict(id="chunk_n128_d2_m8192_B1025", n=128, d=2, m=8192, B=1025, stationary="matern52", form="product",
+                  vec_alpha=False, cov=False, n_samples=1025, seed=1500, items=[0, 1007, 1008, 1023, 1024],
+                  ref_items=[0, 1023, 1024], ref_rows=64)
+
 ALL = {c["id"]: c for c in LML_CASES + SCHED_CASES + GRAD_CASES + POST_CASES + WARP_CASES + PVRS_CASES + SAMPLE_CASES
-       + FANTASY_CASES}
+       + FANTASY_CASES + PREDB_CASES + PVRSB_CASES + SAMPLEB_CASES + [CHUNK_CASE]}
 
 
 @functools.lru_cache(maxsize=None)
@@ -338,28 +427,160 @@ def ref_predict(cid, noise_zero):
                       post=ref_post(cid))
 
 
-def mean_scale(cid):
-    """max_i sum_j |K*_ij a_j| (long double reference)."""
+@functools.lru_cache(maxsize=None)
+def mean_scale(cid, b=0):
+    """max_i sum_j |K*_ij a_j| of item b (long double reference)."""
     from oracle import hp_oracle as HP
 
     c = ALL[cid]
     X, y, alpha, H, _ = problem(cid)
-    Ks = HP.gram(query(cid), H[0], c["stationary"], c["form"], Y=X)
-    return float(np.abs(Ks * ref_post(cid)["alpha"][None, :]).sum(axis=1).max())
+    Ks = HP.gram(query(cid), H[b], c["stationary"], c["form"], Y=X)
+    return float(np.abs(Ks * ref_lml(cid, b)["alpha"][None, :]).sum(axis=1).max())
 
 
-def prior_var(cid, noise_zero):
+def prior_var(cid, noise_zero, b=0):
     c = ALL[cid]
     _X, _y, _a, H, _ = problem(cid)
     from oracle import hp_oracle as HP
 
-    return float(HP.prior_var(H[0], c["d"], c["form"], noise=not noise_zero))
+    return float(HP.prior_var(H[b], c["d"], c["form"], noise=not noise_zero))
+
+
+@functools.lru_cache(maxsize=None)
+def ref_predict_b(cid, b, noise_zero):
+    """Long-double predict of item b of a batched case (the covariance only where the case asks for it)."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    return HP.predict(X, y, alpha, H[b], query(cid), c["stationary"], c["form"], noise_zero=noise_zero,
+                      return_cov=c["cov"], post=ref_lml(cid, b))
+
+
+@functools.lru_cache(maxsize=None)
+def ref_chunk(cid, b):
+    """Long-double mean and variance (white level kept) of item b of the chunk case on its first ``ref_rows`` query rows, the
+    mean's absolute-sum scale there and the prior variance."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    Xq = query(cid)[: c["ref_rows"]]
+    post = ref_lml(cid, b)
+    pr = HP.predict(X, y, alpha, H[b], Xq, c["stationary"], c["form"], post=post)
+    Ks = HP.gram(Xq, H[b], c["stationary"], c["form"], Y=X)
+    return pr, float(np.abs(Ks * post["alpha"][None, :]).sum(axis=1).max()), prior_var(cid, False, b)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the acquisition pass
+# ------------------------------------------------------------------------------------------------------------------------------
+ACQ_KINDS = ["EI", "EI", "LCB", "LCB", "MEAN", "STD"]
+ACQ_Y_MEAN, ACQ_Y_STD, ACQ_Y_OPT = 1.5, 3.0, 0.3
+ACQ_PARAMS = [float("nan"), ACQ_Y_OPT, 1.96, 3.0, 0.0, 0.0]
+
+
+@functools.lru_cache(maxsize=None)
+def ref_acq(cid, noise_zero):
+    """The averaged acquisitions of a batched case from the long-double moments of its B items (``hp_oracle.acquisitions``)
+    and their tolerance per acquisition k and candidate i: the first-order image of the moment tolerances.  With
+    dmu_b = y_std tol("mean", kappa_b, n) mean_scale_b and dsd_bi = y_std tol("var", kappa_b, n) prior_var_b / (2 sqrt(var_bi)),
+    a draw contributes  Phi(x) dmu + phi(x) dsd  to EI with a given y_opt (d EI / d mu = -Phi, d EI / d sd = phi), twice the
+    dmu term when y_opt is the draw's lowest mu (it moves by dmu as well), dmu + |param| dsd to LCB, dmu to MEAN, dsd to STD,
+    and 8 eps (|y_opt - mu| + sd) to EI for the device's erf / erfc / exp; the sum over the draws is divided by n_samples.
+    ``keep``: the candidates whose variance is >= 100 tol("var") prior_var in every draw (dsd is first order in d var / var)."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    n, B = c["n"], c["B"]
+    kap = problem(cid)[4]
+    mean = np.array([ref_predict_b(cid, b, noise_zero)["mean"] for b in range(B)])
+    var = np.array([ref_predict_b(cid, b, noise_zero)["var"] for b in range(B)])
+    vals, info = HP.acquisitions(mean, var, ACQ_Y_MEAN, ACQ_Y_STD, ACQ_KINDS, ACQ_PARAMS, c["n_samples"])
+    dmu = np.array([ACQ_Y_STD * tol("mean", kap[b], n) * mean_scale(cid, b) for b in range(B)])[:, None]
+    tv = np.array([tol("var", kap[b], n) * prior_var(cid, noise_zero, b) for b in range(B)])[:, None]
+    keep = (f(var) >= 100.0 * tv).all(axis=0)
+    dsd = ACQ_Y_STD * tv / (2.0 * np.sqrt(np.maximum(f(var), 100.0 * tv)))
+    mu, sd = f(info["mu"]), f(info["sd"])
+    T = np.empty((len(ACQ_KINDS), mean.shape[1]))
+    for k, (kind, par) in enumerate(zip(ACQ_KINDS, ACQ_PARAMS)):
+        if kind == "EI":
+            t = (f(info["Phi"][k]) * ((2.0 if math.isnan(par) else 1.0) * dmu) + f(info["phi"][k]) * dsd
+                 + 8.0 * EPS * (np.abs(f(info["y_opt"][k])[:, None] - mu) + sd))
+        elif kind == "LCB":
+            t = dmu + abs(par) * dsd
+        else:
+            t = dmu + 0.0 * dsd if kind == "MEAN" else dsd
+        T[k] = t.sum(axis=0) / c["n_samples"]
+    return {"values": vals, "tol": T, "keep": keep}
+
+
+def acq64(mu, std, n_samples):
+    """The acquisition average in fp64 numpy / scipy from per-draw ``mu``, ``std`` (B, m) in y units."""
+    from oracle import gp_oracle as O
+
+    out = np.zeros((len(ACQ_KINDS), mu.shape[1]))
+    for b in range(len(mu)):
+        for k, (kind, par) in enumerate(zip(ACQ_KINDS, ACQ_PARAMS)):
+            if kind == "EI":
+                v = O.expected_improvement(mu[b], std[b], None if math.isnan(par) else par)
+            else:
+                v = O.lcb(mu[b], std[b], par) if kind == "LCB" else (-mu[b] if kind == "MEAN" else std[b])
+            out[k] += v / n_samples
+    return out
+
+
+def acq_ratio(got, ref):
+    """Per acquisition the worst err / tol over the compared candidates: (n_acq,)."""
+    k = ref["keep"]
+    return (np.abs(f(got) - f(ref["values"]))[:, k] / ref["tol"][:, k]).max(axis=1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the Gram form: host-evaluated fp64 kernel matrices in, device arithmetic behind them
+# ------------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def gram_inputs(cid, b):
+    """(K, Ks, kss, Kss or None) of item b in fp64 from ``gp_oracle.kernel_matrix`` (the white level on the diagonals)."""
+    from oracle import gp_oracle as O
+
+    c = ALL[cid]
+    X, _y, _a, H, _ = problem(cid)
+    st, fm, Xq = c["stationary"], c["form"], query(cid)
+    return (O.kernel_matrix(X, H[b], st, fm), O.kernel_matrix(Xq, H[b], st, fm, Y=X), O.kernel_diag(len(Xq), H[b], c["d"], fm),
+            O.kernel_matrix(Xq, H[b], st, fm) if c["cov"] else None)
+
+
+@functools.lru_cache(maxsize=None)
+def ref_gram(cid, b):
+    """Long-double posterior factors and predict from the fp64 matrices of ``gram_inputs`` (taken as exact), and the mean's
+    absolute-sum scale."""
+    from oracle import hp_oracle as HP
+
+    _X, y, alpha, _H, _ = problem(cid)
+    K, Ks, kss, Kss = gram_inputs(cid, b)
+    post = HP.posterior_gram(K, alpha, y)
+    post.update(HP.predict_gram(post, Ks, kss, Kss))
+    post["mean_scale"] = float(np.abs(Ks.astype(np.longdouble) * post["alpha"][None, :]).sum(axis=1).max())
+    return post
+
+
+def gram_errs(cid, b, L, a, Ki, mean, var, cov):
+    """{quantity: error} of item b's Gram-form factors and predict on the scales of the canonical path."""
+    ref = ref_gram(cid, b)
+    pv = prior_var(cid, False, b)
+    errs = {"L": err_L(L, ref), "alpha": err_alpha(a, ref), "K_inv": err_K_inv(Ki, ref["K_inv"]),
+            "mean": err_rel_max(mean, ref["mean"], ref["mean_scale"]), "var": err_rel_max(var, ref["var"], pv)}
+    if cov is not None:
+        errs["cov"] = err_rel_max(cov, ref["cov"], pv)
+    return errs
 
 
 def pvrs_inputs(cid):
     c = ALL[cid]
     rng = np.random.RandomState(c["seed"] + 3)
-    return rng.uniform(size=(c["nc"], c["d"])), rng.uniform(size=(c["nt"], c["d"]))
+    Xc, Xt = rng.uniform(size=(c["nc"], c["d"])), rng.uniform(size=(c["nt"], c["d"]))
+    return Xc, (Xc if c.get("tp_is_cand") else Xt)
 
 
 @functools.lru_cache(maxsize=None)
@@ -369,7 +590,29 @@ def ref_pvrs(cid):
     c = ALL[cid]
     X, _y, alpha, H, _ = problem(cid)
     Xc, Xt = pvrs_inputs(cid)
+    if c.get("warp"):
+        w = warp_params(cid)[0]
+        X, Xc, Xt = (HP.warp_inputs(A, w) for A in (X, Xc, Xt))
     return HP.pvrs_covs(X, alpha if c["vec_alpha"] else None, H[0], Xc, Xt, c["stationary"], c["form"])
+
+
+@functools.lru_cache(maxsize=None)
+def pvrs_tol(cid):
+    """tol("pvrs") of a case; under a context-level warp at kappa of the warped Gram matrix and with the Beta-CDF budget
+    (``sens``: the fp64 computation's error with the warped points rounded to fp32, over 2^-24, as in ``ref_set_warp``)."""
+    from oracle import gp_oracle as O
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, _y, alpha, H, kap = problem(cid)
+    if not c.get("warp"):
+        return tol("pvrs", kap[0], len(X))
+    w = warp_params(cid)[0]
+    Xc, Xt = pvrs_inputs(cid)
+    Xw, Xcw, Xtw = (to32(f(HP.warp_inputs(A, w))) for A in (X, Xc, Xt))
+    got32 = O.pvrs_covs(Xw, alpha if c["vec_alpha"] else None, H[0], Xcw, Xtw, c["stationary"], c["form"])
+    kw = kappa_of(f(HP.warp_inputs(X, w)), alpha, H[0], c["stationary"], c["form"])
+    return tol("pvrs", kw, len(X), err_rel_max(got32, ref_pvrs(cid)) / F32)
 
 
 SAMPLE_JITTER = 1e-8
@@ -398,6 +641,45 @@ def sample_kappa(cid):
     C = f(ref_predict(cid, True)["cov"])
     w = np.linalg.eigvalsh(C + SAMPLE_JITTER * np.eye(len(C)))
     return max(float(kap[0]), float(w[-1] / w[0]))
+
+
+def sampleb_query(cid):
+    c = ALL[cid]
+    Xq = query(cid).copy()
+    if c["dup_query"]:
+        Xq[-1] = Xq[3]
+    return Xq
+
+
+def sampleb_z(cid):
+    """(z of the ``draws`` rows for sample_y, z of the items of sample_y_batch)."""
+    c = ALL[cid]
+    rng = np.random.RandomState(c["seed"] + 4)
+    return rng.standard_normal((c["draws"], c["m"])), rng.standard_normal((len(c["pidx"]), c["m"]))
+
+
+@functools.lru_cache(maxsize=None)
+def _sampleb_factor(cid, b, latent):
+    """``hp_oracle.sample_y_factor`` of resident posterior b (what the items on it share) and the kappa that governs its draws."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, kap = problem(cid)
+    fac = HP.sample_y_factor(X, y, alpha, H[b], sampleb_query(cid), c["jitter"], c["stationary"], c["form"], noise_zero=latent)
+    w = np.linalg.eigvalsh(f(fac[2]["cov"]))  # (the jitter is on its diagonal)
+    return fac, max(float(kap[b]), float(w[-1] / w[0]))
+
+
+def ref_sampleb(cid, b, latent, z):
+    """(``hp_oracle.sample_y`` for the rows of z on resident posterior b, tol("sample") there)."""
+    from oracle import hp_oracle as HP
+
+    c = ALL[cid]
+    X, y, alpha, H, _ = problem(cid)
+    fac, k = _sampleb_factor(cid, b, latent)
+    out, _p = HP.sample_y(X, y, alpha, H[b], sampleb_query(cid), z, c["jitter"], c["stationary"], c["form"], noise_zero=latent,
+                         factor=fac)
+    return out, tol("sample", k, len(X))
 
 
 def grad_vs_fp64(g_dev, X, y, alpha, h, stationary="matern52", form="product"):

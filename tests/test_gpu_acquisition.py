@@ -75,9 +75,9 @@ def test_device_average_over_draws_follows_the_reference_rules(lib, ctx):
 
 def test_device_acquisition_pass_equals_host_loop(lib):
     """evaluate_acquisitions with the device pass (build + predict + closed forms + average in one call, nothing but
-    (n_acq, m) values returned) against the same call with the host loop over draws, at a size where the batched
-    predict runs in two chunks of draws; a criterion without a device form (TopTwoEI) sends the whole call to the
-    host path."""
+    (n_acq, m) values returned) against the same call with the host loop over draws (one chunk of draws at this size: the
+    chunk loop of the batched predict is tests/test_gpu_predictive_precision.py::test_predict_chunk_loop); a criterion
+    without a device form (TopTwoEI) sends the whole call to the host path."""
     import bayes_skopt_amd as bask
     from bayes_skopt_amd import acquisition as acq
 

@@ -3,7 +3,9 @@
 margin and a single-precision slip misses it by 10x): the LML on every tile edge, dimension-staging edge and kernel family,
 every factorisation schedule, the warped LML and posterior, the LML gradient, the posterior factors, predict, PVRS and the
 sample_y transform.  Every test prints its worst err / tol (``pytest -s``); lines start with ``PRECISION``.
-The moments after fantasy conditioning (``fant_mean`` / ``fant_var``) meet the same model in tests/test_gpu_fantasy.py."""
+The moments after fantasy conditioning (``fant_mean`` / ``fant_var``) meet the same model in tests/test_gpu_fantasy.py; the
+batched predictive pipeline (predict and covariance over many posteriors, the acquisition pass, sample_y's draw groups,
+sample_y_batch, larger PVRS sets, the Gram form, the chunk loop) in tests/test_gpu_predictive_precision.py."""
 import json
 import os
 import subprocess
