@@ -126,6 +126,8 @@ SIGNATURES = {
     "bgp_last_timing": (C.c_int, [_vp, _dp, _ip]),
     "bgp_set_timing": (C.c_int, [_vp, C.c_int]),
     "bgp_set_persist": (C.c_int, [_vp, C.c_int]),
+    "bgp_set_panel_fused": (C.c_int, [_vp, C.c_int]),
+    "bgp_panel_fused_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_last_timing_columns": (C.c_int, [_vp, _dp, _ip]),
     "bgp_debug_workspace": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "bgp_debug_cov_factor": (C.c_int, [_vp, _ip, _dp]),
@@ -757,6 +759,17 @@ class Context:
     def set_persist(self, mode):
         """Launch-free factorisation of small batches: 1 on, 0 off, -1 as BGP_PERSIST says (bgp_set_persist)."""
         _check(self._lib.bgp_set_persist(self._h, int(mode)), "bgp_set_persist")
+
+    def set_panel_fused(self, mode):
+        """Diagonal block and panel solve of a block column in one launch on the launch schedule's LML path: 1 on, 0 off, -1 as
+        BGP_PANEL_FUSED says (bgp_set_panel_fused)."""
+        _check(self._lib.bgp_set_panel_fused(self._h, int(mode)), "bgp_set_panel_fused")
+
+    def panel_fused_stats(self):
+        """Fused panel launches enqueued by this context (bgp_panel_fused_stats)."""
+        v = (C.c_longlong * 1)()
+        _check(self._lib.bgp_panel_fused_stats(self._h, v), "bgp_panel_fused_stats")
+        return {"launches": int(v[0])}
 
     def set_timing(self, enable):
         _check(self._lib.bgp_set_timing(self._h, int(bool(enable))), "bgp_set_timing")

@@ -195,6 +195,7 @@ static int alloc_work(bgp_ctx* c) {
   int rc = c->dK.ensure(mb * npad * npad);
   if (!rc) rc = c->dW.ensure(mb * nblk * 128 * 128);
   if (!rc) rc = c->dyw.ensure(mb * 2 * npad);  // augmented right-hand sides are 2 npad long
+  if (!rc) rc = c->dzf.ensure(mb * npad);
   return rc;
 }
 
@@ -248,7 +249,7 @@ static void warn_unknown_env_once() {
   if (done) return;
   done = true;
   static const char* known[] = {"BGP_COMM_DIR", "BGP_COMM_PORT", "BGP_COMM_TCP", "BGP_DIST_BACKEND", "BGP_DIST_FORCE",
-                                "BGP_COMM_JOB", "BGP_BENCH_TIMEOUT", "BGP_DEBUG_TIMES", "BGP_PANELS", "BGP_NO_ENV_DEFAULTS",
+                                "BGP_COMM_JOB", "BGP_BENCH_TIMEOUT", "BGP_DEBUG_TIMES", "BGP_PANELS", "BGP_PANEL_FUSED", "BGP_NO_ENV_DEFAULTS",
                                 "BGP_PERSIST", "BGP_PS_COOLDOWN", "BGP_PS_GEN", "BGP_SYRK_GEN", "BGP_PS_PAIR", "BGP_PS_TIMEOUT_MS", "BGP_PS_TIMEOUT_TICKS", "BGP_PS_TRACE", "BGP_STREAMS", "BGP_WAIT", "BGP_COMM_TIMEOUT_S"};
   for (char** e = environ; e && *e; e++) {
     if (strncmp(*e, "BGP_", 4) != 0) continue;
@@ -304,17 +305,20 @@ extern "C" int bgp_ctx_create(int device, int n, int d, const double* X, const d
     return BGP_ERR_HIP;
   }
   {
-    // walker-group streams: BGP_STREAMS=k forces k groups; unset = automatic (two groups for batches of
-    // >= 64 matrices, where the second group's kernels fill the tail of the first group's launches: +3.7 %
-    // at BASELINE config C, results bit-identical; one group below that)
+    // walker-group streams: BGP_STREAMS=k forces k groups; unset = ONE group.  (Two groups for batches of >= 64 matrices were
+    // the default while the second group's kernels filled the tails of the first group's launches; with the fused panel launches,
+    // which take whole CUs, one group measured faster at BASELINE config C: 14.60-14.97 against 15.02-15.11 ms per step,
+    // docs/EXPERIMENTS.md G29; results bit-identical either way)
     const char* env = getenv("BGP_STREAMS");
-    int ns = env ? atoi(env) : 2;
+    int ns = env ? atoi(env) : 1;
     c->streams_auto = env ? 0 : 1;
     if (ns < 1) ns = 1;
     if (ns > BGP_MAX_STREAMS) ns = BGP_MAX_STREAMS;
     c->nstreams = ns;
     const char* envps = getenv("BGP_PERSIST");  // 0: never, 1: whenever the batch fits (<= 64 matrices, n > 128); unset: automatic
     c->persist = envps ? (atoi(envps) != 0 ? 1 : 0) : -1;
+    const char* envpf = getenv("BGP_PANEL_FUSED");  // 0: never, 1: every block column with a solve; unset: bgp_panel_fused_rule
+    c->panel_fused = envpf ? (atoi(envpf) != 0 ? 1 : 0) : -1;
     c->panels = 2;
     c->panels_auto = 1;
     const char* envp = getenv("BGP_PANELS");
@@ -414,6 +418,12 @@ extern "C" int bgp_lml_gen_stats(bgp_ctx* c, long long* out) {
   return BGP_OK;
 }
 
+extern "C" int bgp_panel_fused_stats(bgp_ctx* c, long long* out) {
+  if (!c || !out) return BGP_ERR_INVALID;
+  out[0] = c->fused_launches;
+  return BGP_OK;
+}
+
 // Launch-free path bookkeeping of a context: out[0] = launch-free calls enqueued, out[1] = of which timed out (redone by
 // launches), out[2] = 1 while the path is switched off by a time-out, out[3] = eligible calls left before it is tried again
 // (0 with out[2] == 1: off for good after three time-outs, until bgp_set_persist(ctx, 1)).
@@ -480,6 +490,7 @@ int bgp_lml_enqueue_dev(bgp_ctx* c, int nb, int warped) {
   gsz = nb;
   }
   const bool warp = warped != 0;
+  c->panel_groups = ng;  // (the groups' launches share the CUs: a fused panel launch sizes its grid for its share)
   int rc = BGP_OK;
   const bool fused_small = c->nblk == 1 && !warp;
   // launch-free path (bgp_chol.hip, ps_chain_kernel): automatic below 64 matrices per call when the matrices have at
@@ -733,9 +744,22 @@ extern "C" int bgp_debug_workspace(bgp_ctx* c, int b, double* Lout, double* zout
     return BGP_ERR_INVALID;
   }
   BGP_HIP(hipSetDevice(c->device));
-  const size_t np = c->npad;
+  const size_t np = c->npad, nblk = c->nblk;
   if (Lout) BGP_HIP(hipMemcpy(Lout, c->dK + (size_t)b * np * np, np * np * sizeof(double), hipMemcpyDeviceToHost));
   if (zout) BGP_HIP(hipMemcpy(zout, c->dyw + (size_t)b * np, np * sizeof(double), hipMemcpyDeviceToHost));
+  // block columns that went through panel_kernel (bgp_chol.hip): the lower triangle of L_kk is in slot (b, k) of dW and z_k in dzf;
+  // block (k, k) of the working matrix and segment k of the right-hand side still hold what the factorisation read
+  std::vector<double> blk;
+  for (size_t k = 0; k < nblk && c->fused_col.size() >= (b + 1) * nblk; k++) {
+    if (!c->fused_col[b * nblk + k]) continue;
+    if (Lout) {
+      blk.resize(128 * 128);
+      BGP_HIP(hipMemcpy(blk.data(), c->dW + ((size_t)b * nblk + k) * (128 * 128), 128 * 128 * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < 128; i++)
+        for (size_t j = 0; j <= i; j++) Lout[(k * 128 + i) * np + k * 128 + j] = blk[i * 128 + j];
+    }
+    if (zout) BGP_HIP(hipMemcpy(zout + k * 128, c->dzf + (size_t)b * np + k * 128, 128 * sizeof(double), hipMemcpyDeviceToHost));
+  }
   return BGP_OK;
 }
 
@@ -803,6 +827,24 @@ extern "C" int bgp_set_persist(bgp_ctx* c, int mode) {
     c->persist = mode;
   }
   if (mode == 1) c->ps_disabled = c->ps_cooldown = 0;
+  return BGP_OK;
+}
+
+// Diagonal block and panel solve of a block column in one launch on the LML path of the launch schedule (panel_kernel,
+// bgp_chol.hip): -1 = as the environment says (BGP_PANEL_FUSED; unset: bgp_panel_fused_rule), 0 = never,
+// 1 = every block column that has a solve.
+extern "C" int bgp_set_panel_fused(bgp_ctx* c, int mode) {
+  if (!c || mode < -1 || mode > 1) {
+    bgp_set_error("bgp_set_panel_fused: mode must be -1, 0 or 1");
+    return BGP_ERR_INVALID;
+  }
+  BGP_REQUIRE_IDLE(c, "bgp_set_panel_fused");
+  if (mode == -1) {
+    const char* envpf = getenv("BGP_PANEL_FUSED");
+    c->panel_fused = envpf ? (atoi(envpf) != 0 ? 1 : 0) : -1;
+  } else {
+    c->panel_fused = mode;
+  }
   return BGP_OK;
 }
 

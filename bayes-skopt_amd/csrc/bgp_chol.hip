@@ -26,6 +26,7 @@
 
 #include "bgp_gemm.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -78,6 +79,84 @@ __global__ void __launch_bounds__(PF_THREADS) potrf_kernel(double* __restrict__ 
   nopre.state = 0;
   (void)pf_block<GEN, STAT, FORM, 0>(b, Kbuf, Wbuf, yw, accb, lml, status, n, ld, mstride, ystride, nblk, k, gen, false, nullptr,
                                      PsArgs(), nopre);
+}
+
+// ------------------------------------------------------------------------------------------
+// Block column k of the LML path in ONE launch: diagonal factorisation and panel solve, W_kk never leaves LDS.
+//
+// Apart, potrf_kernel keeps one CU per matrix busy for ~30 us while the others idle, writes W_kk to memory only for trsm4_kernel to
+// stream it back through every 64-row workgroup's ring, and that solve is a chain of ten dependent memory round trips per workgroup.
+// Here matrix b gets S workgroups (b, p), p < S, each a whole CU with pf_block's LDS, that do not talk to each other:
+//   1. every one of them factorises block (k, k) -- the same code on the same inputs, so the same bits, on CUs that had nothing to do;
+//   2. with W_kk and z_k in its own LDS, workgroup p solves the row blocks i = k+1+p, k+1+p+S, ...:  X_i = A_ik W_kk^T in place,
+//      y_i -= X_i z_k (pf_solve_mma / pf_solve_out, bgp_pf.h: step 1 of the launch-free chain role, the arithmetic of
+//      trsm4_kernel), A fragments straight from memory into registers, those of the next row block requested before this one's MFMAs.
+// In-place outputs would be a hazard: the co-workers (p >= 1) read block (k, k) and y_k as INPUTS and may start arbitrarily late.
+// So nobody writes them: the owner (p = 0) alone puts L_kk into slot (b, k) of dW (nothing needs W_kk in memory any more), z_k into
+// row b of `zbuf`, and updates acc / lml / status; block (k, k) of dK and segment k of yw keep their pre-factorisation contents
+// (bgp_debug_workspace assembles L and z from both places).  A workgroup whose factorisation fails returns without solving.
+// Workgroup id = p * B8 + b: the S workgroups of a matrix land on the XCD b % 8 and share its L2 for block (k, k).
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(PF_THREADS) panel_kernel(double* __restrict__ Kbuf, double* __restrict__ Wbuf,
+                                                           double* __restrict__ yw, double* __restrict__ zbuf,
+                                                           double* __restrict__ accb, double* __restrict__ lml,
+                                                           int* __restrict__ status, int n, int ld, size_t mstride, int ystride,
+                                                           int nblk, int k, int B, int B8, int S) {
+  __shared__ int st_lds;
+  const int b = blockIdx.x % B8, p = blockIdx.x / B8;
+  if (b >= B) return;
+  // (one reader: the owner may set the status while a co-worker starts, and the workgroup must leave or stay as a whole)
+  if (threadIdx.x == 0) st_lds = status[b];
+  __syncthreads();
+  if (st_lds != 0) return;
+  PfPre nopre;
+  nopre.state = 0;
+  PfFuse fu;
+  fu.L = p == 0 ? Wbuf + ((size_t)b * nblk + k) * (128 * 128) : nullptr;
+  fu.z = zbuf + (size_t)b * ystride + k * 128;
+  if (pf_block<0, 0, 0, 0, 1>(b, Kbuf, Wbuf, yw, accb, lml, status, n, ld, mstride, ystride, nblk, k, PfGen(), false, nullptr, PsArgs(),
+                              nopre, fu))
+    return;
+  const PfLds lds = pf_lds();
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, lk = lane >> 4;
+  int i = k + 1 + p;
+  if (i >= nblk) return;
+  double* const Ak = Kbuf + (size_t)b * mstride + (size_t)k * 128;  // block column k of the matrix
+  double* const yb = yw + (size_t)b * ystride;
+  const size_t rowoff = (size_t)(16 * w + lr) * ld;
+  // Two fragment sets, half of the second at a time (three halves fit the register file beside the solve, four spilled): the
+  // k-groups 0-3 of row block i + S are requested before the MFMAs of row block i, the k-groups 4-7 behind its k-step 15, into the
+  // registers that the first half of row block i has left by then.
+  double af[32], alo[16], ahi[16];
+  pf_afrag_issue(Ak + (size_t)i * 128 * ld + rowoff, lk, af);
+#pragma unroll 1
+  for (; i < nblk; i += S) {
+    asm volatile("" ::: "memory");  // (nothing in this loop writes LDS: without this, every W operand of the solve is hoisted out of it and spills)
+    const bool more = i + S < nblk;  // (uniform)
+    const double* const An = Ak + (size_t)(i + S) * 128 * ld + rowoff;
+    if (more) pf_afrag_issue_half<0>(An, lk, alo);
+    double* const yi = yb + i * 128;
+    pf_afrag_transpose(af);
+    d4 x[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) x[j] = (d4){0.0, 0.0, 0.0, 0.0};
+    pf_solve_mma(af, lds.s, lds.Minv, lr, lk, x, [&] {
+      if (more) pf_afrag_issue_half<1>(An, lk, ahi);
+    });
+    d4 yv;  // (requested behind the MFMAs: the registers are full until then; the X stores cover most of its latency)
+#pragma unroll
+    for (int r = 0; r < 4; r++) yv[r] = yi[16 * w + lk + 4 * r];
+    pf_solve_out(x, lds.zpart, Ak + (size_t)i * 128 * ld, ld, w, lr, lk, yv, yi);
+    if (more) {
+#pragma unroll
+      for (int t = 0; t < 16; t++) {
+        af[t] = alo[t];
+        af[16 + t] = ahi[t];
+      }
+    }
+  }
 }
 
 // Device-resident ensemble sampler, n <= 128 (bgp_mcmc.hip): half-step h in ONE launch.  Workgroup i = proposal i of the half-step:
@@ -255,6 +334,7 @@ int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
     if (rch) return rch;
     *c->ps_herr = 0;
   }
+  std::fill(c->fused_col.begin(), c->fused_col.end(), 0);  // (this path leaves every block of L and z in place)
   const size_t words = ps_flag_words(B, nblk);
   {
     const int rcf = bgp_ps_ensure_flags(c, B);
@@ -415,6 +495,7 @@ void bgp_launch_syrk4_gen(hipStream_t st, int B8, double* dK, const int* dstatus
                           int K, int jstart, int colmode, int B, const S4Gen& gen, int stationary, int form);
 
 int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented) {
+  ctx->panel_groups = 1;
   return bgp_launch_cholesky_slice(ctx, 0, B, ctx->stream, augmented);
 }
 
@@ -443,6 +524,8 @@ int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int 
     // with the LDS-DMA kernels, whose look-ahead column launches are cheap enough), 2 below (P = 2, 3, 4 are equal
     // within noise at n = 1024); BGP_PANELS fixes it.
     const int P = ctx->panels_auto ? (nblk >= 12 ? 4 : 2) : ctx->panels;
+    double* dzf = ctx->dzf + (size_t)off * ystride;  // z_k of the fused block columns (panel_kernel)
+    if (ctx->fused_col.size() < (size_t)ctx->max_batch * nblk) ctx->fused_col.resize((size_t)ctx->max_batch * nblk, 0);
     S4Gen ga{};
     if (gen) {
       const int rcg = bgp_lml_gen_args(ctx, off, &ga);
@@ -453,14 +536,28 @@ int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int 
     while (k < nblk) {
       const int np = std::min(P, nblk - k);
       for (int j = 0; j < np; j++) {
-        bgp_tbegin(ctx, 1, st);
-        hipLaunchKernelGGL((potrf_kernel<0, 0, 0>), dim3(B), dim3(PF_THREADS), 0, st, dK, dW, dyw, dacc, dlml, dstatus,
-                           ctx->n, ld, mstride, ystride, nblk, k + j, PfGen());
-        bgp_tend(ctx, st);
-        if (k + j + 1 >= nblk) break;
-        bgp_tbegin(ctx, 2, st);
-        bgp_launch_trsm4(st, B, dK, dW, dyw, dstatus, ld, mstride, ystride, nblk, k + j, 0);
-        bgp_tend(ctx, st);
+        const int nrb = nblk - (k + j) - 1;
+        const bool fuse = nrb > 0 && (ctx->panel_fused == 1 ||
+                                      (ctx->panel_fused == -1 && bgp_panel_fused_rule(nrb, B, ctx->ncu / std::max(1, ctx->panel_groups))));
+        for (int bb = 0; bb < B; bb++) ctx->fused_col[(size_t)(off + bb) * nblk + k + j] = fuse ? 1 : 0;
+        if (fuse) {
+          // diagonal block and panel solve in one launch (panel_kernel); timed as the panel phase under "trsm"
+          const int S = bgp_panel_fused_wgs(nrb, B, ctx->ncu / std::max(1, ctx->panel_groups));
+          bgp_tbegin(ctx, 2, st);
+          hipLaunchKernelGGL(panel_kernel, dim3(S * B8), dim3(PF_THREADS), 0, st, dK, dW, dyw, dzf, dacc, dlml, dstatus, ctx->n, ld,
+                             mstride, ystride, nblk, k + j, B, B8, S);
+          bgp_tend(ctx, st);
+          ctx->fused_launches++;
+        } else {
+          bgp_tbegin(ctx, 1, st);
+          hipLaunchKernelGGL((potrf_kernel<0, 0, 0>), dim3(B), dim3(PF_THREADS), 0, st, dK, dW, dyw, dacc, dlml, dstatus,
+                             ctx->n, ld, mstride, ystride, nblk, k + j, PfGen());
+          bgp_tend(ctx, st);
+          if (k + j + 1 >= nblk) break;
+          bgp_tbegin(ctx, 2, st);
+          bgp_launch_trsm4(st, B, dK, dW, dyw, dstatus, ld, mstride, ystride, nblk, k + j, 0);
+          bgp_tend(ctx, st);
+        }
         if (j + 1 < np) {  // look-ahead: block column k+j+1 with the panels k .. k+j
           bgp_tbegin(ctx, 5, st);
           if (gen && k == 0) {
@@ -489,6 +586,7 @@ int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int 
   }
   // posterior build: nblk steps on the augmented matrix, the ring kernels in single-panel mode with the active-row
   // remap of bgp_rowblk (nblk active row blocks at every step)
+  std::fill(ctx->fused_col.begin(), ctx->fused_col.end(), 0);
   for (int k = 0; k < nblk; k++) {
     bgp_tbegin(ctx, 1, st);
     hipLaunchKernelGGL((potrf_kernel<0, 0, 0>), dim3(B), dim3(PF_THREADS), 0, st, dK, dW, dyw, dacc, dlml, dstatus, ctx->n,

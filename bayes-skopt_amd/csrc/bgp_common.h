@@ -194,6 +194,13 @@ struct bgp_ctx {
   int ps_disabled = 0;          // a persistent call timed out: multi-launch path (see bgp_ps_note_timeout)
   int ps_cooldown = 0;          // eligible calls left on the multi-launch path before the launch-free one is tried again
   long long gen_batches = 0, gen_launches = 0;  // bgp_lml_gen_stats
+  // launch schedule, LML path: diagonal block + panel solve of a block column in one launch (panel_kernel, bgp_chol.hip)
+  // (0 here: a context made without bgp_ctx_create -- the covariance workspace of sample_y -- is READ in place and never fuses)
+  int panel_fused = 0;          // bgp_ctx_create, env BGP_PANEL_FUSED: 0 never, 1 every block column that has a solve, -1 (unset) bgp_panel_fused_rule
+  int panel_groups = 1;         // walker-group streams that factorise side by side: a launch takes its share of the CUs (bgp_lml_enqueue_dev)
+  long long fused_launches = 0; // panel_kernel launches enqueued by this context (bgp_panel_fused_stats)
+  BgpDev<double> dzf;           // max_batch * npad: z_k of the fused block columns (segment k of dyw keeps y_k there)
+  std::vector<unsigned char> fused_col;  // [slot * nblk + k] = 1: the last factorisation of the slot left L_kk in dW and z_k in dzf
   long long ps_calls = 0;       // launch-free calls enqueued by this context (bgp_persist_stats)
   long long ps_timeouts = 0;    // ... of which timed out and were redone by launches
   int pending_warped = 0;       // the pending batch carries per-walker warps (redo path of bgp_lml_batch_wait)
@@ -315,6 +322,24 @@ struct PsArgs {
 // 0.383 -> 0.362; 1536 x 16 0.729 -> 0.719; 2048 x 8 0.927 -> 0.884; 512 x 32 0.260 -> 0.250; but 1024 x 32 0.522 -> 0.527, 2048 x 16
 // 1.308 -> 1.357 and 3072 x 8 1.921 -> 1.936: there the tile side is the bound already and the blocks are extra work for it)
 static inline bool bgp_ps_gen_auto_rule(int nblk, int B) { return nblk >= 4 && nblk <= 16 && B <= 32 && B * nblk <= 192; }
+// Block columns of the launch schedule's LML path that take ONE fused launch (panel_kernel, bgp_chol.hip) instead of potrf_kernel +
+// trsm4_kernel: nrb = row blocks under the diagonal block, B = matrices of the launch, ncu = the CUs the launch can count on (the
+// device's, divided by the walker-group streams that factorise side by side).  bgp_panel_fused_wgs = workgroups per matrix, S.
+// Measured per block column (config C: n = 2048 x 128 matrices, S = 2, one stream, rocprofv3 kernel trace, us, potrf + trsm4 -> fused):
+//   nrb = 15: 31.8 + 130.7 -> 129.4   14: 31.0 + 113.9 -> 116.3   13: 30.6 + 105.9 -> 114.4   12: 30.8 + 100.5 -> 104.4
+//   11: 31.9 + 92.5 -> 107.3   10: 31.7 + 84.1 -> 98.5   9: 31.2 + 72.6 -> 95.2   8: 30.8 + 65.4 -> 84.0   7: 31.1 + 60.4 -> 83.1
+//   6: 30.9 + 47.6 -> 70.6   5: 31.1 + 44.5 -> 71.8   4: 31.2 + 37.5 -> 59.6   3: 31.0 + 27.9 -> 57.7   2: 31.0 + 18.2 -> 46.7
+//   but nrb = 1: 30.8 + 12.3 -> 44.6 (one row block: 13 us behind the diagonal block's 31 either way, and the separate solve splits
+//   it over two workgroups per matrix).  A fused launch costs the diagonal block plus ~12.3 us per row block of its busiest
+//   workgroup: 1.481 -> 1.284 ms per half-step over the fifteen columns.
+// So: at least two row blocks and at least two workgroups per matrix.  (One workgroup per matrix -- more than ncu / 2 matrices --
+// leaves the solve to as many CUs as there are matrices, one row block after the other: ahead in two whole-call probes (1536 x 200:
+// 5.48 -> 5.36 ms, 640 x 256: 0.89 -> 0.85), no per-column table yet: not taken.  docs/EXPERIMENTS.md G29.)
+static inline int bgp_panel_fused_wgs(int nrb, int B, int ncu) {
+  const int B8 = 8 * ((B + 7) / 8), s = ncu / B8;
+  return s < 1 ? 1 : (s > nrb ? (nrb < 1 ? 1 : nrb) : s);
+}
+static inline bool bgp_panel_fused_rule(int nrb, int B, int ncu) { return nrb >= 2 && bgp_panel_fused_wgs(nrb, B, ncu) >= 2; }
 static inline size_t ps_flag_words(int B, int nblk) { return PS_HDR + (size_t)B * nblk * (8 + 2 * (size_t)nblk); }
 // Batch sizes at which the launch-free factorisation wins over the multi-launch schedule (tools/persist_probe.py on MI355X,
 // DESIGN.md section 4; wall time per LML call, launch schedule / launch-free, by n and number of matrices):

@@ -277,6 +277,21 @@ static __device__ __forceinline__ void pf_afrag_issue(const double* __restrict__
     af[4 * g + 3] = v[1];
   }
 }
+// (half of it: the k-groups 4 H .. 4 H + 3 -- entries 16 H .. 16 H + 15 of pf_afrag_issue's image -- for a caller that has
+// registers for half a fragment set at a time: panel_kernel, bgp_chol.hip)
+template <int H>
+static __device__ __forceinline__ void pf_afrag_issue_half(const double* __restrict__ rowp, int lk, double (&af)[16]) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  const d2v* const q = reinterpret_cast<const d2v*>(rowp + 4 * lk);
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const d2v u = q[8 * (4 * H + g)], v = q[8 * (4 * H + g) + 1];
+    af[4 * g] = u[0];
+    af[4 * g + 1] = u[1];
+    af[4 * g + 2] = v[0];
+    af[4 * g + 3] = v[1];
+  }
+}
 static __device__ __forceinline__ void pf_afrag_transpose(double (&af)[32]) {
 #pragma unroll
   for (int g = 0; g < 8; g++) {

@@ -297,12 +297,21 @@ static __device__ __forceinline__ void pf_pre_issue(const PsArgs& a, int b, int 
 // which the factorisation failed (status / lml of the walker are set here either way).  Called once per launch by
 // potrf_kernel and once per block column by the persistent chain kernel (ps_chain_kernel): the LDS tile is free again
 // when the function returns through its trailing barrier.
-template <int GEN, int STAT, int FORM, int PRE>
+// FU (panel_kernel, bgp_chol.hip: the diagonal block and the panel solve of a block column in ONE launch): several workgroups
+// factorise the same block side by side and only read it -- nothing is written in place.  The owner (L != nullptr) puts L_kk into
+// the 128 x 128 slot `L` (leading dimension 128: the slot of dW that the separate solve would have read W_kk from), z_k into `z`
+// and updates acc / lml / status; a co-worker (L == nullptr) writes nothing at all.  W_kk stays in LDS only.
+struct PfFuse {
+  double* L = nullptr;
+  double* z = nullptr;
+};
+template <int GEN, int STAT, int FORM, int PRE, int FU = 0>
 static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf, double* __restrict__ Wbuf,
                                                double* __restrict__ yw, double* __restrict__ accb,
                                                double* __restrict__ lml, int* __restrict__ status, int n, int ld,
                                                size_t mstride, int ystride, int nblk, int k, const PfGen& gen,
-                                               bool inlds, unsigned* wrow, const PsArgs& pa, PfPre& pre) {
+                                               bool inlds, unsigned* wrow, const PsArgs& pa, PfPre& pre,
+                                               const PfFuse& fu = PfFuse()) {
   // PRE (the single chain workgroup of the launch-free factorisation): request the operands of pf_chain_next(k) behind the
   // last step when the tile workers have handed them over by then (struct PfPre)
   // inlds (chain kernel, k > 0): the block and its right-hand side are in LDS already (pf_chain_next left them there)
@@ -323,6 +332,9 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   const int lr = lane & 15, lk = lane >> 4;
   double* T = Kbuf + (size_t)b * mstride + (size_t)(k * 128) * ld + k * 128;
   double* yk = yw + (size_t)b * ystride + k * 128;
+  double* const To = FU ? fu.L : T;     // where L_kk goes
+  const int ldo = FU ? 128 : ld;
+  const bool wr = FU ? fu.L != nullptr : true;  // this workgroup writes results
   PF_T(0);
 
   if (GEN) {
@@ -358,7 +370,7 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   __syncthreads();
   PF_T(1);
 
-  double* Wg = GEN ? nullptr : Wbuf + ((size_t)b * nblk + k) * (128 * 128);
+  double* Wg = (GEN || FU) ? nullptr : Wbuf + ((size_t)b * nblk + k) * (128 * 128);
   int failed = 0;
   d4 xpend = (d4){0.0, 0.0, 0.0, 0.0};  // wave 0: X_{sb,sb-1}^T, written in place one step later (the update
                                         // waves still read the unscaled block T_{sb,sb-1} during this step)
@@ -491,12 +503,12 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
         pf_wfinish(acc, s, Minv, Wg, p, J, lane);
       }
       // row block sb-2 of L is final and visible: stream it out now (lower triangle, 16-byte pairs)
-      if (!GEN && sb >= 2 && sb <= 6) {  // (the last step is the update waves' busiest: blocks 5..7 go out after the loop)
+      if (!GEN && wr && sb >= 2 && sb <= 6) {  // (the last step is the update waves' busiest: blocks 5..7 go out after the loop)
         const int R = sb - 2, ut = u6 * 64 + lane;  // 384 update threads: 24 per row
         const int rr = ut / 24, c0 = ut - 24 * rr, row = R * 16 + rr;
         for (int seg = c0; seg < 8 * R + 8; seg += 24) {
           if (2 * seg <= row)
-            *reinterpret_cast<d2*>(T + (size_t)row * ld + seg * 2) = *reinterpret_cast<const d2*>(&s[row * PF_LD + seg * 2]);
+            *reinterpret_cast<d2*>(To + (size_t)row * ldo + seg * 2) = *reinterpret_cast<const d2*>(&s[row * PF_LD + seg * 2]);
         }
       }
       // last step: rows <= 5 of W are complete -> the terms K <= 5 of row 7 (one block per update wave)
@@ -515,7 +527,7 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   }
   if (!failed && w == 4) pf_check_diag(s, 7, lane, lds.fail, PF_LD);  // the last sub-block: read behind the next barrier
   if (failed) {
-    if (tid == 0) {
+    if (tid == 0 && wr) {
       status[b] = k * 128 + failed;  // 1-based index of the failing pivot
       lml[b] = -INFINITY;            // sklearn/_gpr.py:588-589
     }
@@ -525,20 +537,20 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   // ---- L_kk out.  Only the lower triangle is written (16-byte stores; the element right of the diagonal in
   // a straddling pair is junk nobody reads: every consumer of this tile masks j <= i).  Block (7, 6) is still
   // in the panel wave's registers and goes out from there.  The stores drain while row 7 of W is formed.
-  if (!GEN) {
+  if (!GEN && wr) {
     const int seg = tid & 63, rbase = tid >> 6;
 #pragma unroll
     for (int i = 10; i < 16; i++) {  // row blocks 5, 6 and 7 (0..4 went out inside the loop)
       const int row = rbase + 8 * i;
       if (2 * seg <= row && !(row >= 112 && seg >= 48 && seg < 56))
-        *reinterpret_cast<d2*>(T + (size_t)row * ld + seg * 2) = *reinterpret_cast<const d2*>(&s[row * PF_LD + seg * 2]);
+        *reinterpret_cast<d2*>(To + (size_t)row * ldo + seg * 2) = *reinterpret_cast<const d2*>(&s[row * PF_LD + seg * 2]);
     }
   }
   // ---- row 7 of W: last term (K = 6) and the multiplication by -M_7
   if (w == 0) {
-    if (!GEN) {
+    if (!GEN && wr) {
 #pragma unroll
-      for (int r = 0; r < 4; r++) T[(size_t)(7 * 16 + lr) * ld + 6 * 16 + lk + 4 * r] = xpend[r];
+      for (int r = 0; r < 4; r++) To[(size_t)(7 * 16 + lr) * ldo + 6 * 16 + lk + 4 * r] = xpend[r];
     }
     d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
     acc = pf_wsum(acc, s, Minv, xrow0 + 16 * PF_MLD, 7, 6, 6, 7, lane);
@@ -554,7 +566,7 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   __syncthreads();
   failed = fail_lds;  // (a failure inside the last 16 pivots)
   if (failed) {
-    if (tid == 0) {
+    if (tid == 0 && wr) {
       status[b] = k * 128 + failed;
       lml[b] = -INFINITY;
     }
@@ -578,14 +590,14 @@ static __device__ __forceinline__ int pf_block(int b, double* __restrict__ Kbuf,
   double zv = 0.0;
   if (tid < 128) {
     zv = (zpart[tid] + zpart[128 + tid]) + (zpart[256 + tid] + zpart[384 + tid]);
-    if (!GEN) yk[tid] = zv;
+    if (!GEN && wr) (FU ? fu.z : yk)[tid] = zv;
     zpart[tid] = zv;  // (a thread reads and writes its own column only: z stays in LDS for pf_chain_next)
   }
   double zz = zv * zv;
   for (int o = 32; o > 0; o >>= 1) zz += __shfl_xor(zz, o);
   if (lane == 0) red[8 + w] = zz;
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0 && wr) {
     double ldt = red[0] + red[1];  // threads 0..127 (waves 0 and 1) hold the diagonal and z
     double zzt = red[8] + red[9];
     ldt += ld_prev;
@@ -638,6 +650,63 @@ static __device__ __forceinline__ void pf_diag_update(d4 (&dt)[5], const double*
       a0[u] = a1[u];
       b0[u] = b1[u];
     }
+  }
+}
+
+// (The launch-free kernel is held instruction for instruction to what it was before the two were factored out of pf_chain_next:
+// y travels by value -- read through a reference to the caller's array it was scheduled differently.)
+// The panel solve of ONE 128-row block against the W_kk that pf_block left in LDS -- step 1 of pf_chain_next below, and the solve
+// of panel_kernel (bgp_chol.hip) -- in two halves, so that a caller can put its own loads between them.
+//   pf_solve_mma: x = A W_kk^T for this wave's 16 rows; `af` holds their A fragments (pf_afrag_issue + pf_afrag_transpose), W_kk
+//   sits transposed in the upper triangle of the tile `s`, its diagonal blocks in `Minv`; chunk c of k only reaches the column
+//   blocks j >= c.  (The W operands of k-step t+1 are read while k-step t multiplies: with the reads placed just in front of their
+//   MFMAs the two waves of a SIMD stalled on LDS together -- the second one finished its 144 MFMAs 5.6 us after the first.)
+//   `mid` is called between the k-steps 15 and 16, when af[0 .. 15] have been used up (panel_kernel requests operands there).
+template <class Mid>
+static __device__ __forceinline__ void pf_solve_mma(const double (&af)[32], const double* s, const double* Minv, int lr, int lk,
+                                                    d4 (&x)[8], Mid&& mid) {
+  double bq[2][8];
+#pragma unroll
+  for (int j = 1; j < 8; j++) bq[0][j] = s[lk * PF_LD + j * 16 + lr];
+  bq[0][0] = Minv[lr * PF_MLD + lk];
+#pragma unroll
+  for (int t = 0; t < 32; t++) {
+    const int c = t >> 2, cur = t & 1, nxt = cur ^ 1;
+    if (t + 1 < 32) {
+      const int cn = (t + 1) >> 2, kn = (t + 1) & 3;
+      // column block cn: the diagonal block of W (its upper part holds zeros); j > cn: W[j][cn]^T in the upper triangle
+      bq[nxt][cn] = Minv[cn * 16 * PF_MLD + lr * PF_MLD + 4 * kn + lk];
+#pragma unroll
+      for (int j = cn + 1; j < 8; j++) bq[nxt][j] = s[(cn * 16 + 4 * kn + lk) * PF_LD + j * 16 + lr];
+    }
+    const double av = af[t];
+#pragma unroll
+    for (int j = c; j < 8; j++) x[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq[cur][j], x[j], 0, 0, 0);
+    if (t == 15) mid();
+  }
+}
+//   pf_solve_out: X out, in place over the block `Ab`, and the right-hand side ydst[row] = y[row] - (X z_k)[row] (z_k in `zl`, one
+//   row per 16 lanes, fixed shuffle order: the arithmetic of trsm4_kernel); yv = this lane's four entries of y (rows 16 w + lk + 4 r).
+static __device__ __forceinline__ void pf_solve_out(const d4 (&x)[8], const double* zl, double* Ab, int ld, int w, int lr, int lk,
+                                                    d4 yv, double* ydst) {
+  double zc[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) zc[j] = zl[16 * j + lr];
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int row = 16 * w + lk + 4 * r;
+    double part = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const double xv = x[j][r];
+      Ab[(size_t)row * ld + 16 * j + lr] = xv;
+      part = __builtin_fma(xv, zc[j], part);  // (trsm4_kernel's `part += x * zc[j]` is contracted the same way)
+    }
+    part += __shfl_xor(part, 1);
+    part += __shfl_xor(part, 2);
+    part += __shfl_xor(part, 4);
+    part += __shfl_xor(part, 8);
+    if (lr == 0) ydst[row] = yv[r] - part;
   }
 }
 
@@ -713,28 +782,7 @@ static __device__ __forceinline__ int pf_chain_next(const PsArgs& a, int b, int 
   d4 x[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) x[j] = (d4){0.0, 0.0, 0.0, 0.0};
-  // (the W operands of k-step t+1 are read while k-step t multiplies: with the reads placed just in front of their MFMAs the
-  // two waves of a SIMD stalled on LDS together -- the second one finished its 144 MFMAs 5.6 us after the first)
-  {
-    double bq[2][8];
-#pragma unroll
-    for (int j = 1; j < 8; j++) bq[0][j] = s[lk * PF_LD + j * 16 + lr];
-    bq[0][0] = Minv[lr * PF_MLD + lk];
-#pragma unroll
-    for (int t = 0; t < 32; t++) {
-      const int c = t >> 2, cur = t & 1, nxt = cur ^ 1;
-      if (t + 1 < 32) {
-        const int cn = (t + 1) >> 2, kn = (t + 1) & 3;
-        // column block cn: the diagonal block of W (its upper part holds zeros); j > cn: W[j][cn]^T in the upper triangle
-        bq[nxt][cn] = Minv[cn * 16 * PF_MLD + lr * PF_MLD + 4 * kn + lk];
-#pragma unroll
-        for (int j = cn + 1; j < 8; j++) bq[nxt][j] = s[(cn * 16 + 4 * kn + lk) * PF_LD + j * 16 + lr];
-      }
-      const double av = af[t];
-#pragma unroll
-      for (int j = c; j < 8; j++) x[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bq[cur][j], x[j], 0, 0, 0);
-    }
-  }
+  pf_solve_mma(af, s, Minv, lr, lk, x, [] {});
   // (the D tiles are fetched under the epilogue: with them in flight during the solve the kernel spilled)
 #pragma unroll
   for (int u = 0; u < 5; u++) {
@@ -746,27 +794,7 @@ static __device__ __forceinline__ int pf_chain_next(const PsArgs& a, int b, int 
     }
   }
   if (tr && tid == 0) tr[J * 8 + 4] = wall_clock64();
-  {
-    double zc[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) zc[j] = zl[16 * j + lr];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = 16 * w + lk + 4 * r;
-      double part = 0.0;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const double xv = x[j][r];
-        Ab[(size_t)row * ld + 16 * j + lr] = xv;
-        part = __builtin_fma(xv, zc[j], part);  // (trsm4_kernel's `part += x * zc[j]` is contracted the same way)
-      }
-      part += __shfl_xor(part, 1);
-      part += __shfl_xor(part, 2);
-      part += __shfl_xor(part, 4);
-      part += __shfl_xor(part, 8);
-      if (lr == 0) ylds[row] = yv[r] - part;
-    }
-  }
+  pf_solve_out(x, zl, Ab, ld, w, lr, lk, (d4){yv[0], yv[1], yv[2], yv[3]}, ylds);
   __syncthreads();  // nobody reads W in the tile any more (X's stores drain while it goes into the tile)
   if (tr && tid == 0) tr[J * 8 + 5] = wall_clock64();
 #pragma unroll

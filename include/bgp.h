@@ -333,16 +333,17 @@ int bgp_posterior_batch_gram(bgp_ctx* ctx, int B, const double* K, int use_alpha
 int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const double* kss, const double* Kss, double* mean,
                            double* var, double* cov);
 
-/* Number of walker groups (HIP streams) an LML batch is split over: one group's kernels fill the tail
- * of the other group's launches.  Default: automatic -- two groups for batches of >= 64 matrices (+3.7 % at
- * n = 2048 x 128 matrices on MI355X, results bit-identical), one group below that (every group's dependent
- * chain is as long as the whole batch's, nothing to gain).  This call, or the environment variable
- * BGP_STREAMS read at context creation, forces a fixed group count.
+/* Number of walker groups (HIP streams) an LML batch of the launch schedule is split over; results are bit-identical for
+ * every count.  Default: ONE group.  With k > 1 groups a batch of at least 64 matrices (or, after this call, of at least 16) is
+ * factorised as k slices side by side, one group's kernels filling the tails of another's launches.  Two groups were the
+ * default for batches of >= 64 matrices while that paid (+3.7 % at n = 2048 x 128 matrices on MI355X in round 2, nothing any
+ * more in round 6); the fused panel launches (bgp_set_panel_fused) take whole CUs, and one group measured faster with them
+ * (docs/EXPERIMENTS.md G29).  This call, or the environment variable BGP_STREAMS read at context creation, fixes the count.
  *
  * Environment switches the library reads (a BGP_* variable it does not read is reported once on stderr).  Schedule switches --
  * each selects between code paths whose results are bit-identical (tests/test_gpu_edge.py, tests/test_gpu_persist.py):
  *   BGP_STREAMS (this call), BGP_PANELS (block columns per trailing update, 1..64; default 4 from n = 1536, else 2), BGP_PERSIST
- *   (bgp_set_persist), BGP_PS_PAIR (0 / 1: one or two chain workgroups per matrix on the launch-free path; default by shape),
+ *   (bgp_set_persist), BGP_PANEL_FUSED (bgp_set_panel_fused), BGP_PS_PAIR (0 / 1: one or two chain workgroups per matrix on the launch-free path; default by shape),
  *   BGP_PS_GEN (0 / 1: the Gram blocks of a launch-free LML batch are built by a kernel in front of it / by its own tile workers
  *   at the head of their ticket list; default by shape), BGP_SYRK_GEN (0 / 1: on the launch schedule, every Gram block by the
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
@@ -388,6 +389,15 @@ int bgp_persist_stats(bgp_ctx* ctx, long long* out4);
  * block with the Gram kernel in front).  out[0] = LML batches (per walker-group stream) factorised that way by this context,
  * out[1] = generating launches among their trailing updates. */
 int bgp_lml_gen_stats(bgp_ctx* ctx, long long* out2);
+/* Launch schedule, LML path: the diagonal factorisation and the panel solve of a block column in ONE launch (panel_kernel,
+ * csrc/bgp_chol.hip: the inverse W_kk of the diagonal factor stays in LDS, and CUs that idle during a separate potrf launch
+ * factorise the block redundantly and share the solve; same bits as potrf_kernel + trsm4_kernel): 1 = every block column that has
+ * a solve, 0 = never, -1 = as BGP_PANEL_FUSED says (unset: where it measured faster on MI355X, bgp_panel_fused_rule).  A scheduling
+ * choice behind cholesky() / cho_solve() of sklearn/_gpr.py:587-597.  With timing on, a fused launch counts under "trsm", which is
+ * then the panel phase of those block columns. */
+int bgp_set_panel_fused(bgp_ctx* ctx, int mode);
+/* out[0] = fused panel launches enqueued by this context. */
+int bgp_panel_fused_stats(bgp_ctx* ctx, long long* out1);
 /* Enable (1) / disable (0) per-kernel event timing (adds synchronisation; off by default). */
 int bgp_set_timing(bgp_ctx* ctx, int enable);
 /* Debugging aid (BGP_PS_TRACE=1): in-kernel wall-clock stamps (100 MHz) of the last launch-free call.  dims = {matrices,
