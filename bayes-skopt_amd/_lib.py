@@ -96,6 +96,7 @@ SIGNATURES = {
     "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -616,6 +617,43 @@ class Context:
                                              _p(hi), float(gtol), int(max_iter), _p(x), _p(mean), _p(var), _p(iters), _p(evals),
                                              _p(status)), "bgp_minimize_starts")
         return {"x": x, "mean": mean, "var": var, "iters": iters, "evals": evals, "status": status}
+
+    # ---- partial dependence of the surrogate mean (bgp_pdep.hip)
+    def partial_dependence(self, H_kernel, Xs, grids, panels):
+        """``bgp_partial_dependence``: the mean of the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2)) averaged over the sample
+        rows ``Xs`` (S, d) with the panel's coordinates replaced by grid values.  ``grids``: d 1-D arrays (1 .. 256 values each);
+        ``panels``: ``(k1, -1)`` / ``(k1,)`` / ``k1`` for a curve, ``(k1, k2)`` for a map.  Returns one array per panel, (B, G1) or
+        (B, G1, G2), in normalised-target units.  Needs d <= 32."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xs = _c(np.atleast_2d(Xs))
+        if Xs.shape[1] != self.d:
+            raise ValueError(f"sample rows must have {self.d} columns, got {Xs.shape[1]}")
+        grids = [_c(np.asarray(g, dtype=np.float64).reshape(-1)) for g in grids]
+        if len(grids) != self.d:
+            raise ValueError(f"one grid per dimension: {self.d} expected, got {len(grids)}")
+        ng = np.array([len(g) for g in grids], dtype=np.int32)
+        gmax = max(int(ng.max()), 1)
+        grid = np.empty((gmax, self.d))
+        for k, g in enumerate(grids):  # (rows past a dimension's grid are not read: its last value, so that a warp sees a number)
+            grid[:len(g), k] = g
+            grid[len(g):, k] = g[-1] if len(g) else 0.5
+        pan = np.empty((len(panels), 2), dtype=np.int32)
+        for i, pnl in enumerate(panels):
+            pnl = tuple(np.atleast_1d(pnl).astype(int))
+            pan[i] = (pnl[0], pnl[1] if len(pnl) > 1 else -1)
+        shapes = [(int(ng[a]),) if b < 0 else (int(ng[a]), int(ng[b])) for a, b in pan
+                  if 0 <= a < self.d and -1 <= b < self.d] if len(pan) else []
+        total = int(sum(int(np.prod(s)) for s in shapes))
+        out = np.empty((B, max(total, 1)))
+        _check(self._lib.bgp_partial_dependence(self._h, B, _p(H), Xs.shape[0], _p(Xs), gmax, _p(ng), _p(grid), len(pan), _p(pan),
+                                                _p(out)), "bgp_partial_dependence")
+        res, o = [], 0
+        for s in shapes:
+            sz = int(np.prod(s))
+            res.append(out[:, o:o + sz].reshape((B,) + s).copy())
+            o += sz
+        return res
 
     # ---- pathwise posterior function draws (bgp_paths_*; DESIGN.md section 14)
     def paths_begin(self, pidx, H_kernel, log_s2, omega, phase, w, eps):

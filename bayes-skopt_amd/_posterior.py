@@ -4,6 +4,8 @@ the reference does for every kernel (``sklearn/_gpr.py:582``), and the device fa
 predictive products (``ctx.*_gram``).  Every method takes the estimator and reads ``gp._ctx`` at the call: a backend holds no
 context.  What only the canonical form has -- the resident sampler, the device acquisitions, the fantasy fast path, the
 device ``mvn`` draw, the sharded asynchronous gather -- is behind ``canonical``.  Predictions: normalised-target units."""
+import sys
+
 import numpy as np
 from sklearn.base import clone
 
@@ -29,6 +31,58 @@ def noise_off(H):
     Hk = H.copy()
     Hk[:, -1] = -np.inf
     return Hk
+
+
+_pd_told = []
+
+
+def _pd_tell_once(why):
+    """One line on stderr, once per process: a partial dependence computed through ``predict`` on synthesised rows."""
+    if not _pd_told:
+        _pd_told.append(True)
+        print("[bayes_skopt_amd] partial_dependence: through predict on synthesised rows (%s)" % why, file=sys.stderr, flush=True)
+
+
+PD_ROWS = 8192  # synthesised rows per predict of the fallback
+
+
+def partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why):
+    """The fallback of ``partial_dependence``: per panel, the sample rows with the panel's columns overwritten cell by cell, at most
+    ``PD_ROWS`` rows per ``predict``, the mean, the average over the samples.  ``thetas=None``: the resident posterior with
+    ``kernel_`` as it is; otherwise one item per chain row -- under ``warp_inputs`` one row at a time with the row's own warp
+    (``BayesGPR._row_warps``), because every draw there has its own training inputs."""
+    _pd_tell_once(why)
+    Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
+    S = Xs.shape[0]
+    rows = None if thetas is None else np.atleast_2d(thetas)
+
+    def means(X):
+        if rows is None:
+            return gp._post.predict(gp, X, False)[0]
+        if gp.warp_inputs:
+            with gp._row_warps() as install:
+                return np.stack([gp._post.rows_predict(gp, install(r), X, True)[0][0] for r in rows])
+        return gp._post.hyper_predict(gp, rows, X, True)[0]
+
+    out = []
+    for k1, k2 in panels:
+        axes = [(k1, np.asarray(grids[k1], dtype=np.float64))] + ([(k2, np.asarray(grids[k2], dtype=np.float64))] if k2 >= 0 else [])
+        shape = tuple(len(g) for _k, g in axes)
+        ncell = int(np.prod(shape))
+        vals = None
+        step = max(1, PD_ROWS // S)
+        for c0 in range(0, ncell, step):
+            cells = range(c0, min(ncell, c0 + step))
+            X = np.repeat(Xs[None, :, :], len(cells), axis=0)
+            for i, c in enumerate(cells):
+                for (k, g), gi in zip(axes, np.unravel_index(c, shape)):
+                    X[i, :, k] = g[gi]
+            m = np.asarray(means(X.reshape(-1, Xs.shape[1])))
+            if vals is None:
+                vals = np.empty((m.shape[0], ncell))
+            vals[:, c0:c0 + len(cells)] = m.reshape(m.shape[0], len(cells), S).mean(axis=2)
+        out.append(vals.reshape((vals.shape[0],) + shape))
+    return out
 
 
 class PendingLml:
@@ -152,6 +206,21 @@ class CanonicalPosterior:
         return gp._ctx.minimize_starts(0, gp._canonical(gp._kernel_theta_for_predict()), y_mean, y_std, kappa, X0, lo, hi,
                                        gtol=gtol, max_iter=max_iter)
 
+    def partial_dependence(self, gp, thetas, Xs, grids, panels):
+        """(per panel a (B, G1) or (B, G1, G2) array in normalised-target units, "device" | "host").  ``thetas=None``: the resident
+        median GP (B = 1); a block of chain rows: one batched build, then ONE device call over all of them
+        (``bgp_partial_dependence``).  More than 32 dimensions, and chain rows under ``warp_inputs`` (every
+        row has its own training inputs), go through ``predict``."""
+        if gp._X_train_.shape[1] > 32 or (thetas is not None and gp.warp_inputs):
+            why = "more than 32 dimensions" if gp._X_train_.shape[1] > 32 else "hyper-posterior rows with input warping"
+            return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why), "host"
+        if thetas is None:
+            self.make_resident(gp)
+            H = gp._canonical(gp._kernel_theta_for_predict())
+        else:
+            H = self.build_rows(gp, thetas)
+        return gp._ctx.partial_dependence(H, Xs, grids, panels), "device"
+
     def pvrs(self, gp, X, T, has_alpha_vec):
         Hk = gp._canonical(gp._kernel_theta_for_predict())
         raise_if_not_pd(gp._ctx.pvrs_prepare(Hk, has_alpha_vec))
@@ -238,6 +307,9 @@ class GramPosterior:
     def grad_x(self, gp, x, Xt):
         """``kernel_.gradient_x`` is ``kernels.gradient_x`` (skopt's method restated for scikit-learn kernel objects)."""
         return gradient_x(gp.kernel_, x, Xt), gp.kernel_(x[None, :], Xt)[0]
+
+    def partial_dependence(self, gp, thetas, Xs, grids, panels):
+        return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, "generic kernel tree"), "host"
 
     def pvrs(self, gp, X, T, has_alpha_vec):
         """PVRS through the bordered-inverse identity of ``bgp_pvrs``,

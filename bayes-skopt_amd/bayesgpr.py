@@ -703,6 +703,42 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         grad_std[nz] = dvar[nz] / (2.0 * y_std[nz])[:, None] * self.y_train_std_**2
         return y_mean, y_std, grad_mean, grad_std
 
+    def partial_dependence(self, Xs, grids, panels=None, thetas=None, return_path=False):
+        """Partial dependence of the predictive mean: per panel the mean averaged over the sample rows ``Xs`` (S, d; transformed
+        space) with the panel's coordinates replaced by grid values -- ``grids``: one 1-D array per dimension (transformed space, at
+        most 256 values), ``panels``: ``k`` / ``(k,)`` / ``(k, -1)`` for a curve, ``(k1, k2)`` for a map, None for every dimension
+        and every pair k1 < k2.  Returns a list with one array per panel, (G1,) or (G1, G2) in y units, for the median GP
+        (``thetas=None``), or (B, G1) / (B, G1, G2) for a block of B chain rows.  Canonical kernels in up to 32 dimensions: ONE
+        device call for all panels and rows (``bgp_partial_dependence``; the context-level warp of
+        ``warp_inputs`` is applied to samples and grids on the device).  Generic kernel trees, more dimensions, and chain rows
+        under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" | "host"."""
+        Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        d = self._X_train_.shape[1]
+        grids = [np.asarray(g, dtype=np.float64).reshape(-1) for g in grids]
+        if Xs.shape[1] != d or len(grids) != d:
+            raise ValueError(f"sample rows need {d} columns and one grid per dimension is needed")
+        if self.warp_inputs:
+            validate_zeroone(Xs)
+            validate_zeroone(np.concatenate(grids))
+        if panels is None:
+            panels = [(k, -1) for k in range(d)] + [(a, b) for a in range(d) for b in range(a + 1, d)]
+        pan = []
+        for pnl in panels:
+            pnl = tuple(int(v) for v in np.atleast_1d(pnl))
+            pnl = (pnl[0], pnl[1] if len(pnl) > 1 else -1)
+            if not (0 <= pnl[0] < d and -1 <= pnl[1] < d and pnl[0] != pnl[1]):
+                raise ValueError(f"panel {pnl} is not a dimension or a pair of two different dimensions of {d}")
+            pan.append(pnl)
+        if not pan or Xs.shape[0] < 1 or any(not 1 <= len(g) <= 256 for g in grids):
+            raise ValueError("partial_dependence needs a panel, a sample row and 1 .. 256 grid values per dimension")
+        vals, path = self._post.partial_dependence(self, thetas, Xs, grids, pan)
+        vals = [self.y_train_std_ * v + self.y_train_mean_ for v in vals]
+        if thetas is None:
+            vals = [v[0] for v in vals]
+        return (vals, path) if return_path else vals
+
     @contextmanager
     def _row_warps(self):
         """Yields ``install(row)``, which gives the estimator chain row ``row``'s own input warp (its own training inputs)

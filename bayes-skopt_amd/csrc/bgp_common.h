@@ -484,6 +484,8 @@ int bgp_launch_kcross_matvec(bgp_ctx* ctx, int nb, const double* dH, int m, cons
 int bgp_launch_warp(bgp_ctx* c, hipStream_t st, const double* dX, const double* dW, double* dout, int n, int B,
                     size_t ostride);
 int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented);
+// bgp_post.hip: `rows` query rows to the device, through the context-level warp when one is set (predict's staging; bgp_pdep.hip)
+int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows);
 // n <= 128: K-build + factorisation + LML of the slice [off, off+B) in ONE launch (bgp_chol.hip, potrf_kernel<1,..>)
 int bgp_launch_lml_small(bgp_ctx* ctx, int off, int B, hipStream_t st);
 int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int augmented, int gen = 0);

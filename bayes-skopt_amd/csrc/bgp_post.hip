@@ -155,7 +155,7 @@ static int post_chunk(int B, size_t per_item, size_t budget, bool round8) {
 
 // Query points to the device, through the context-level warp when one is set: BayesGPR.predict warps them with the current warpers
 // (bask/bayesgpr.py:630-632), PVRS compares candidates and Thompson points in the warped space (bask/acquisition.py:324-327).
-static int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows) {
+int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows) {
   BGP_HIP(bgp_memcpy_async(dst, src, (size_t)rows * c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return c->has_warp ? bgp_launch_warp(c, c->stream, dst, c->dwarp, dst, rows, 1, 0) : BGP_OK;
 }

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi, inverse_unrounded
+from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence
 
 __all__ = ["Optimizer"]
 
@@ -245,6 +245,11 @@ class Optimizer:
         ``mean + kappa std``, found on the device from the best observed point and ``n_random_starts`` random points
         (``utils.expected_optimum``).  Returns (x, value, info)."""
         return expected_optimum(self._result(), kappa=kappa, n_random_starts=n_random_starts, random_state=random_state)
+
+    def partial_dependence(self, **kw):
+        """What the surrogate looks like right now: 1-D curves and 2-D maps of its partial dependence
+        (``utils.partial_dependence`` on the current result, same keyword arguments)."""
+        return partial_dependence(self._result(), **kw)
 
     def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed, minimizer="scipy"):
         """Function draws (device ``sample_y``) at [expected optimum, n_space_samples random points]:

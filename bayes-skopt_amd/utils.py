@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -237,6 +237,62 @@ def expected_optimum(res, kappa=0.0, n_random_starts=20, random_state=None, gtol
     info = {"path": "device", "status": out["status"], "iters": out["iters"], "evals": out["evals"], "fun": fun,
             "x_transformed": out["x"], "mean": out["mean"], "var": out["var"], "best": best}
     return x, float(fun[best]), info
+
+
+def _pd_grid(dim, n_points):
+    """(grid in the original space, the same in the transformed space) of one dimension: ``n_points`` values equally spaced in the
+    TRANSFORMED space for a Real dimension (log-spaced for a log-uniform one), the distinct integers (at most ``n_points`` of them)
+    for an Integer one, every category for a Categorical one."""
+    from .space import Categorical, Integer
+
+    if isinstance(dim, Categorical):
+        orig = list(dim.categories)
+    elif isinstance(dim, Integer):
+        orig = [int(v) for v in np.unique(np.round(np.linspace(dim.low, dim.high, min(n_points, dim.high - dim.low + 1))))]
+    else:
+        t = np.linspace(0.0, 1.0, n_points)
+        return np.asarray(dim.inverse_transform(t), dtype=np.float64), t
+    return np.asarray(orig, dtype=object if isinstance(dim, Categorical) else np.int64), np.asarray(dim.transform(orig), dtype=np.float64)
+
+
+def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, samples=None, n_gp_samples=0, random_state=None):
+    """The data of the "plot objective" figure: the partial dependence of the surrogate mean on single dimensions and on pairs,
+    i.e. the mean of ``res.models[-1]`` averaged over ``n_samples`` points of the space (``space.rvs_transformed(n_samples,
+    random_state)``, or the given ``samples`` in the original space) with one or two coordinates swept over a grid (``_pd_grid``:
+    at most ``n_points`` values, at most 256).  ``dims``: the dimensions (default all); ``pairs``: "all" (every k1 < k2 of
+    ``dims``), None, or a list of pairs.  Returns a dict: ``"dims"`` {k: (grid, values)}, ``"pairs"`` {(k1, k2): (grid1, grid2,
+    values[G1, G2])}, grids in the original space and values in y units, and ``"path"``: "device" when every panel came from ONE
+    device call (``bgp_partial_dependence``), "host" when they came through ``predict`` on synthesised rows.
+    ``n_gp_samples > 0``: the fully Bayesian curve -- the average over that many rows drawn from ``chain_`` with
+    ``random_state`` -- and under ``"band"`` {k: (5 %, 95 %)} the per-draw band of the 1-D curves; the default is the median GP,
+    which ``res.models[-1]`` predicts with."""
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    d = space.n_dims
+    dims = list(range(d)) if dims is None else [int(k) for k in dims]
+    if pairs == "all":
+        pairs = [(a, b) for i, a in enumerate(dims) for b in dims[i + 1:]]
+    pairs = [] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    Xs = space.rvs_transformed(n_samples, random_state=rng) if samples is None else space.transform(samples)
+    both = [_pd_grid(dim, n_points) for dim in space.dimensions]
+    panels = [(k, -1) for k in dims] + pairs
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    vals, path = reg.partial_dependence(Xs, [g[1] for g in both], panels, thetas=thetas, return_path=True)
+    out = {"dims": {}, "pairs": {}, "path": path}
+    if thetas is not None:
+        out["band"] = {k: tuple(np.percentile(v, [5.0, 95.0], axis=0)) for k, v in zip(dims, vals)}
+        vals = [v.mean(axis=0) for v in vals]
+    for k, v in zip(dims, vals):
+        out["dims"][k] = (both[k][0], v)
+    for (a, b), v in zip(pairs, vals[len(dims):]):
+        out["pairs"][(a, b)] = (both[a][0], both[b][0], v)
+    return out
 
 
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):

@@ -292,6 +292,26 @@ int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, 
                        double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status);
 
 /*
+ * Partial dependence of the surrogate mean on one or two input dimensions: the data of the "plot objective"
+ * figure, for the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read: cross
+ * values carry none).  With S sample rows Xs (S*d) and a panel D = {k1} or {k1, k2} with grid values g (normalised-y units):
+ *   pd_b(D, g) = (1 / S) sum_s sum_j alpha_bj k_b(x_s[D <- g], X_j)
+ * evaluated from Q_sj = sum_{k not in D} (x_sk / l_k - X_jk / l_k)^2 and T_j(g) = sum_{k in D} (g_k / l_k - X_jk / l_k)^2 (both sums of
+ * squares, ascending dimension), k = k(Q + T): the mean of bgp_predict_batch on the S synthesised rows of every cell to the
+ * precision model's tolerance, not its bits.
+ * grid is gmax*d row-major: column k holds dimension k's grid in its first ng[k] rows (the rest is not read); samples and grid rows
+ * go through the context-level warp as predict's queries do.  panels is P*2 ints: (k1, -1) or (k1, k2), k1 != k2, either order,
+ * repeats allowed.  out is B*total: panel p's block starts at the sum of the earlier panels' sizes and holds ng[k1] values, or
+ * ng[k1]*ng[k2] row-major with k1's index slow.  A panel's values do not depend on which panels or posteriors share the call, nor
+ * on its place in the list.
+ * Needs d <= 32, S >= 1 (at most 65535*16), P >= 1, 1 <= ng[k] <= gmax <= 256, panel indices in [0, d), at most 2^30 cells
+ * (BGP_ERR_INVALID before anything is launched) and B resident posteriors (BGP_ERR_STATE).
+ *   Replaces: the per-cell predict loop of skopt.plots.partial_dependence (reached from bask's plot_objective).
+ */
+int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
+                           const double* grid, int P, const int* panels, double* out);
+
+/*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
  * the host (z: n_draws*m), via a Cholesky factor of cov (+jitter) instead of numpy's SVD.
  * Replaces: sklearn sample_y (sklearn/_gpr.py:522-526) reached from BayesGPR.sample_y
