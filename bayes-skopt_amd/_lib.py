@@ -78,6 +78,8 @@ SIGNATURES = {
     "bgp_kernel_matrix": (C.c_int, [_vp, _dp, _dp]),
     "bgp_posterior_batch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
     "bgp_predict_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "bgp_posterior_batch_warped": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "bgp_predict_batch_warped": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "bgp_acq_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, C.c_int, _dp]),
     "bgp_acq_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, _dp]),
     "bgp_pvrs": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
@@ -435,7 +437,13 @@ class Context:
                                         _p(Ki) if want_K_inv else nul, _p(lml), _p(st)), name)
         return {"L": L, "alpha": a, "K_inv": Ki, "lml": lml, "status": st}
 
-    def posterior(self, H, want_L=False, want_alpha=True, want_K_inv=False):
+    def posterior(self, H, want_L=False, want_alpha=True, want_K_inv=False, warps=None):
+        """Batched posterior build; the posteriors stay resident.  ``warps`` (B, 2d): row b is built from the training inputs
+        through its OWN warp (``bgp_posterior_batch_warped``); such posteriors are read by ``predict_warped`` alone and
+        ``resident_H`` stays None, so the next plain consumer rebuilds."""
+        if warps is not None:
+            H, W, B = self._HW(H, warps)
+            return self._posterior("bgp_posterior_batch_warped", B, (_p(H), _p(W)), want_L, want_alpha, want_K_inv)
         H = self._H(H)
         res = self._posterior("bgp_posterior_batch", H.shape[0], (_p(H),), want_L, want_alpha, want_K_inv)
         if np.all(res["status"] == 0):
@@ -502,6 +510,18 @@ class Context:
         _check(self._lib.bgp_predict_batch(self._h, B, _p(H), m, _p(Xq), _p(mean), _p(var),
                                            _p(cov) if return_cov else nul), "bgp_predict_batch")
         return (mean, var, cov) if return_cov else (mean, var)
+
+    def predict_warped(self, H_kernel, Xq):
+        """(mean, var), each (B, m), of the first B per-row-warped resident posteriors (``posterior(H, warps=W)``): row b sees the
+        un-warped ``Xq`` through its own warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xq = _c(np.atleast_2d(Xq))
+        m = Xq.shape[0]
+        mean = np.empty((B, m))
+        var = np.empty((B, m))
+        _check(self._lib.bgp_predict_batch_warped(self._h, B, _p(H), m, _p(Xq), _p(mean), _p(var)), "bgp_predict_batch_warped")
+        return mean, var
 
     def acq(self, H_kernel, Xq, y_mean, y_std, kinds, params, n_samples):
         """Closed-form acquisitions (ACQ_EI / ACQ_MEAN / ACQ_LCB / ACQ_STD) of the resident posteriors at Xq, averaged

@@ -155,10 +155,16 @@ class CanonicalPosterior:
         inverse = np.asarray(inverse).ravel()
         return out[0][inverse], out[1][inverse], (out[2][inverse] if return_cov else None)
 
-    def hyper_predict(self, gp, thetas, X, noise_zero):
-        """(mean, var) of every hyper-posterior draw: one build over all rows, one predict."""
-        H = self.build_rows(gp, thetas)
-        return gp._ctx.predict(noise_off(H) if noise_zero else H, X)
+    def hyper_predict(self, gp, thetas, X, noise_zero, warps=None):
+        """(mean, var) of every hyper-posterior draw: one build over all rows, one predict.  ``warps`` (B, 2d): every row with
+        its own input warp -- its own training inputs and its own view of ``X`` -- still one build and one predict
+        (``bgp_posterior_batch_warped`` / ``bgp_predict_batch_warped``); the context-level warp is not touched."""
+        if warps is None:
+            H = self.build_rows(gp, thetas)
+            return gp._ctx.predict(noise_off(H) if noise_zero else H, X)
+        H = gp._canonical(np.atleast_2d(thetas))
+        raise_if_not_pd(gp._ctx.posterior(H, want_alpha=False, warps=warps)["status"], gp.kernel_)
+        return gp._ctx.predict_warped(noise_off(H) if noise_zero else H, X)
 
     def grad_x(self, gp, x, Xt):
         """(d k(x, X_i) / dx as (n, d), k(x, X_i)) at one (warped) query point, in closed form from H."""

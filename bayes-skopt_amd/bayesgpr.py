@@ -758,14 +758,25 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             self.create_warpers(*backup)
             self.rewarp()
 
+    _warp_rows_path = "auto"  # "loop": hyper-posterior rows under input warping one at a time (tests compare the two)
+
     def _predict_hyper_samples(self, thetas, X, noise_zero=True):
         """Posterior build + predict for a whole batch of hyper-posterior draws (what
         ``evaluate_acquisitions`` does one ``gpr.theta = chain_[i]`` at a time,
         ``bask/acquisition.py:112-125``): ONE batched device build, ONE batched predict.  With input warping every draw
-        carries its own warp, i.e. its own training inputs: one build + predict per draw (``:113-119``)."""
+        carries its own warp, i.e. its own training inputs (``:113-119``); rows are then ``chain_`` rows, kernel parameters
+        first and the 2d warp parameters behind them.  A canonical kernel still takes one build and one predict: the device
+        warps the training inputs and the queries per row (``CanonicalPosterior.hyper_predict(..., warps=...)``, DESIGN.md
+        section 17), and neither the estimator's warpers nor the context-level warp are touched.  A generic kernel tree, and
+        ``_warp_rows_path = "loop"``, install one row's warp after the other: one build + predict per draw.  Same bits."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         rows = np.atleast_2d(thetas)
-        if self.warp_inputs:
+        if self.warp_inputs and self._post.canonical and self._warp_rows_path == "auto":
+            validate_zeroone(X)
+            n_theta = len(self.kernel_.theta)
+            mean, var = self._post.hyper_predict(self, rows[:, :n_theta], X, noise_zero,
+                                                 warps=np.ascontiguousarray(rows[:, n_theta:]))
+        elif self.warp_inputs:
             validate_zeroone(X)
             mean, var = np.empty((len(rows), X.shape[0])), np.empty((len(rows), X.shape[0]))
             with self._row_warps() as install:

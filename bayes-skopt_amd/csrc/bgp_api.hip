@@ -237,6 +237,7 @@ static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, cons
   BGP_HIP(bgp_stream_sync(c->stream));
   if (dbg) fprintf(stderr, "upload_data: alloc %.3f ms, stage+enqueue %.3f ms, sync %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
   c->post_B = 0;
+  c->post_rowwarp = 0;
   c->has_warp = 0;  // new data: the caller re-installs the warp (bgp_ctx_set_warp)
   c->dXeff = c->dX;
   return BGP_OK;

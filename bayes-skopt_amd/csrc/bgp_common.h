@@ -172,6 +172,12 @@ struct bgp_ctx {
   // resident posterior state
   int post_B = 0;            // number of resident posteriors (0 = none)
   int post_gen = 0;          // bumped by every posterior build (a fantasy state checks that its posteriors are still there)
+  // per-row-warped resident posteriors (bgp_posterior_batch_warped): posterior b was built from dX through ITS OWN warp, so it
+  // goes with its own training inputs, not with dXeff.  Buffers of their own: a warped LML batch between build and predict
+  // overwrites dXwB / dwarpB.
+  int post_rowwarp = 0;      // the resident posteriors are per-row warped (bgp_refuse_rowwarp; ended by any build / new data / set_warp)
+  BgpDev<double> dXwP;       // post_B * n * d   warped training inputs of every resident posterior
+  BgpDev<double> dwarpP;     // post_B * 2d      their warp parameters (log space)
   std::vector<double> post_h;
   // scratch for predict / pvrs (grown on demand, carved through BgpScratch below)
   BgpDev<char> dscratch;
@@ -429,6 +435,17 @@ static inline int post_call(bgp_ctx* c, Body&& body) {
   return rc;
 }
 
+// Per-row-warped resident posteriors (bgp_posterior_batch_warped) go with their own warped training inputs: an entry point that
+// would combine them with the shared c->dXeff refuses, and launches nothing.
+#define BGP_REFUSE_ROWWARP(c, who)                                                                                     \
+  do {                                                                                                                 \
+    if ((c) && (c)->post_rowwarp) {                                                                                    \
+      bgp_set_error(who ": the resident posteriors are per-row warped (bgp_posterior_batch_warped): only "              \
+                        "bgp_predict_batch_warped reads them; build plain posteriors first");                          \
+      return BGP_ERR_STATE;                                                                                            \
+    }                                                                                                                  \
+  } while (0)
+
 // The context's scratch, carved by ONE layout per call (bgp_mem.h; every region on 16 bytes).  A carve may free and re-allocate
 // dscratch, so the pointers of an earlier one would dangle: while a BgpScratch that has carved is in scope, another carve of the
 // same context is refused.  (No scratch user calls another one inside that scope today.)
@@ -457,8 +474,11 @@ int bgp_grow_workspace(bgp_ctx* ctx, size_t doubles);
 // posterior build on the augmented matrices; use_alpha == 0 drops alpha_diag (PVRS quirk).  Kgram != nullptr: the B kernel
 // matrices come from the host (n x n each, bgp_gram.hip) instead of the device Gram build, h is not read.  want_Linv: L^-1
 // stays resident beside K^-1 (the draws read it; the LML gradient does not)
+// warp != nullptr (B x 2d, host): item b is built from c->dX through its own warp instead of c->dXeff; the warped inputs and the
+// warp parameters of all B items stay resident in c->dXwP / c->dwarpP (bgp_posterior_batch_warped)
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
-                        double* lml, int* status, const double* Kgram = nullptr, bool want_Linv = true);
+                        double* lml, int* status, const double* Kgram = nullptr, bool want_Linv = true,
+                        const double* warp = nullptr);
 // host kernel matrices -> working matrices (bgp_gram.hip)
 int bgp_gram_load(bgp_ctx* c, int nb, const double* K, int augmented, int use_alpha);
 
@@ -479,6 +499,10 @@ int bgp_launch_kcross_batch(bgp_ctx* ctx, int nb, const double* dH, int m, const
                             double* dout, int ldo, size_t ostride);
 int bgp_launch_kcross_matvec(bgp_ctx* ctx, int nb, const double* dH, int m, const double* dXq, int nx, const double* dXt,
                              double* dout, int ldo, size_t ostride, const double* vec, size_t svec, double* dpart);
+// ... with per-item queries dXq + b * qstride and training inputs dXt + b * xstride (stride 0: shared; the three above forward here)
+int bgp_launch_kcross_matvec_x(bgp_ctx* ctx, int nb, const double* dH, int m, const double* dXq, size_t qstride, int nx,
+                               const double* dXt, size_t xstride, double* dout, int ldo, size_t ostride, const double* vec,
+                               size_t svec, double* dpart);
 // Blocked Cholesky of the B matrices in dK (in place) + forward substitution + LML.
 // Beta-CDF warp of n x d inputs for B parameter sets (bgp_warp.hip)
 int bgp_launch_warp(bgp_ctx* c, hipStream_t st, const double* dX, const double* dW, double* dout, int n, int B,

@@ -212,6 +212,7 @@ extern "C" int bgp_fantasy_begin(bgp_ctx* c, int B, const double* h_kernel, cons
                                  double y_mean, double y_std, int n_acq, const int* kinds, const double* params, int n_samples,
                                  int qmax) {
   BGP_REQUIRE_IDLE(c, "bgp_fantasy_begin");
+  BGP_REFUSE_ROWWARP(c, "bgp_fantasy_begin");
   if (!c || !h_kernel || !noise || !Xcand || !kinds || !params || B <= 0 || m <= 0 || qmax <= 0 || n_samples <= 0 ||
       n_acq <= 0 || n_acq > BGP_ACQ_MAX) {
     bgp_set_error("bgp_fantasy_begin: bad argument");

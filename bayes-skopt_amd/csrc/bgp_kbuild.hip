@@ -44,7 +44,8 @@ __global__ void __launch_bounds__(256) kbuild_gram_kernel(const double* __restri
                               npad, xi, xj, ell, acc);
 }
 
-// blockIdx.y = item of a batch: hyper-parameters h + b (d+2), output out + b ostride (the inputs are shared).
+// blockIdx.y = item of a batch: hyper-parameters h + b (d+2), output out + b ostride, inputs Xq + b qstride and Xt + b xstride
+// (stride 0: shared -- every consumer but the per-row-warped predict, whose items carry their own warped queries and training inputs).
 // vec != nullptr: the tile also contributes to the matrix-vector product  out_b vec_b  (the posterior mean K_* alpha
 // of BayesGPR.predict) while its values are still in registers: dpart[(b tiles_j + tj) mpad + row] = the tile's 128-column
 // share of the row's dot product (16 lanes share a row: fixed shuffle order); the caller adds the column tiles in
@@ -55,12 +56,13 @@ __global__ void __launch_bounds__(256) kbuild_cross_kernel(const double* __restr
                                                             const double* __restrict__ h, double* __restrict__ out,
                                                             int ldo, int tiles_j, size_t ostride,
                                                             const double* __restrict__ vec, size_t svec,
-                                                            double* __restrict__ dpart, int mpad) {
+                                                            double* __restrict__ dpart, int mpad, size_t qstride,
+                                                            size_t xstride) {
   const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j, b = blockIdx.y;
   __shared__ double xi[KB_DK][BGP_TILE_LD], xj[KB_DK][BGP_TILE_LD], ell[KB_DK];
   double acc[8][8];
-  kb_tile<256, 0, STAT, FORM>(Xq, m, Xt, n, d, h + (size_t)b * (d + 2), nullptr, ti * 128, tj * 128,
-                              out + (size_t)b * ostride, (size_t)ldo, m, n, xi, xj, ell, acc);
+  kb_tile<256, 0, STAT, FORM>(Xq + (size_t)b * qstride, m, Xt + (size_t)b * xstride, n, d, h + (size_t)b * (d + 2), nullptr,
+                              ti * 128, tj * 128, out + (size_t)b * ostride, (size_t)ldo, m, n, xi, xj, ell, acc);
   if (vec) {
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const double* vb = vec + (size_t)b * svec;
@@ -304,10 +306,19 @@ int bgp_launch_kcross_batch(bgp_ctx* ctx, int nb, const double* dH, int m, const
 // ... and, with vec, the column-tile partials of  out_b vec_b  into dpart (nb x tiles_j x pad128(m))
 int bgp_launch_kcross_matvec(bgp_ctx* ctx, int nb, const double* dH, int m, const double* dXq, int nx, const double* dXt,
                              double* dout, int ldo, size_t ostride, const double* vec, size_t svec, double* dpart) {
+  return bgp_launch_kcross_matvec_x(ctx, nb, dH, m, dXq, 0, nx, dXt, 0, dout, ldo, ostride, vec, svec, dpart);
+}
+
+// ... with per-item inputs: item b reads its queries at dXq + b * qstride and its training inputs at dXt + b * xstride (the
+// per-row-warped predict, bgp_predict_batch_warped); stride 0: shared.  Item b's bits are those of a one-item launch on its inputs.
+int bgp_launch_kcross_matvec_x(bgp_ctx* ctx, int nb, const double* dH, int m, const double* dXq, size_t qstride, int nx,
+                               const double* dXt, size_t xstride, double* dout, int ldo, size_t ostride, const double* vec,
+                               size_t svec, double* dpart) {
   const int tiles_i = (m + 127) / 128, tiles_j = (nx + 127) / 128;
   KB_DISPATCH(ctx->ks.stationary, ctx->ks.form,
               hipLaunchKernelGGL((kbuild_cross_kernel<S, F>), dim3(tiles_i * tiles_j, nb), dim3(256), 0, ctx->stream, dXq,
-                                 m, dXt, nx, ctx->d, dH, dout, ldo, tiles_j, ostride, vec, svec, dpart, tiles_i * 128));
+                                 m, dXt, nx, ctx->d, dH, dout, ldo, tiles_j, ostride, vec, svec, dpart, tiles_i * 128, qstride,
+                                 xstride));
   BGP_HIP(hipGetLastError());
   return BGP_OK;
 }

@@ -420,6 +420,7 @@ static int paths_begin_run(bgp_ctx* c, int P, const int* pidx, const double* h_k
 extern "C" int bgp_paths_begin(bgp_ctx* c, int P, const int* pidx, const double* h_kernel, const double* s2, int F,
                                const double* omega, const double* phase, const double* w, const double* eps) {
   BGP_REQUIRE_IDLE(c, "bgp_paths_begin");
+  BGP_REFUSE_ROWWARP(c, "bgp_paths_begin");
   if (c && (P < 1 || P > PT_PMAX || F < 1 || F > PT_FMAX)) {
     bgp_set_error("bgp_paths_begin: %d paths of %d features (1 .. %d paths, 1 .. %d features)", P, F, PT_PMAX, PT_FMAX);
     return BGP_ERR_INVALID;

@@ -153,6 +153,7 @@ static int pdep_run(bgp_ctx* c, int B, const double* h_kernel, int ns, const dou
 extern "C" int bgp_partial_dependence(bgp_ctx* c, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
                                       const double* grid, int P, const int* panels, double* out) {
   BGP_REQUIRE_IDLE(c, "bgp_partial_dependence");
+  BGP_REFUSE_ROWWARP(c, "bgp_partial_dependence");
   if (!c || !h_kernel || !Xs || !ng || !grid || !panels || !out || B <= 0 || S <= 0 || P <= 0 || gmax <= 0 || gmax > PD_GMAX) {
     bgp_set_error("bgp_partial_dependence: bad argument (B, S, P >= 1, 1 <= gmax <= %d)", PD_GMAX);
     return BGP_ERR_INVALID;

@@ -163,22 +163,32 @@ int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows) {
 // ------------------------------------------------------------------------------------------
 // posterior build
 // ------------------------------------------------------------------------------------------
-static int ensure_resident(bgp_ctx* c, int B, bool want_Linv) {
+static int ensure_resident(bgp_ctx* c, int B, bool want_Linv, bool rowwarp) {
   // K^-1 needs B npad^2 doubles, alpha B npad: the two capacities are tracked separately (a context reused through
   // bgp_ctx_update_data may see n shrink and B grow: B=1 at npad=1024 and B=64 at npad=128 need the same K^-1
   // bytes but 8x the alpha bytes)
   int rc = c->dKinv.ensure((size_t)B * c->npad * c->npad);
   if (!rc && want_Linv) rc = c->dLinv.ensure((size_t)B * c->npad * c->npad);
+  // (per-row-warped posteriors keep their warped training inputs and warp parameters beside K^-1)
+  if (!rc && rowwarp) rc = c->dXwP.ensure((size_t)B * c->n * c->d);
+  if (!rc && rowwarp) rc = c->dwarpP.ensure((size_t)B * 2 * c->d);
   return rc ? rc : c->dalpha_sol.ensure((size_t)B * c->npad);
 }
 
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
-                        double* lml, int* status, const double* Kgram, bool want_Linv) {
+                        double* lml, int* status, const double* Kgram, bool want_Linv, const double* warp) {
   const int npad = c->npad, n = c->n;
-  const size_t p = c->d + 2;
+  const size_t p = c->d + 2, nd = (size_t)n * c->d, w2 = 2 * (size_t)c->d;
   const size_t ld = 2 * (size_t)npad;
-  int rc = ensure_resident(c, B, want_Linv);
+  c->post_rowwarp = 0;  // (any build ends the per-row-warped state; the warped one sets it again when it is through)
+  int rc = ensure_resident(c, B, want_Linv, warp != nullptr);
   if (rc) return rc;
+  if (warp) {
+    // every item's own Beta-CDF warp of the un-warped training inputs, all B in one launch; they stay resident for the predict
+    BGP_HIP(bgp_memcpy_async(c->dwarpP, warp, (size_t)B * w2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    rc = bgp_launch_warp(c, c->stream, c->dX, c->dwarpP, c->dXwP, n, B, nd);
+    if (rc) return rc;
+  }
   // augmented matrices are 4x the LML workspace per item
   int chunk = (int)(c->dK.cap / (ld * ld));
   if (chunk < 1) {
@@ -196,7 +206,10 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
     for (int b = 0; b < nb; b++)
       BGP_HIP(hipMemsetAsync(c->dK + (size_t)b * ld * ld + (size_t)npad * ld, 0, (size_t)npad * ld * sizeof(double),
                              c->stream));
-    rc = Kgram ? bgp_gram_load(c, nb, Kgram + (size_t)off * n * n, 1, use_alpha) : bgp_launch_kbuild(c, nb, 0, 1, use_alpha);
+    // (no kernel of the augmented factorisation reads c->dXeff: bgp_launch_cholesky_slice generates nothing there)
+    rc = Kgram  ? bgp_gram_load(c, nb, Kgram + (size_t)off * n * n, 1, use_alpha)
+         : warp ? bgp_launch_kbuild_x(c, 0, nb, c->stream, 0, 1, use_alpha, c->dXwP + (size_t)off * nd, nd)
+                : bgp_launch_kbuild(c, nb, 0, 1, use_alpha);
     if (rc) return rc;
     hipLaunchKernelGGL(aug_init_kernel, dim3((npad + 255) / 256, nb), dim3(256), 0, c->stream, c->dK, c->dyw, npad, nb);
     rc = bgp_launch_cholesky(c, nb, 1);
@@ -232,16 +245,18 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
   }
   c->post_B = B;
   c->post_gen++;
+  c->post_rowwarp = warp ? 1 : 0;
   return BGP_OK;
 }
 
 // ... as an entry point runs it: whatever was resident is gone before the build starts
 static int post_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv, double* lml,
-                      int* status, const double* Kgram = nullptr) {
+                      int* status, const double* Kgram = nullptr, const double* warp = nullptr) {
   return post_call(c, [&]() -> int {
     BGP_HIP(hipSetDevice(c->device));
     c->post_B = 0;
-    return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram);
+    c->post_rowwarp = 0;
+    return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram, true, warp);
   });
 }
 
@@ -253,6 +268,20 @@ extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L
     return BGP_ERR_INVALID;
   }
   return post_build(c, B, h, 1, L, alpha, K_inv, lml, status);
+}
+
+// The same posterior build with item b's training inputs passed through ITS OWN Beta-CDF warp, warp[b * 2d .. (b + 1) * 2d) (log
+// space, [wa_1..wa_d, wb_1..wb_d], as bgp_lml_batch_warped lays them out): the hyper-posterior draws of warp_inputs=True, every one
+// with its own warped design matrix.  A context-level warp is replaced for this call, not composed with it.  The warped inputs stay
+// resident beside K^-1 / alpha for bgp_predict_batch_warped, the only reader of these posteriors (BGP_REFUSE_ROWWARP).
+extern "C" int bgp_posterior_batch_warped(bgp_ctx* c, int B, const double* h, const double* warp, double* L, double* alpha,
+                                          double* K_inv, double* lml, int* status) {
+  BGP_REQUIRE_IDLE(c, "bgp_posterior_batch_warped");
+  if (!c || !h || !warp || B <= 0) {
+    bgp_set_error("bgp_posterior_batch_warped: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  return post_build(c, B, h, 1, L, alpha, K_inv, lml, status, nullptr, warp);
 }
 
 // The same posterior build from HOST-evaluated kernel matrices (generic kernel expression trees, bgp_gram.hip): K is B
@@ -345,24 +374,29 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
   return BGP_OK;
 }
 
+// rowwarp: the resident posteriors are per-row warped -- item b reads its own training inputs (c->dXwP) and its own warped copy of
+// the queries (one upload of the m rows, ONE warp launch over the B parameter sets in c->dwarpP); no cov there.
 static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
-                       double* cov, const AcqPlan* ap) {
+                       double* cov, const AcqPlan* ap, bool rowwarp = false) {
   if (B > c->post_B) {
-    bgp_set_error("bgp_predict_batch: %d posteriors requested but %d resident (call bgp_posterior_batch first)", B,
-                  c->post_B);
+    bgp_set_error("%s: %d posteriors requested but %d resident (call %s first)",
+                  rowwarp ? "bgp_predict_batch_warped" : "bgp_predict_batch", B, c->post_B,
+                  rowwarp ? "bgp_posterior_batch_warped" : "bgp_posterior_batch");
     return BGP_ERR_STATE;
   }
   BGP_HIP(hipSetDevice(c->device));
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
   const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
+  const size_t qs = rowwarp ? (size_t)m * d : 0, xs = rowwarp ? (size_t)n * d : 0;  // per-item strides of queries / training inputs
   // (1 << 30 doubles of scratch per chunk: 8 GiB of the 288 GB)
   const int chunk = post_chunk(B, sKs + 2 * (size_t)mpad + (cov ? sKs + sCv : 0), (size_t)1 << 30, true);
   const int n_acq = ap ? ap->n_acq : 0;
-  double *dXq, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr;
+  double *dXq, *dXq0 = nullptr, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr;
   AcqScratch as;
   BgpScratch live(c);
   BGP_TRY(live.carve([&](BgpCarve& s) {
-    dXq = s.take<double>((size_t)m * d);
+    dXq = s.take<double>(rowwarp ? (size_t)B * qs : (size_t)m * d);  // (every item's warped queries: all B, as dqB / doutB)
+    if (rowwarp) dXq0 = s.take<double>((size_t)m * d);              // the un-warped rows they are made from
     dH = s.take<double>((size_t)B * p);
     dKs = s.take<double>((size_t)chunk * sKs);
     dmpart = s.take<double>((size_t)chunk * (npad / 128) * mpad);  // column-tile partials of the means
@@ -374,7 +408,13 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     }
     if (n_acq) as.take(s, n_acq, B, mpad);
   }));
-  BGP_TRY(post_stage_queries(c, dXq, Xq, m));
+  if (rowwarp) {
+    BGP_HIP(bgp_memcpy_async(dXq0, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_TRY(bgp_launch_warp(c, c->stream, dXq0, c->dwarpP, dXq, m, B, qs));
+  } else {
+    BGP_TRY(post_stage_queries(c, dXq, Xq, m));
+  }
+  const double* dXt = rowwarp ? (const double*)c->dXwP : (const double*)c->dXeff;
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
   for (int off = 0; off < B; off += chunk) {
     const int nb = std::min(chunk, B - off);
@@ -383,13 +423,14 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     const double* al = c->dalpha_sol + (size_t)off * npad;
     double *dq = dqB + (size_t)off * mpad, *dout = doutB + (size_t)off * mpad;
     // K_* and, from the same registers, the column-tile partials of the mean K_* alpha (added in tile order below)
-    BGP_TRY(bgp_launch_kcross_matvec(c, nb, dHc, m, dXq, n, c->dXeff, dKs, npad, sKs, al, (size_t)npad, dmpart));
+    BGP_TRY(bgp_launch_kcross_matvec_x(c, nb, dHc, m, dXq + (size_t)off * qs, qs, n, dXt + (size_t)off * xs, xs, dKs, npad, sKs, al,
+                                       (size_t)npad, dmpart));
     hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((mpad + 255) / 256, nb), dim3(256), 0, c->stream, dmpart, npad / 128, mpad,
                        dout);
     if (mean) BGP_HIP(rows_down(c, mean + (size_t)off * m, dout, m, mpad, nb));
     // q_i = k_i^T K^-1 k_i  (= rowsum((K_* K^-1) o K_*), evaluated on the lower block triangle of K^-1)
     BGP_TRY(launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq));
-    if (cov) BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, PostKss{dHc, dXq}, 2, dCov, cov + (size_t)off * m * m));
+    if (cov) BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, PostKss{dHc, dXq}, 2, dCov, cov + (size_t)off * m * m));  // (never rowwarp)
     hipLaunchKernelGGL(finish_var_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, (size_t)mpad, dHc, d,
                        c->ks.form, m, dq, (size_t)mpad);  // in place
     BGP_HIP(hipGetLastError());
@@ -404,11 +445,28 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
 extern "C" int bgp_predict_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                                  double* var, double* cov) {
   BGP_REQUIRE_IDLE(c, "bgp_predict_batch");
+  BGP_REFUSE_ROWWARP(c, "bgp_predict_batch");
   if (!c || !h_kernel || !Xq || !mean || !var || m <= 0 || B <= 0) {
     bgp_set_error("bgp_predict_batch: bad argument");
     return BGP_ERR_INVALID;
   }
   return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, mean, var, cov, nullptr); });
+}
+
+// Predict for per-row-warped resident posteriors (bgp_posterior_batch_warped): item b sees the m query rows through ITS warp and
+// its own warped training inputs; everything behind the cross build is bgp_predict_batch's (predict_run).  Mean and variance only.
+extern "C" int bgp_predict_batch_warped(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
+                                        double* var) {
+  BGP_REQUIRE_IDLE(c, "bgp_predict_batch_warped");
+  if (!c || !h_kernel || !Xq || !mean || !var || m <= 0 || B <= 0) {
+    bgp_set_error("bgp_predict_batch_warped: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  if (!c->post_rowwarp) {
+    bgp_set_error("bgp_predict_batch_warped: the resident posteriors are not per-row warped (call bgp_posterior_batch_warped first)");
+    return BGP_ERR_STATE;
+  }
+  return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, mean, var, nullptr, nullptr, true); });
 }
 
 // var_i = max(0, kss_i - q_i) with the prior variances kernel_.diag(Xq) supplied by the host (generic kernels)
@@ -598,6 +656,7 @@ extern "C" int bgp_acq_batch(bgp_ctx* c, int B, const double* h_kernel, int m, c
                              double y_std, int n_acq, const int* kinds, const double* params, int n_samples,
                              double* out) {
   BGP_REQUIRE_IDLE(c, "bgp_acq_batch");
+  BGP_REFUSE_ROWWARP(c, "bgp_acq_batch");
   if (!c || !h_kernel || !Xq || m <= 0 || B <= 0) {
     bgp_set_error("bgp_acq_batch: bad argument");
     return BGP_ERR_INVALID;
@@ -867,6 +926,7 @@ __global__ void pvrs_combine_kernel(const double* __restrict__ G, int ldg, const
 extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double* Xcand, int T,
                         const double* Xthompson, double* covs) {
   BGP_REQUIRE_IDLE(c, "bgp_pvrs");
+  BGP_REFUSE_ROWWARP(c, "bgp_pvrs");
   if (!c || !h_kernel || !Xcand || !Xthompson || !covs || m <= 0 || T <= 0) {
     bgp_set_error("bgp_pvrs: bad argument");
     return BGP_ERR_INVALID;
@@ -1036,6 +1096,7 @@ __global__ void __launch_bounds__(256) tri_matmul_draws_kernel(const double* __r
 extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, const double* Xq, int n_draws,
                             const double* z, double jitter, double* out) {
   BGP_REQUIRE_IDLE(c, "bgp_sample_y");
+  BGP_REFUSE_ROWWARP(c, "bgp_sample_y");
   if (!c || !h_kernel || !Xq || !z || !out || m <= 0 || n_draws <= 0 || b < 0) {
     bgp_set_error("bgp_sample_y: bad argument");
     return BGP_ERR_INVALID;
@@ -1152,6 +1213,7 @@ static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out) {
 extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const double* h_kernel, int m, const double* Xq,
                                   const double* z, double jitter, double* out, int* status) {
   BGP_REQUIRE_IDLE(c, "bgp_sample_y_batch");
+  BGP_REFUSE_ROWWARP(c, "bgp_sample_y_batch");
   if (!c || !pidx || !h_kernel || !Xq || !z || !out || !status || m <= 0 || B <= 0) {
     bgp_set_error("bgp_sample_y_batch: bad argument");
     return BGP_ERR_INVALID;

@@ -252,6 +252,7 @@ static int pg_check(bgp_ctx* c, const char* who) {
 extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                                       double* var, double* dmean, double* dvar) {
   BGP_REQUIRE_IDLE(c, "bgp_predict_grad_batch");
+  BGP_REFUSE_ROWWARP(c, "bgp_predict_grad_batch");
   if (!c || !h_kernel || !Xq || !mean || !var || !dmean || m <= 0 || B <= 0) {
     bgp_set_error("bgp_predict_grad_batch: bad argument");
     return BGP_ERR_INVALID;
@@ -308,6 +309,7 @@ extern "C" int bgp_minimize_starts(bgp_ctx* c, int b, const double* h_kernel, do
                                    const double* X0, const double* lo, const double* hi, double gtol, int max_iter, double* X_out,
                                    double* mean_out, double* var_out, int* iters, int* evals, int* status) {
   BGP_REQUIRE_IDLE(c, "bgp_minimize_starts");
+  BGP_REFUSE_ROWWARP(c, "bgp_minimize_starts");
   if (!c || !h_kernel || !X0 || !lo || !hi || !X_out || !mean_out || !var_out || !iters || !evals || !status || S_ <= 0 ||
       S_ > 65535 || b < 0 || max_iter < 0 || !(gtol >= 0.0)) {
     bgp_set_error("bgp_minimize_starts: bad argument");

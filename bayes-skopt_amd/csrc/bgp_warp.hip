@@ -74,6 +74,7 @@ extern "C" int bgp_ctx_set_warp(bgp_ctx* c, const double* warp) {
   }
   BGP_HIP(hipSetDevice(c->device));
   c->post_B = 0;
+  c->post_rowwarp = 0;
   if (!warp) {
     c->has_warp = 0;
     c->dXeff = c->dX;

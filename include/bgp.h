@@ -102,6 +102,14 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   every later posterior / predict / pvrs / gradient / sample_y / bgp_lml_batch call, including their
  *   query points (bask/bayesgpr.py:630-632); NULL clears it; bgp_ctx_update_data clears it.
  * bgp_beta_cdf: warp m points (m*d row-major) on the device -- BayesGPR.warp() (bask/bayesgpr.py:249-264).
+ *
+ * Per-row-warped posteriors (bgp_posterior_batch_warped, below): posterior b is built from the un-warped training inputs
+ *   through ITS OWN warp and keeps them resident; a context-level warp is replaced for that call, not composed.  While such
+ *   posteriors are resident only bgp_predict_batch_warped reads them: every entry point that would combine resident posteriors
+ *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
+ *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
+ *   bgp_partial_dependence -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
 int bgp_ctx_set_warp(bgp_ctx* ctx, const double* warp);
@@ -158,6 +166,23 @@ int bgp_posterior_batch(bgp_ctx* ctx, int B, const double* h, double* L, double*
  */
 int bgp_predict_batch(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                       double* var, double* cov);
+
+/*
+ * The same pair for hyper-posterior draws under input warping, where every draw carries its own warp and therefore its own
+ * training inputs (evaluate_acquisitions under warp_inputs: create_warpers + rewarp + theta setter + predict per chain row,
+ * bask/acquisition.py:112-125,142-145).
+ *   bgp_posterior_batch_warped  as bgp_posterior_batch, item b built from the training inputs through warp[b*2d .. (b+1)*2d)
+ *          (log space, [wa_1..wa_d, wb_1..wb_d] as for bgp_lml_batch_warped).  The B warped design matrices and the warp
+ *          parameters stay resident beside K^-1 / alpha; a warped LML batch in between does not touch them.  Same chunking,
+ *          outputs and status semantics: a matrix that is not positive definite fails alone.
+ *   bgp_predict_batch_warped    as bgp_predict_batch without cov: item b sees the m query rows through its own warp (one upload,
+ *          one warp launch over the B parameter sets) and its own warped training inputs.  Needs B <= the resident posteriors of
+ *          a bgp_posterior_batch_warped call, BGP_ERR_STATE otherwise.
+ * Item b's results are the bits of bgp_ctx_set_warp(warp_b) + bgp_posterior_batch(h_b) + bgp_predict_batch(h_kernel_b).
+ */
+int bgp_posterior_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* L, double* alpha,
+                               double* K_inv, double* lml, int* status);
+int bgp_predict_batch_warped(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var);
 
 /*
  * Closed-form acquisition functions averaged over the B resident posteriors (hyper-posterior draws), evaluated
