@@ -237,8 +237,13 @@ class Context:
         _live_contexts.add(self)
         self._pending, self._pending_H = 0, None  # batch handed to lml_submit and not yet collected
         self._timing = False
-        # canonical vectors of the posteriors whose K^-1 / alpha are resident on the device
-        # (None after a call that overwrites them: gradient / pvrs_prepare / update_data)
+        self._paths_P = 0           # open pathwise draws (paths_begin .. paths_end / update_data)
+        self._fantasy_shape = None  # (B, m, n_acq) of the last fantasy_begin
+        self._drop_resident()
+
+    def _drop_resident(self):
+        # resident_H: canonical vectors of the posteriors whose K^-1 / alpha are resident on the device; None after a call that
+        # overwrites them (gradient / pvrs_prepare / update_data / set_warp / any build: posterior() alone sets it again)
         self.resident_H = None
 
     def close(self):
@@ -261,7 +266,7 @@ class Context:
         alpha_diag = _c(np.broadcast_to(np.asarray(alpha_diag, dtype=np.float64), (n,)))
         _check(self._lib.bgp_ctx_update_data(self._h, n, _p(X), _p(y), _p(alpha_diag)), "bgp_ctx_update_data")
         self.n = n
-        self.resident_H = None
+        self._drop_resident()
         self._paths_P = 0  # (bgp_ctx_update_data drops the pathwise draws)
 
     def _H(self, H):
@@ -393,7 +398,7 @@ class Context:
 
     def set_warp(self, w):
         """Context-level warp (2d log-space parameters) or None to clear."""
-        self.resident_H = None
+        self._drop_resident()
         if w is None:
             _check(self._lib.bgp_ctx_set_warp(self._h, C.cast(None, _dp)), "bgp_ctx_set_warp")
             return
@@ -413,7 +418,7 @@ class Context:
         out = np.empty(B)
         grad = np.empty((B, self.p))
         st = np.zeros(B, dtype=np.int32)
-        self.resident_H = None
+        self._drop_resident()
         _check(self._lib.bgp_lml_grad_batch(self._h, B, _p(H), _p(out), _p(grad), _p(st)), "bgp_lml_grad_batch")
         return out, grad, st
 
@@ -432,7 +437,7 @@ class Context:
         lml = np.empty(B)
         st = np.zeros(B, dtype=np.int32)
         nul = C.cast(None, _dp)
-        self.resident_H = None  # (set by posterior() alone: posteriors of host matrices belong to no canonical vector)
+        self._drop_resident()  # (set by posterior() alone: posteriors of host matrices belong to no canonical vector)
         _check(getattr(self._lib, name)(self._h, B, *head, _p(L) if want_L else nul, _p(a) if want_alpha else nul,
                                         _p(Ki) if want_K_inv else nul, _p(lml), _p(st)), name)
         return {"L": L, "alpha": a, "K_inv": Ki, "lml": lml, "status": st}
@@ -549,7 +554,7 @@ class Context:
     def pvrs_prepare(self, h_kernel, has_alpha_vec):
         H = self._H(h_kernel)
         st = np.zeros(1, dtype=np.int32)
-        self.resident_H = None
+        self._drop_resident()
         _check(self._lib.bgp_pvrs_prepare(self._h, _p(H), int(bool(has_alpha_vec)), _p(st)), "bgp_pvrs_prepare")
         return int(st[0])
 
@@ -699,7 +704,7 @@ class Context:
         Xq = _c(np.atleast_2d(Xq))
         if Xq.shape[1] != self.d:
             raise ValueError(f"query points must have {self.d} columns, got {Xq.shape[1]}")
-        P, m = getattr(self, "_paths_P", 0), Xq.shape[0]
+        P, m = self._paths_P, Xq.shape[0]
         out = np.empty((P, m))
         dout = np.empty((P, m, self.d)) if want_grad else None
         _check(self._lib.bgp_paths_eval(self._h, m, _p(Xq), _p(out), _p(dout) if want_grad else C.cast(None, _dp)), "bgp_paths_eval")
@@ -711,7 +716,7 @@ class Context:
         units) and grad (P, S, d | None): the search's evaluator at x; iters, evals, status (P, S; 0 converged to ``gtol``, 1
         ``max_iter`` reached, 2 no decrease found).  ``max_iter=0`` evaluates the clipped starts."""
         X0 = _c(X0)
-        P = getattr(self, "_paths_P", 0)
+        P = self._paths_P
         if X0.ndim != 3 or X0.shape[2] != self.d or (P and X0.shape[0] != P):
             raise ValueError(f"X0 must be (P, S, d) = ({P}, S, {self.d}), got {X0.shape}")
         S = X0.shape[1]

@@ -212,6 +212,7 @@ static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, cons
     return std::chrono::duration<double, std::milli>(b - a).count();
   };
   const auto t0 = now();
+  c->post.drop();  // (first: from here on the buffers and c->n / c->npad change, and a failure must not leave posteriors "resident")
   int rc = alloc_data(c, n);
   if (rc) return rc;
   c->n = n;
@@ -236,8 +237,6 @@ static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, cons
   const auto t2 = now();
   BGP_HIP(bgp_stream_sync(c->stream));
   if (dbg) fprintf(stderr, "upload_data: alloc %.3f ms, stage+enqueue %.3f ms, sync %.3f ms\n", ms(t0, t1), ms(t1, t2), ms(t2, now()));
-  c->post_B = 0;
-  c->post_rowwarp = 0;
   c->has_warp = 0;  // new data: the caller re-installs the warp (bgp_ctx_set_warp)
   c->dXeff = c->dX;
   return BGP_OK;
@@ -348,7 +347,7 @@ extern "C" int bgp_ctx_create(int device, int n, int d, const double* X, const d
 }
 
 extern "C" int bgp_ctx_update_data(bgp_ctx* c, int n, const double* X, const double* y, const double* alpha_diag) {
-  BGP_REQUIRE_IDLE(c, "bgp_ctx_update_data");
+  BGP_TRY(bgp_guard(c, "bgp_ctx_update_data"));
   if (!c) {
     bgp_set_error("bgp_ctx_update_data: NULL ctx");
     return BGP_ERR_INVALID;
@@ -469,7 +468,7 @@ extern "C" int bgp_lml_batch(bgp_ctx* c, int B, const double* h, double* lml, in
 
 extern "C" int bgp_lml_batch_warped(bgp_ctx* c, int B, const double* h, const double* warp, double* lml,
                                     int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_lml_batch_warped");
+  BGP_TRY(bgp_guard(c, "bgp_lml_batch_warped"));
   if (!c || !h || !warp || !lml || B < 0) {
     bgp_set_error("bgp_lml_batch_warped: bad argument");
     return BGP_ERR_INVALID;
@@ -722,7 +721,7 @@ int bgp_lml_redo_if_abandoned(bgp_ctx* c, int B) {
 }
 
 extern "C" int bgp_kernel_matrix(bgp_ctx* c, const double* h, double* K) {
-  BGP_REQUIRE_IDLE(c, "bgp_kernel_matrix");
+  BGP_TRY(bgp_guard(c, "bgp_kernel_matrix"));
   if (!c || !h || !K) {
     bgp_set_error("bgp_kernel_matrix: NULL argument");
     return BGP_ERR_INVALID;
@@ -739,7 +738,7 @@ extern "C" int bgp_kernel_matrix(bgp_ctx* c, const double* h, double* K) {
 // Debugging aid: the working matrix (npad x npad, row-major: the factor L in its lower triangle after an LML call) and
 // the working right-hand side (z = L^-1 y) of batch slot b, as the last bgp_lml_batch call left them.
 extern "C" int bgp_debug_workspace(bgp_ctx* c, int b, double* Lout, double* zout) {
-  BGP_REQUIRE_IDLE(c, "bgp_debug_workspace");
+  BGP_TRY(bgp_guard(c, "bgp_debug_workspace"));
   if (!c || b < 0 || b >= c->max_batch) {
     bgp_set_error("bgp_debug_workspace: bad argument");
     return BGP_ERR_INVALID;
@@ -767,7 +766,7 @@ extern "C" int bgp_debug_workspace(bgp_ctx* c, int b, double* Lout, double* zout
 // The factor sample_y's last call left in the child workspace (mpad x mpad doubles, L in the lower triangle; the strict upper
 // triangle is whatever the covariance build left there).
 extern "C" int bgp_debug_cov_factor(bgp_ctx* c, int* mpad, double* Lout) {
-  BGP_REQUIRE_IDLE(c, "bgp_debug_cov_factor");
+  BGP_TRY(bgp_guard(c, "bgp_debug_cov_factor"));
   if (!c || !mpad) {
     bgp_set_error("bgp_debug_cov_factor: bad argument");
     return BGP_ERR_INVALID;
@@ -791,7 +790,7 @@ extern "C" int bgp_set_streams(bgp_ctx* c, int nstreams) {
     bgp_set_error("bgp_set_streams: nstreams must be in 1..%d", BGP_MAX_STREAMS);
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(c, "bgp_set_streams");
+  BGP_TRY(bgp_guard(c, "bgp_set_streams"));
   BGP_HIP(hipSetDevice(c->device));
   for (int g = 0; g < nstreams; g++) {
     if (!c->gstream[g]) {
@@ -820,7 +819,7 @@ extern "C" int bgp_set_persist(bgp_ctx* c, int mode) {
     bgp_set_error("bgp_set_persist: mode must be -1, 0 or 1");
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(c, "bgp_set_persist");
+  BGP_TRY(bgp_guard(c, "bgp_set_persist"));
   if (mode == -1) {
     const char* envps = getenv("BGP_PERSIST");
     c->persist = envps ? (atoi(envps) != 0 ? 1 : 0) : -1;
@@ -839,7 +838,7 @@ extern "C" int bgp_set_panel_fused(bgp_ctx* c, int mode) {
     bgp_set_error("bgp_set_panel_fused: mode must be -1, 0 or 1");
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(c, "bgp_set_panel_fused");
+  BGP_TRY(bgp_guard(c, "bgp_set_panel_fused"));
   if (mode == -1) {
     const char* envpf = getenv("BGP_PANEL_FUSED");
     c->panel_fused = envpf ? (atoi(envpf) != 0 ? 1 : 0) : -1;
@@ -851,7 +850,7 @@ extern "C" int bgp_set_panel_fused(bgp_ctx* c, int mode) {
 
 extern "C" int bgp_set_timing(bgp_ctx* c, int enable) {
   if (!c) return BGP_ERR_INVALID;
-  BGP_REQUIRE_IDLE(c, "bgp_set_timing");
+  BGP_TRY(bgp_guard(c, "bgp_set_timing"));
   c->timing = enable ? 1 : 0;
   return BGP_OK;
 }

@@ -599,7 +599,7 @@ extern "C" int bgp_comm_bench_lml_gather(bgp_ctx* ctx, bgp_comm* c, int per, int
     bgp_set_error("bgp_comm_bench_lml_gather: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(ctx, "bgp_comm_bench_lml_gather");
+  BGP_TRY(bgp_guard(ctx, "bgp_comm_bench_lml_gather"));
   BGP_HIP(hipSetDevice(ctx->device));
   if (!bgp_comm_recv(c, ((size_t)per + 1) * c->world)) {
     bgp_set_error("bgp_comm_bench_lml_gather: no exchange buffers for %d rows per rank", per);

@@ -130,6 +130,22 @@ static inline hipError_t bgp_stream_sync(hipStream_t st) {
   return e;
 }
 
+// What is resident in dKinv / dLinv / dalpha_sol (and dXwP / dwarpP), and nothing else: every invalidation is drop(), the end of a
+// posterior build is commit(), and everybody else reads.
+struct BgpResident {
+  void drop() { B_ = 0, rowwarp_ = false; }  // nothing is resident any more (the generation stays)
+  void commit(int B, bool rowwarp) { B_ = B, rowwarp_ = rowwarp, gen_++; }
+  int B() const { return B_; }               // number of resident posteriors (0 = none)
+  int gen() const { return gen_; }           // bumped by every build (a fantasy state checks that its posteriors are still there)
+  // posterior b was built from dX through ITS OWN warp (bgp_posterior_batch_warped): it goes with its own training inputs in dXwP,
+  // not with dXeff, and bgp_predict_batch_warped alone reads it
+  bool rowwarp() const { return rowwarp_; }
+
+ private:
+  int B_ = 0, gen_ = 0;
+  bool rowwarp_ = false;
+};
+
 struct bgp_ctx {
   int device = 0;
   int n = 0, d = 0, npad = 0, nblk = 0;
@@ -169,16 +185,10 @@ struct bgp_ctx {
   BgpDev<double> dKinv;
   BgpDev<double> dLinv;
   BgpDev<double> dalpha_sol;
-  // resident posterior state
-  int post_B = 0;            // number of resident posteriors (0 = none)
-  int post_gen = 0;          // bumped by every posterior build (a fantasy state checks that its posteriors are still there)
-  // per-row-warped resident posteriors (bgp_posterior_batch_warped): posterior b was built from dX through ITS OWN warp, so it
-  // goes with its own training inputs, not with dXeff.  Buffers of their own: a warped LML batch between build and predict
-  // overwrites dXwB / dwarpB.
-  int post_rowwarp = 0;      // the resident posteriors are per-row warped (bgp_refuse_rowwarp; ended by any build / new data / set_warp)
-  BgpDev<double> dXwP;       // post_B * n * d   warped training inputs of every resident posterior
-  BgpDev<double> dwarpP;     // post_B * 2d      their warp parameters (log space)
-  std::vector<double> post_h;
+  BgpResident post;          // how many of them, of which build, per-row warped or not
+  // per-row-warped resident posteriors: buffers of their own (a warped LML batch between build and predict overwrites dXwB / dwarpB)
+  BgpDev<double> dXwP;       // post.B() * n * d   warped training inputs of every resident posterior
+  BgpDev<double> dwarpP;     // post.B() * 2d      their warp parameters (log space)
   // scratch for predict / pvrs (grown on demand, carved through BgpScratch below)
   BgpDev<char> dscratch;
   int scratch_live = 0;        // pointers carved out of dscratch are in use: a second carve would free them (BgpScratch)
@@ -226,15 +236,6 @@ struct bgp_ctx {
   std::vector<hipEvent_t> ev;  // (start, stop) pairs of the launches of the current call
   std::vector<int> evcat;
 };
-
-// The workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it.
-#define BGP_REQUIRE_IDLE(c, who)                                                                     \
-  do {                                                                                              \
-    if ((c) && (c)->pending_B != 0) {                                                               \
-      bgp_set_error(who ": a submitted batch is still pending (call bgp_lml_batch_wait)");          \
-      return BGP_ERR_STATE;                                                                         \
-    }                                                                                               \
-  } while (0)
 
 // Per-launch HIP-event timing on the context's stream (only when ctx->timing != 0).
 // Categories: 0 K-build, 1 potrf, 2 trsm, 3 syrk (bulk update of a panel group), 5 syrk look-ahead column launch (counted
@@ -420,12 +421,60 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_persist_fits(bgp_ctx* ctx, int B);
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
-// ONE exit path for the entry points of bgp_post.hip and bgp_paths.hip (their stages return from the middle, with BGP_HIP or a plain
-// return): a failed call waits for what it enqueued -- its kernels run over scratch that the next call may carve again --, clears the
-// sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success path is the body's own.
+// ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
+// bgp_paths.hip, bgp_pdep.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
+// checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
+// workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
+// other entry point's guard too (bgp_api.hip, bgp_gram.hip, bgp_mcmc.hip, bgp_comm.hip).
+//   BGP_POST_PLAIN    the resident posteriors are not per-row warped: they go with the shared c->dXeff
+//   BGP_POST_ROWWARP  they are (bgp_predict_batch_warped)
+//   count > 0: at least `count` are resident (index b: b + 1);  idx: every idx[0 .. nidx) names a resident one.
+// Nothing is launched and nothing changes on a refusal.
+enum BgpPostKind { BGP_POST_ANY, BGP_POST_PLAIN, BGP_POST_ROWWARP };
+static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind = BGP_POST_ANY, int count = 0,
+                            const int* idx = nullptr, int nidx = 0) {
+  if (!c) {
+    bgp_set_error("%s: NULL ctx", who);
+    return BGP_ERR_INVALID;
+  }
+  const char* why = nullptr;
+  if (c->pending_B != 0)
+    why = "a submitted batch is still pending (call bgp_lml_batch_wait)";
+  else if (kind == BGP_POST_PLAIN && c->post.rowwarp())
+    why = "the resident posteriors are per-row warped (bgp_posterior_batch_warped): only bgp_predict_batch_warped reads them; "
+          "build plain posteriors first";
+  else if (kind == BGP_POST_ROWWARP && !c->post.rowwarp())
+    why = "the resident posteriors are not per-row warped (call bgp_posterior_batch_warped first)";
+  else if ((count > 0 || nidx > 0) && c->post.B() == 0)
+    why = "no resident posteriors (build them first: bgp_posterior_batch and its kin)";
+  if (why) {
+    bgp_set_error("%s: %s", who, why);
+    return BGP_ERR_STATE;
+  }
+  if (count > c->post.B()) {
+    bgp_set_error("%s: needs %d posteriors, %d resident", who, count, c->post.B());
+    return BGP_ERR_STATE;
+  }
+  for (int i = 0; i < nidx; i++)
+    if (idx[i] < 0 || idx[i] >= c->post.B()) {
+      bgp_set_error("%s: item %d names posterior %d, %d resident", who, i, idx[i], c->post.B());
+      return BGP_ERR_STATE;
+    }
+  return BGP_OK;
+}
+
+// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_pdep.hip,
+// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
+// runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
+// carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
+// path is the body's own.
 template <class Body>
 static inline int post_call(bgp_ctx* c, Body&& body) {
-  const int rc = body();
+  const int rc = [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    return body();
+  }();
   if (rc != BGP_OK) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
@@ -434,17 +483,6 @@ static inline int post_call(bgp_ctx* c, Body&& body) {
   }
   return rc;
 }
-
-// Per-row-warped resident posteriors (bgp_posterior_batch_warped) go with their own warped training inputs: an entry point that
-// would combine them with the shared c->dXeff refuses, and launches nothing.
-#define BGP_REFUSE_ROWWARP(c, who)                                                                                     \
-  do {                                                                                                                 \
-    if ((c) && (c)->post_rowwarp) {                                                                                    \
-      bgp_set_error(who ": the resident posteriors are per-row warped (bgp_posterior_batch_warped): only "              \
-                        "bgp_predict_batch_warped reads them; build plain posteriors first");                          \
-      return BGP_ERR_STATE;                                                                                            \
-    }                                                                                                                  \
-  } while (0)
 
 // The context's scratch, carved by ONE layout per call (bgp_mem.h; every region on 16 bytes).  A carve may free and re-allocate
 // dscratch, so the pointers of an earlier one would dangle: while a BgpScratch that has carved is in scope, another carve of the

@@ -12,6 +12,8 @@
 // The acquisition closed forms and the fixed-order average over the draws are bgp_acq_batch's kernels (bgp_post.hip),
 // the argmax over the candidates not yet chosen is one workgroup: only the index (and optionally the m averaged values)
 // comes back.  Every reduction has a fixed order; the only atomics are bgp_acq_batch's integer "row not finite" flags.
+#include <memory>
+
 #include "bgp_common.h"
 #include "bgp_device.h"
 
@@ -211,8 +213,7 @@ __global__ void __launch_bounds__(1024) fant_argmax_kernel(const double* __restr
 extern "C" int bgp_fantasy_begin(bgp_ctx* c, int B, const double* h_kernel, const double* noise, int m, const double* Xcand,
                                  double y_mean, double y_std, int n_acq, const int* kinds, const double* params, int n_samples,
                                  int qmax) {
-  BGP_REQUIRE_IDLE(c, "bgp_fantasy_begin");
-  BGP_REFUSE_ROWWARP(c, "bgp_fantasy_begin");
+  BGP_TRY(bgp_guard(c, "bgp_fantasy_begin", BGP_POST_PLAIN));
   if (!c || !h_kernel || !noise || !Xcand || !kinds || !params || B <= 0 || m <= 0 || qmax <= 0 || n_samples <= 0 ||
       n_acq <= 0 || n_acq > BGP_ACQ_MAX) {
     bgp_set_error("bgp_fantasy_begin: bad argument");
@@ -231,64 +232,59 @@ extern "C" int bgp_fantasy_begin(bgp_ctx* c, int B, const double* h_kernel, cons
     bgp_set_error("bgp_fantasy_begin: %s", c->has_warp ? "warped inputs are not supported" : "d > 32 is not supported");
     return BGP_ERR_INVALID;
   }
-  if (B > c->post_B) {
-    bgp_set_error("bgp_fantasy_begin: %d posteriors requested but %d resident (call bgp_posterior_batch first)", B, c->post_B);
-    return BGP_ERR_STATE;
-  }
-  BGP_HIP(hipSetDevice(c->device));
-  fantasy_free(c);
-  // the starting means / variances: bgp_predict_batch itself (the same bits as the proposal's bgp_acq_batch saw)
-  std::vector<double> mean((size_t)B * m), var((size_t)B * m);
-  int rc = bgp_predict_batch(c, B, h_kernel, m, Xcand, mean.data(), var.data(), nullptr);
-  if (rc) return rc;
-  bgp_fantasy_state* f = new bgp_fantasy_state();
-  c->fantasy = f;
-  const int d = c->d, npad = c->npad, mpad = ((m + 255) / 256) * 256;
-  f->B = B, f->m = m, f->mpad = mpad, f->qmax = qmax, f->j = 0, f->n_acq = n_acq, f->n_samples = n_samples;
-  f->y_mean = y_mean, f->y_std = y_std, f->post_gen = c->post_gen;
-  for (int k = 0; k < n_acq; k++) f->kinds[k] = kinds[k], f->params[k] = params[k];
-  const size_t Bm = (size_t)B * mpad;
-  rc = bgp_carve(f->mem, 16, [&](BgpCarve& s) {
-    f->dXc = s.take<double>((size_t)m * d);
-    f->dH = s.take<double>((size_t)B * (d + 2));
-    f->dnoise = s.take<double>(B);
-    f->dmu = s.take<double>(Bm);
-    f->dvar = s.take<double>(Bm);
-    f->dU = s.take<double>((size_t)qmax * Bm);
-    f->dkp = s.take<double>((size_t)B * npad);
-    f->dw = s.take<double>((size_t)B * npad);
-    f->dc = s.take<double>(Bm);
-    f->dpv = s.take<double>(2 * (size_t)B);
-    f->dT = s.take<double>((size_t)n_acq * Bm);
-    f->dacc = s.take<double>((size_t)n_acq * mpad);
-    f->dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);
-    f->dparams = s.take<double>(BGP_ACQ_MAX);
-    f->dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);
-    f->dkinds = s.take<int>(BGP_ACQ_MAX);
-    f->dchosen = s.take<int>(mpad);
-    f->dnext = s.take<int>(1);
+  BGP_TRY(bgp_guard(c, "bgp_fantasy_begin", BGP_POST_PLAIN, B));
+  fantasy_free(c);  // (whatever happens below, the previous batch is over)
+  return post_call(c, [&]() -> int {
+    // the starting means / variances: bgp_predict_batch itself (the same bits as the proposal's bgp_acq_batch saw); a complete call
+    // of its own, outside this body's carve
+    std::vector<double> mean((size_t)B * m), var((size_t)B * m);
+    BGP_TRY(bgp_predict_batch(c, B, h_kernel, m, Xcand, mean.data(), var.data(), nullptr));
+    std::unique_ptr<bgp_fantasy_state> st(new bgp_fantasy_state());
+    bgp_fantasy_state* f = st.get();
+    const int d = c->d, npad = c->npad, mpad = ((m + 255) / 256) * 256;
+    f->B = B, f->m = m, f->mpad = mpad, f->qmax = qmax, f->j = 0, f->n_acq = n_acq, f->n_samples = n_samples;
+    f->y_mean = y_mean, f->y_std = y_std, f->post_gen = c->post.gen();
+    for (int k = 0; k < n_acq; k++) f->kinds[k] = kinds[k], f->params[k] = params[k];
+    const size_t Bm = (size_t)B * mpad;
+    BGP_TRY(bgp_carve(f->mem, 16, [&](BgpCarve& s) {
+      f->dXc = s.take<double>((size_t)m * d);
+      f->dH = s.take<double>((size_t)B * (d + 2));
+      f->dnoise = s.take<double>(B);
+      f->dmu = s.take<double>(Bm);
+      f->dvar = s.take<double>(Bm);
+      f->dU = s.take<double>((size_t)qmax * Bm);
+      f->dkp = s.take<double>((size_t)B * npad);
+      f->dw = s.take<double>((size_t)B * npad);
+      f->dc = s.take<double>(Bm);
+      f->dpv = s.take<double>(2 * (size_t)B);
+      f->dT = s.take<double>((size_t)n_acq * Bm);
+      f->dacc = s.take<double>((size_t)n_acq * mpad);
+      f->dmumin = s.take<double>((size_t)B + BGP_ACQ_MAX);
+      f->dparams = s.take<double>(BGP_ACQ_MAX);
+      f->dbad = s.take<int>((size_t)n_acq * B + BGP_ACQ_MAX);
+      f->dkinds = s.take<int>(BGP_ACQ_MAX);
+      f->dchosen = s.take<int>(mpad);
+      f->dnext = s.take<int>(1);
+    }));
+    BGP_HIP(hipMemsetAsync(f->mem, 0, f->mem.cap, c->stream));  // (a fresh block: exactly the layout's bytes)
+    BGP_HIP(bgp_memcpy_async(f->dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(f->dH, h_kernel, (size_t)B * (d + 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(f->dnoise, noise, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(f->dparams, params, (size_t)n_acq * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(f->dkinds, kinds, (size_t)n_acq * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy2d_async(f->dmu, (size_t)mpad * sizeof(double), mean.data(), (size_t)m * sizeof(double),
+                               (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy2d_async(f->dvar, (size_t)mpad * sizeof(double), var.data(), (size_t)m * sizeof(double),
+                               (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));  // (the host vectors above are staged; the state is complete)
+    c->fantasy = st.release();
+    c->fant_stats[0]++;
+    return BGP_OK;
   });
-  if (rc) {
-    fantasy_free(c);
-    return rc;
-  }
-  BGP_HIP(hipMemsetAsync(f->mem, 0, f->mem.cap, c->stream));  // (a fresh block: exactly the layout's bytes)
-  BGP_HIP(bgp_memcpy_async(f->dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(f->dH, h_kernel, (size_t)B * (d + 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(f->dnoise, noise, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(f->dparams, params, (size_t)n_acq * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(f->dkinds, kinds, (size_t)n_acq * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy2d_async(f->dmu, (size_t)mpad * sizeof(double), mean.data(), (size_t)m * sizeof(double),
-                             (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy2d_async(f->dvar, (size_t)mpad * sizeof(double), var.data(), (size_t)m * sizeof(double),
-                             (size_t)m * sizeof(double), B, hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_stream_sync(c->stream));
-  c->fant_stats[0]++;
-  return BGP_OK;
 }
 
 extern "C" int bgp_fantasy_step(bgp_ctx* c, int p, int lie_kind, double lie_value, int* next, double* values) {
-  BGP_REQUIRE_IDLE(c, "bgp_fantasy_step");
+  BGP_TRY(bgp_guard(c, "bgp_fantasy_step"));
   if (!c || !next) {
     bgp_set_error("bgp_fantasy_step: bad argument");
     return BGP_ERR_INVALID;
@@ -298,7 +294,7 @@ extern "C" int bgp_fantasy_step(bgp_ctx* c, int p, int lie_kind, double lie_valu
     bgp_set_error("bgp_fantasy_step: no fantasy state (call bgp_fantasy_begin first)");
     return BGP_ERR_STATE;
   }
-  if (f->post_gen != c->post_gen || f->B > c->post_B) {
+  if (f->post_gen != c->post.gen() || f->B > c->post.B()) {
     bgp_set_error("bgp_fantasy_step: the resident posteriors changed since bgp_fantasy_begin");
     return BGP_ERR_STATE;
   }
@@ -307,41 +303,42 @@ extern "C" int bgp_fantasy_step(bgp_ctx* c, int p, int lie_kind, double lie_valu
                   lie_kind);
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  const int B = f->B, m = f->m, mpad = f->mpad, n = c->n, npad = c->npad, d = c->d;
-  hipStream_t st = c->stream;
-  KB_DISPATCH(c->ks.stationary, c->ks.form,
-              hipLaunchKernelGGL((fant_kp_kernel<S, F>), dim3((npad + 255) / 256, B), dim3(256), 0, st, c->dXeff, n, npad, d,
-                                 f->dXc, p, f->dH, f->dkp));
-  hipLaunchKernelGGL(fant_w_kernel, dim3((npad + 3) / 4, B), dim3(256), 0, st, c->dKinv, n, npad, f->dkp, f->dw);
-  KB_DISPATCH(c->ks.stationary, c->ks.form,
-              hipLaunchKernelGGL((fant_col_kernel<S, F>), dim3(mpad / 256, B), dim3(256), 0, st, c->dXeff, n, npad, d, f->dXc,
-                                 m, mpad, p, f->dH, f->dw, f->dU, f->j, B, f->dc));
-  hipLaunchKernelGGL(fant_pivot_kernel, dim3((B + 255) / 256), dim3(256), 0, st, f->dc, f->dmu, mpad, p, B, f->dpv,
-                     f->dchosen);
-  hipLaunchKernelGGL(fant_update_kernel, dim3(mpad / 256, B), dim3(256), 0, st, f->dc, f->dpv, f->dnoise, m, mpad, B, f->j,
-                     lie_kind == BGP_LIE_KB ? 1 : 0, lie_value, f->dU, f->dmu, f->dvar);
-  // closed forms + average over the draws (bgp_acq_batch's kernels), then the argmax of the first acquisition
-  BGP_HIP(hipMemsetAsync(f->dbad, 0, (size_t)f->n_acq * B * sizeof(int), st));
-  hipLaunchKernelGGL(acq_mumin_kernel, dim3(B), dim3(256), 0, st, f->dmu, (size_t)mpad, m, f->y_mean, f->y_std, f->dmumin);
-  hipLaunchKernelGGL(acq_values_kernel, dim3((m + 255) / 256, B), dim3(256), 0, st, f->dmu, f->dvar, (size_t)mpad, m, B,
-                     f->y_mean, f->y_std, f->n_acq, f->dkinds, f->dparams, f->dmumin, f->dT, f->dbad);
-  hipLaunchKernelGGL(acq_sum_kernel, dim3((m + 255) / 256, f->n_acq), dim3(256), 0, st, f->dT, f->dbad, (size_t)mpad, m, B,
-                     f->n_samples, f->dacc);
-  hipLaunchKernelGGL(fant_argmax_kernel, dim3(1), dim3(1024), 0, st, f->dacc, f->dchosen, m, f->dnext);
-  BGP_HIP(hipGetLastError());
-  BGP_HIP(bgp_memcpy_async(next, f->dnext, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (values)
-    BGP_HIP(bgp_memcpy2d_async(values, (size_t)m * sizeof(double), f->dacc, (size_t)mpad * sizeof(double),
-                               (size_t)m * sizeof(double), f->n_acq, hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_stream_sync(st));
-  f->j++;
-  c->fant_stats[1]++;
-  return BGP_OK;
+  return post_call(c, [&]() -> int {
+    const int B = f->B, m = f->m, mpad = f->mpad, n = c->n, npad = c->npad, d = c->d;
+    hipStream_t st = c->stream;
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((fant_kp_kernel<S, F>), dim3((npad + 255) / 256, B), dim3(256), 0, st, c->dXeff, n, npad, d,
+                                   f->dXc, p, f->dH, f->dkp));
+    hipLaunchKernelGGL(fant_w_kernel, dim3((npad + 3) / 4, B), dim3(256), 0, st, c->dKinv, n, npad, f->dkp, f->dw);
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((fant_col_kernel<S, F>), dim3(mpad / 256, B), dim3(256), 0, st, c->dXeff, n, npad, d, f->dXc,
+                                   m, mpad, p, f->dH, f->dw, f->dU, f->j, B, f->dc));
+    hipLaunchKernelGGL(fant_pivot_kernel, dim3((B + 255) / 256), dim3(256), 0, st, f->dc, f->dmu, mpad, p, B, f->dpv,
+                       f->dchosen);
+    hipLaunchKernelGGL(fant_update_kernel, dim3(mpad / 256, B), dim3(256), 0, st, f->dc, f->dpv, f->dnoise, m, mpad, B, f->j,
+                       lie_kind == BGP_LIE_KB ? 1 : 0, lie_value, f->dU, f->dmu, f->dvar);
+    // closed forms + average over the draws (bgp_acq_batch's kernels), then the argmax of the first acquisition
+    BGP_HIP(hipMemsetAsync(f->dbad, 0, (size_t)f->n_acq * B * sizeof(int), st));
+    hipLaunchKernelGGL(acq_mumin_kernel, dim3(B), dim3(256), 0, st, f->dmu, (size_t)mpad, m, f->y_mean, f->y_std, f->dmumin);
+    hipLaunchKernelGGL(acq_values_kernel, dim3((m + 255) / 256, B), dim3(256), 0, st, f->dmu, f->dvar, (size_t)mpad, m, B,
+                       f->y_mean, f->y_std, f->n_acq, f->dkinds, f->dparams, f->dmumin, f->dT, f->dbad);
+    hipLaunchKernelGGL(acq_sum_kernel, dim3((m + 255) / 256, f->n_acq), dim3(256), 0, st, f->dT, f->dbad, (size_t)mpad, m, B,
+                       f->n_samples, f->dacc);
+    hipLaunchKernelGGL(fant_argmax_kernel, dim3(1), dim3(1024), 0, st, f->dacc, f->dchosen, m, f->dnext);
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(bgp_memcpy_async(next, f->dnext, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (values)
+      BGP_HIP(bgp_memcpy2d_async(values, (size_t)m * sizeof(double), f->dacc, (size_t)mpad * sizeof(double),
+                                 (size_t)m * sizeof(double), f->n_acq, hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_stream_sync(st));
+    f->j++;
+    c->fant_stats[1]++;
+    return BGP_OK;
+  });
 }
 
 extern "C" int bgp_fantasy_moments(bgp_ctx* c, double* mean, double* var) {
-  BGP_REQUIRE_IDLE(c, "bgp_fantasy_moments");
+  BGP_TRY(bgp_guard(c, "bgp_fantasy_moments"));
   if (!c || !mean || !var) {
     bgp_set_error("bgp_fantasy_moments: bad argument");
     return BGP_ERR_INVALID;
@@ -351,12 +348,13 @@ extern "C" int bgp_fantasy_moments(bgp_ctx* c, double* mean, double* var) {
     bgp_set_error("bgp_fantasy_moments: no fantasy state (call bgp_fantasy_begin first)");
     return BGP_ERR_STATE;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  const size_t row = (size_t)f->m * sizeof(double), pitch = (size_t)f->mpad * sizeof(double);
-  BGP_HIP(bgp_memcpy2d_async(mean, row, f->dmu, pitch, row, f->B, hipMemcpyDeviceToHost, c->stream));
-  BGP_HIP(bgp_memcpy2d_async(var, row, f->dvar, pitch, row, f->B, hipMemcpyDeviceToHost, c->stream));
-  BGP_HIP(bgp_stream_sync(c->stream));
-  return BGP_OK;
+  return post_call(c, [&]() -> int {
+    const size_t row = (size_t)f->m * sizeof(double), pitch = (size_t)f->mpad * sizeof(double);
+    BGP_HIP(bgp_memcpy2d_async(mean, row, f->dmu, pitch, row, f->B, hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_memcpy2d_async(var, row, f->dvar, pitch, row, f->B, hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
+  });
 }
 
 extern "C" int bgp_fantasy_end(bgp_ctx* c) {

@@ -42,7 +42,7 @@ int bgp_gram_load(bgp_ctx* c, int nb, const double* K, int augmented, int use_al
 }
 
 extern "C" int bgp_lml_batch_gram(bgp_ctx* c, int B, const double* K, int use_alpha, double* lml, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_lml_batch_gram");
+  BGP_TRY(bgp_guard(c, "bgp_lml_batch_gram"));
   if (!c || !K || !lml || B <= 0) {
     bgp_set_error("bgp_lml_batch_gram: bad argument");
     return BGP_ERR_INVALID;

@@ -245,7 +245,7 @@ extern "C" int bgp_mcmc_begin_ex(bgp_ctx* c, bgp_comm* comm, int nwarp, int W, i
     bgp_set_error("bgp_mcmc_begin: bad argument (W must be even and >= 2)");
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(c, "bgp_mcmc_begin");
+  BGP_TRY(bgp_guard(c, "bgp_mcmc_begin"));
   const int Ns = W / 2, hp = c->d + 2, nhalf = 2 * nsteps;
   if (nwarp != 0 && (nwarp != 2 * c->d || p <= nwarp)) {
     bgp_set_error("bgp_mcmc_begin: nwarp = %d must be 0 or 2 d = %d, behind at least one kernel entry (p = %d)", nwarp, 2 * c->d, p);

@@ -354,7 +354,6 @@ static int paths_launch_feat(bgp_ctx* c, const bgp_paths_state* s, const double*
 
 static int paths_begin_run(bgp_ctx* c, int P, const int* pidx, const double* h_kernel, const double* ls2, int F,
                            const double* omega, const double* phase, const double* w, const double* eps) {
-  BGP_HIP(hipSetDevice(c->device));
   paths_free(c);
   const int n = c->n, d = c->d, npad = c->npad;
   const size_t p2 = d + 2, PF = (size_t)P * F, Pn = (size_t)P * n;
@@ -419,8 +418,7 @@ static int paths_begin_run(bgp_ctx* c, int P, const int* pidx, const double* h_k
 
 extern "C" int bgp_paths_begin(bgp_ctx* c, int P, const int* pidx, const double* h_kernel, const double* s2, int F,
                                const double* omega, const double* phase, const double* w, const double* eps) {
-  BGP_REQUIRE_IDLE(c, "bgp_paths_begin");
-  BGP_REFUSE_ROWWARP(c, "bgp_paths_begin");
+  BGP_TRY(bgp_guard(c, "bgp_paths_begin", BGP_POST_PLAIN));
   if (c && (P < 1 || P > PT_PMAX || F < 1 || F > PT_FMAX)) {
     bgp_set_error("bgp_paths_begin: %d paths of %d features (1 .. %d paths, 1 .. %d features)", P, F, PT_PMAX, PT_FMAX);
     return BGP_ERR_INVALID;
@@ -433,20 +431,11 @@ extern "C" int bgp_paths_begin(bgp_ctx* c, int P, const int* pidx, const double*
     bgp_set_error("bgp_paths_begin: %s", c->has_warp ? "warped inputs are not supported" : "d > 32 is not supported");
     return BGP_ERR_INVALID;
   }
-  if (c->post_B <= 0) {
-    bgp_set_error("bgp_paths_begin: no resident posteriors (call bgp_posterior_batch first)");
-    return BGP_ERR_STATE;
-  }
-  for (int p = 0; p < P; p++)
-    if (pidx[p] < 0 || pidx[p] >= c->post_B) {
-      bgp_set_error("bgp_paths_begin: path %d names posterior %d, %d resident", p, pidx[p], c->post_B);
-      return BGP_ERR_STATE;
-    }
+  BGP_TRY(bgp_guard(c, "bgp_paths_begin", BGP_POST_PLAIN, 0, pidx, P));
   return post_call(c, [&] { return paths_begin_run(c, P, pidx, h_kernel, s2, F, omega, phase, w, eps); });
 }
 
 static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, double* dout) {
-  BGP_HIP(hipSetDevice(c->device));
   const bgp_paths_state* s = c->paths;
   const int P = s->P, d = s->d, n = s->n;
   // chunks of query rows: staged outputs of P mc (1 + d) doubles under the budget of the prediction gradients (2^24 doubles)
@@ -488,11 +477,7 @@ static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, doub
 }
 
 extern "C" int bgp_paths_eval(bgp_ctx* c, int m, const double* Xq, double* out, double* dout) {
-  BGP_REQUIRE_IDLE(c, "bgp_paths_eval");
-  if (!c) {
-    bgp_set_error("bgp_paths_eval: NULL ctx");
-    return BGP_ERR_INVALID;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_paths_eval"));
   if (!c->paths) {
     bgp_set_error("bgp_paths_eval: no paths state (call bgp_paths_begin first)");
     return BGP_ERR_STATE;
@@ -506,7 +491,6 @@ extern "C" int bgp_paths_eval(bgp_ctx* c, int m, const double* Xq, double* out, 
 
 static int paths_min_run(bgp_ctx* c, int S, const double* X0, const double* lo, const double* hi, double gtol, int max_iter,
                          double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status) {
-  BGP_HIP(hipSetDevice(c->device));
   const bgp_paths_state* s = c->paths;
   const int P = s->P, d = s->d, n = s->n;
   // chunks of starts: staged starts, end points, values, gradients and counters of P sc items under the budget of bgp_paths_eval
@@ -552,11 +536,7 @@ static int paths_min_run(bgp_ctx* c, int S, const double* X0, const double* lo, 
 
 extern "C" int bgp_paths_minimize(bgp_ctx* c, int S, const double* X0, const double* lo, const double* hi, double gtol,
                                   int max_iter, double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_paths_minimize");
-  if (!c) {
-    bgp_set_error("bgp_paths_minimize: NULL ctx");
-    return BGP_ERR_INVALID;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_paths_minimize"));
   if (!c->paths) {
     bgp_set_error("bgp_paths_minimize: no paths state (call bgp_paths_begin first)");
     return BGP_ERR_STATE;

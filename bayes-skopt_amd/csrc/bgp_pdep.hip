@@ -114,7 +114,6 @@ __global__ void __launch_bounds__(256) pdep_reduce_kernel(const double* __restri
 
 static int pdep_run(bgp_ctx* c, int B, const double* h_kernel, int ns, const double* Xs, int gmax, const double* grid,
                     const std::vector<int>& tiles, int total, double* out) {
-  BGP_HIP(hipSetDevice(c->device));
   const int n = c->n, d = c->d, npad = c->npad, nchunk = (ns + PD_SC - 1) / PD_SC, ntiles = (int)(tiles.size() / 8);
   const size_t p = d + 2;
   double *dXs, *dG, *dH, *dUs, *dus, *dgs, *dpart, *dout;
@@ -152,8 +151,7 @@ static int pdep_run(bgp_ctx* c, int B, const double* h_kernel, int ns, const dou
 
 extern "C" int bgp_partial_dependence(bgp_ctx* c, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
                                       const double* grid, int P, const int* panels, double* out) {
-  BGP_REQUIRE_IDLE(c, "bgp_partial_dependence");
-  BGP_REFUSE_ROWWARP(c, "bgp_partial_dependence");
+  BGP_TRY(bgp_guard(c, "bgp_partial_dependence", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xs || !ng || !grid || !panels || !out || B <= 0 || S <= 0 || P <= 0 || gmax <= 0 || gmax > PD_GMAX) {
     bgp_set_error("bgp_partial_dependence: bad argument (B, S, P >= 1, 1 <= gmax <= %d)", PD_GMAX);
     return BGP_ERR_INVALID;
@@ -190,9 +188,6 @@ extern "C" int bgp_partial_dependence(bgp_ctx* c, int B, const double* h_kernel,
     bgp_set_error("bgp_partial_dependence: at most %d samples and 65535 posteriors per call", 65535 * PD_SC);
     return BGP_ERR_INVALID;
   }
-  if (B > c->post_B) {
-    bgp_set_error("bgp_partial_dependence: %d posteriors requested but %d resident (call bgp_posterior_batch first)", B, c->post_B);
-    return BGP_ERR_STATE;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_partial_dependence", BGP_POST_PLAIN, B));
   return post_call(c, [&] { return pdep_run(c, B, h_kernel, S, Xs, gmax, grid, tiles, (int)total, out); });
 }

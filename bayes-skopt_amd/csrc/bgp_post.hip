@@ -133,7 +133,7 @@ static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const
 
 static inline int pad128(int v) { return ((v + 127) / 128) * 128; }
 
-// (post_call, the ONE exit path of the entry points of this file: bgp_common.h)
+// (bgp_guard and post_call, the ONE guard and the ONE exit path of the entry points of this file: bgp_common.h)
 
 // `rows` rows of `w` doubles between a packed host array and device rows of stride `ld`
 static hipError_t rows_up(bgp_ctx* c, double* dev, const double* host, int w, int ld, int rows) {
@@ -180,7 +180,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
   const int npad = c->npad, n = c->n;
   const size_t p = c->d + 2, nd = (size_t)n * c->d, w2 = 2 * (size_t)c->d;
   const size_t ld = 2 * (size_t)npad;
-  c->post_rowwarp = 0;  // (any build ends the per-row-warped state; the warped one sets it again when it is through)
+  c->post.drop();  // (whatever was resident is gone before the buffers are touched; commit() below when the build is through)
   int rc = ensure_resident(c, B, want_Linv, warp != nullptr);
   if (rc) return rc;
   if (warp) {
@@ -243,26 +243,19 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
     }
     BGP_HIP(bgp_stream_sync(c->stream));
   }
-  c->post_B = B;
-  c->post_gen++;
-  c->post_rowwarp = warp ? 1 : 0;
+  c->post.commit(B, warp != nullptr);
   return BGP_OK;
 }
 
-// ... as an entry point runs it: whatever was resident is gone before the build starts
+// ... as an entry point runs it
 static int post_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv, double* lml,
                       int* status, const double* Kgram = nullptr, const double* warp = nullptr) {
-  return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
-    c->post_B = 0;
-    c->post_rowwarp = 0;
-    return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram, true, warp);
-  });
+  return post_call(c, [&] { return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram, true, warp); });
 }
 
 extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L, double* alpha, double* K_inv,
                                    double* lml, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_posterior_batch");
+  BGP_TRY(bgp_guard(c, "bgp_posterior_batch"));
   if (!c || !h || B <= 0) {
     bgp_set_error("bgp_posterior_batch: bad argument");
     return BGP_ERR_INVALID;
@@ -273,10 +266,10 @@ extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L
 // The same posterior build with item b's training inputs passed through ITS OWN Beta-CDF warp, warp[b * 2d .. (b + 1) * 2d) (log
 // space, [wa_1..wa_d, wb_1..wb_d], as bgp_lml_batch_warped lays them out): the hyper-posterior draws of warp_inputs=True, every one
 // with its own warped design matrix.  A context-level warp is replaced for this call, not composed with it.  The warped inputs stay
-// resident beside K^-1 / alpha for bgp_predict_batch_warped, the only reader of these posteriors (BGP_REFUSE_ROWWARP).
+// resident beside K^-1 / alpha for bgp_predict_batch_warped, the only reader of these posteriors (bgp_guard, BGP_POST_ROWWARP).
 extern "C" int bgp_posterior_batch_warped(bgp_ctx* c, int B, const double* h, const double* warp, double* L, double* alpha,
                                           double* K_inv, double* lml, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_posterior_batch_warped");
+  BGP_TRY(bgp_guard(c, "bgp_posterior_batch_warped"));
   if (!c || !h || !warp || B <= 0) {
     bgp_set_error("bgp_posterior_batch_warped: bad argument");
     return BGP_ERR_INVALID;
@@ -288,7 +281,7 @@ extern "C" int bgp_posterior_batch_warped(bgp_ctx* c, int B, const double* h, co
 // matrices of n x n (kernel_(X_train) without the alpha term), everything behind it as bgp_posterior_batch.
 extern "C" int bgp_posterior_batch_gram(bgp_ctx* c, int B, const double* K, int use_alpha, double* L, double* alpha,
                                         double* K_inv, double* lml, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_posterior_batch_gram");
+  BGP_TRY(bgp_guard(c, "bgp_posterior_batch_gram"));
   if (!c || !K || B <= 0) {
     bgp_set_error("bgp_posterior_batch_gram: bad argument");
     return BGP_ERR_INVALID;
@@ -378,13 +371,6 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
 // the queries (one upload of the m rows, ONE warp launch over the B parameter sets in c->dwarpP); no cov there.
 static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
                        double* cov, const AcqPlan* ap, bool rowwarp = false) {
-  if (B > c->post_B) {
-    bgp_set_error("%s: %d posteriors requested but %d resident (call %s first)",
-                  rowwarp ? "bgp_predict_batch_warped" : "bgp_predict_batch", B, c->post_B,
-                  rowwarp ? "bgp_posterior_batch_warped" : "bgp_posterior_batch");
-    return BGP_ERR_STATE;
-  }
-  BGP_HIP(hipSetDevice(c->device));
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
   const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
   const size_t qs = rowwarp ? (size_t)m * d : 0, xs = rowwarp ? (size_t)n * d : 0;  // per-item strides of queries / training inputs
@@ -444,12 +430,12 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
 
 extern "C" int bgp_predict_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                                  double* var, double* cov) {
-  BGP_REQUIRE_IDLE(c, "bgp_predict_batch");
-  BGP_REFUSE_ROWWARP(c, "bgp_predict_batch");
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xq || !mean || !var || m <= 0 || B <= 0) {
     bgp_set_error("bgp_predict_batch: bad argument");
     return BGP_ERR_INVALID;
   }
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch", BGP_POST_PLAIN, B));
   return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, mean, var, cov, nullptr); });
 }
 
@@ -457,15 +443,12 @@ extern "C" int bgp_predict_batch(bgp_ctx* c, int B, const double* h_kernel, int 
 // its own warped training inputs; everything behind the cross build is bgp_predict_batch's (predict_run).  Mean and variance only.
 extern "C" int bgp_predict_batch_warped(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                                         double* var) {
-  BGP_REQUIRE_IDLE(c, "bgp_predict_batch_warped");
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_warped"));
   if (!c || !h_kernel || !Xq || !mean || !var || m <= 0 || B <= 0) {
     bgp_set_error("bgp_predict_batch_warped: bad argument");
     return BGP_ERR_INVALID;
   }
-  if (!c->post_rowwarp) {
-    bgp_set_error("bgp_predict_batch_warped: the resident posteriors are not per-row warped (call bgp_posterior_batch_warped first)");
-    return BGP_ERR_STATE;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_warped", BGP_POST_ROWWARP, B));
   return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, mean, var, nullptr, nullptr, true); });
 }
 
@@ -483,18 +466,13 @@ __global__ void finish_var_gram_kernel(const double* __restrict__ q, const doubl
 // mean = K_* alpha, var = kss - rowsum((K_* K^-1) o K_*), cov = K_** - (K_* K^-1) K_*^T -- are the kernels of bgp_predict_batch.
 extern "C" int bgp_predict_batch_gram(bgp_ctx* c, int B, int m, const double* Ks, const double* kss, const double* Kss,
                                       double* mean, double* var, double* cov) {
-  BGP_REQUIRE_IDLE(c, "bgp_predict_batch_gram");
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_gram"));
   if (!c || !Ks || !kss || !mean || !var || m <= 0 || B <= 0 || (cov && !Kss)) {
     bgp_set_error("bgp_predict_batch_gram: bad argument");
     return BGP_ERR_INVALID;
   }
-  if (B > c->post_B) {
-    bgp_set_error("bgp_predict_batch_gram: %d posteriors requested but %d resident (call bgp_posterior_batch_gram first)", B,
-                  c->post_B);
-    return BGP_ERR_STATE;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_gram", BGP_POST_ANY, B));
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
     const int npad = c->npad, n = c->n, mpad = pad128(m);
     const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
     const int chunk = post_chunk(B, sKs + 3 * (size_t)mpad + (cov ? sKs + sCv : 0), (size_t)1 << 29, true);
@@ -655,8 +633,7 @@ static int acq_check(const char* who, int n_acq, const int* kinds, const double*
 extern "C" int bgp_acq_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double y_mean,
                              double y_std, int n_acq, const int* kinds, const double* params, int n_samples,
                              double* out) {
-  BGP_REQUIRE_IDLE(c, "bgp_acq_batch");
-  BGP_REFUSE_ROWWARP(c, "bgp_acq_batch");
+  BGP_TRY(bgp_guard(c, "bgp_acq_batch", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xq || m <= 0 || B <= 0) {
     bgp_set_error("bgp_acq_batch: bad argument");
     return BGP_ERR_INVALID;
@@ -665,20 +642,20 @@ extern "C" int bgp_acq_batch(bgp_ctx* c, int B, const double* h_kernel, int m, c
   AcqPlan ap;
   ap.n_acq = n_acq, ap.kinds = kinds, ap.params = params, ap.y_mean = y_mean, ap.y_std = y_std, ap.n_samples = n_samples;
   ap.out = out;
+  BGP_TRY(bgp_guard(c, "bgp_acq_batch", BGP_POST_PLAIN, B));
   return post_call(c, [&] { return predict_run(c, B, h_kernel, m, Xq, nullptr, nullptr, nullptr, &ap); });
 }
 
 // The same closed forms on caller-supplied (mu, std) rows: B x m each, already in y units (y_mean = 0, y_std = 1).
 extern "C" int bgp_acq_values(bgp_ctx* c, int B, int m, const double* mu, const double* std_, int n_acq, const int* kinds,
                               const double* params, int n_samples, double* out) {
-  BGP_REQUIRE_IDLE(c, "bgp_acq_values");
+  BGP_TRY(bgp_guard(c, "bgp_acq_values"));
   if (!c || !mu || !std_ || m <= 0 || B <= 0) {
     bgp_set_error("bgp_acq_values: bad argument");
     return BGP_ERR_INVALID;
   }
   BGP_TRY(acq_check("bgp_acq_values", n_acq, kinds, params, n_samples, out));
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
     const int mpad = pad128(m);
     double *dmu, *dvar;
     AcqScratch as;
@@ -866,18 +843,16 @@ __global__ void grad_reduce_kernel(const double* __restrict__ gpart, double* __r
 }
 
 extern "C" int bgp_lml_grad_batch(bgp_ctx* c, int B, const double* h, double* lml, double* grad, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_lml_grad_batch");
+  BGP_TRY(bgp_guard(c, "bgp_lml_grad_batch"));
   if (!c || !h || !lml || !grad || B <= 0) {
     bgp_set_error("bgp_lml_grad_batch: bad argument");
     return BGP_ERR_INVALID;
   }
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
-    c->post_B = 0;
     const size_t p = c->d + 2;
     std::vector<int> st(B, 0);
     BGP_TRY(bgp_posterior_build(c, B, h, 1, nullptr, nullptr, nullptr, lml, st.data(), nullptr, false));
-    c->post_B = 0;  // the resident K^-1 belong to a gradient evaluation, not to a posterior
+    c->post.drop();  // the resident K^-1 belong to a gradient evaluation, not to a posterior (the build has counted a generation)
     const int ntiles = c->nblk * (c->nblk + 1) / 2;
     double *dgrad, *dH, *dgpart;
     BgpScratch live(c);
@@ -925,18 +900,13 @@ __global__ void pvrs_combine_kernel(const double* __restrict__ G, int ldg, const
 
 extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double* Xcand, int T,
                         const double* Xthompson, double* covs) {
-  BGP_REQUIRE_IDLE(c, "bgp_pvrs");
-  BGP_REFUSE_ROWWARP(c, "bgp_pvrs");
+  BGP_TRY(bgp_guard(c, "bgp_pvrs", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xcand || !Xthompson || !covs || m <= 0 || T <= 0) {
     bgp_set_error("bgp_pvrs: bad argument");
     return BGP_ERR_INVALID;
   }
-  if (c->post_B < 1) {
-    bgp_set_error("bgp_pvrs: no resident posterior (call bgp_posterior_batch / bgp_pvrs_prepare first)");
-    return BGP_ERR_STATE;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_pvrs", BGP_POST_PLAIN, 1));
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
     const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), Tpad = pad128(T);
     const size_t p = d + 2;
     double *dXc, *dXt, *dhk, *dKc, *dKT, *dPT, *dG, *dKti, *du, *dcov, *dst, *dend;
@@ -978,7 +948,7 @@ extern "C" int bgp_pvrs(bgp_ctx* c, const double* h_kernel, int m, const double*
 }
 
 extern "C" int bgp_pvrs_prepare(bgp_ctx* c, const double* h_kernel, int has_alpha_vec, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_pvrs_prepare");
+  BGP_TRY(bgp_guard(c, "bgp_pvrs_prepare"));
   // K_aug's leading block: kernel_(X_train) + alpha only when alpha is a vector
   // (bask/acquisition.py:332-333)
   if (!c || !h_kernel) {
@@ -1095,18 +1065,13 @@ __global__ void __launch_bounds__(256) tri_matmul_draws_kernel(const double* __r
 
 extern "C" int bgp_sample_y(bgp_ctx* c, int b, const double* h_kernel, int m, const double* Xq, int n_draws,
                             const double* z, double jitter, double* out) {
-  BGP_REQUIRE_IDLE(c, "bgp_sample_y");
-  BGP_REFUSE_ROWWARP(c, "bgp_sample_y");
+  BGP_TRY(bgp_guard(c, "bgp_sample_y", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xq || !z || !out || m <= 0 || n_draws <= 0 || b < 0) {
     bgp_set_error("bgp_sample_y: bad argument");
     return BGP_ERR_INVALID;
   }
-  if (b >= c->post_B) {
-    bgp_set_error("bgp_sample_y: posterior %d not resident (%d resident)", b, c->post_B);
-    return BGP_ERR_STATE;
-  }
+  BGP_TRY(bgp_guard(c, "bgp_sample_y", BGP_POST_PLAIN, b + 1));
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
     const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m), rpad = pad128(n_draws);
     const size_t p = d + 2;
     bgp_ctx* w = nullptr;
@@ -1212,19 +1177,13 @@ static int ensure_child(bgp_ctx* c, int mpad, int nb, bgp_ctx** out) {
 // jitter (out[i] undefined) -- the caller retries those items with a larger jitter.
 extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const double* h_kernel, int m, const double* Xq,
                                   const double* z, double jitter, double* out, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_sample_y_batch");
-  BGP_REFUSE_ROWWARP(c, "bgp_sample_y_batch");
+  BGP_TRY(bgp_guard(c, "bgp_sample_y_batch", BGP_POST_PLAIN));
   if (!c || !pidx || !h_kernel || !Xq || !z || !out || !status || m <= 0 || B <= 0) {
     bgp_set_error("bgp_sample_y_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  for (int i = 0; i < B; i++)
-    if (pidx[i] < 0 || pidx[i] >= c->post_B) {
-      bgp_set_error("bgp_sample_y_batch: posterior %d not resident (%d resident)", pidx[i], c->post_B);
-      return BGP_ERR_STATE;
-    }
+  BGP_TRY(bgp_guard(c, "bgp_sample_y_batch", BGP_POST_PLAIN, 0, pidx, B));
   return post_call(c, [&]() -> int {
-    BGP_HIP(hipSetDevice(c->device));
     const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
     const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
     // per item: K_*, P, cov (child), mean / z / out; 1 << 30 doubles per chunk (8 GiB)

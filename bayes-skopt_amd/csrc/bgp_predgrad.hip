@@ -251,119 +251,110 @@ static int pg_check(bgp_ctx* c, const char* who) {
 
 extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,
                                       double* var, double* dmean, double* dvar) {
-  BGP_REQUIRE_IDLE(c, "bgp_predict_grad_batch");
-  BGP_REFUSE_ROWWARP(c, "bgp_predict_grad_batch");
+  BGP_TRY(bgp_guard(c, "bgp_predict_grad_batch", BGP_POST_PLAIN));
   if (!c || !h_kernel || !Xq || !mean || !var || !dmean || m <= 0 || B <= 0) {
     bgp_set_error("bgp_predict_grad_batch: bad argument");
     return BGP_ERR_INVALID;
   }
-  int rc = pg_check(c, "bgp_predict_grad_batch");
-  if (rc) return rc;
-  if (B > c->post_B) {
-    bgp_set_error("bgp_predict_grad_batch: %d posteriors requested but %d resident (call bgp_posterior_batch first)", B,
-                  c->post_B);
-    return BGP_ERR_STATE;
-  }
-  BGP_HIP(hipSetDevice(c->device));
-  const int n = c->n, d = c->d, npad = c->npad;
-  const size_t p = d + 2;
-  const bool lds = n <= PG_NLDS;
-  // chunks of query rows: outputs of B mc (2 + 2 d) doubles, and B mc scratch rows of 2 npad doubles beyond PG_NLDS points
-  size_t mc = std::min<size_t>((size_t)m, 65535);
-  mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)B * (2 + 2 * (size_t)d))));
-  if (!lds) mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 26) / ((size_t)B * 2 * npad)));
-  const size_t Bm = (size_t)B * mc;
-  double *dXq, *dH, *dm, *dv, *ddm, *ddv, *rows = nullptr;
-  BgpScratch live(c);
-  rc = live.carve([&](BgpCarve& s) {
-    dXq = s.take<double>(mc * d);
-    dH = s.take<double>(B * p);
-    dm = s.take<double>(Bm);
-    dv = s.take<double>(Bm);
-    ddm = s.take<double>(Bm * d);
-    ddv = s.take<double>(Bm * d);
-    if (!lds) rows = s.take<double>(Bm * 2 * npad);
+  BGP_TRY(pg_check(c, "bgp_predict_grad_batch"));
+  BGP_TRY(bgp_guard(c, "bgp_predict_grad_batch", BGP_POST_PLAIN, B));
+  return post_call(c, [&]() -> int {
+    const int n = c->n, d = c->d, npad = c->npad;
+    const size_t p = d + 2;
+    const bool lds = n <= PG_NLDS;
+    // chunks of query rows: outputs of B mc (2 + 2 d) doubles, and B mc scratch rows of 2 npad doubles beyond PG_NLDS points
+    size_t mc = std::min<size_t>((size_t)m, 65535);
+    mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)B * (2 + 2 * (size_t)d))));
+    if (!lds) mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 26) / ((size_t)B * 2 * npad)));
+    const size_t Bm = (size_t)B * mc;
+    double *dXq, *dH, *dm, *dv, *ddm, *ddv, *rows = nullptr;
+    BgpScratch live(c);
+    int rc = live.carve([&](BgpCarve& s) {
+      dXq = s.take<double>(mc * d);
+      dH = s.take<double>(B * p);
+      dm = s.take<double>(Bm);
+      dv = s.take<double>(Bm);
+      ddm = s.take<double>(Bm * d);
+      ddv = s.take<double>(Bm * d);
+      if (!lds) rows = s.take<double>(Bm * 2 * npad);
+    });
+    if (rc) return rc;
+    const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
+    BGP_HIP(bgp_memcpy_async(dH, h_kernel, B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
+      const int mm = (int)std::min(mc, (size_t)m - m0);
+      BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      KB_DISPATCH(c->ks.stationary, c->ks.form,
+                  hipLaunchKernelGGL((pg_rows_kernel<S, F>), dim3(mm, B), dim3(PG_NT), shmem, c->stream, c->dXeff, n, d, npad,
+                                     c->dalpha_sol, c->dKinv, dH, dXq, mm, rows, dm, dv, ddm, dvar ? ddv : nullptr));
+      BGP_HIP(hipGetLastError());
+      const size_t w1 = (size_t)mm * sizeof(double), wd = (size_t)mm * d * sizeof(double);
+      BGP_HIP(bgp_memcpy2d_async(mean + m0, (size_t)m * sizeof(double), dm, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
+      BGP_HIP(bgp_memcpy2d_async(var + m0, (size_t)m * sizeof(double), dv, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
+      BGP_HIP(bgp_memcpy2d_async(dmean + m0 * d, (size_t)m * d * sizeof(double), ddm, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
+      if (dvar)
+        BGP_HIP(bgp_memcpy2d_async(dvar + m0 * d, (size_t)m * d * sizeof(double), ddv, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
+      BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the buffers)
+    }
+    return BGP_OK;
   });
-  if (rc) return rc;
-  const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
-  BGP_HIP(bgp_memcpy_async(dH, h_kernel, B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
-    const int mm = (int)std::min(mc, (size_t)m - m0);
-    BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    KB_DISPATCH(c->ks.stationary, c->ks.form,
-                hipLaunchKernelGGL((pg_rows_kernel<S, F>), dim3(mm, B), dim3(PG_NT), shmem, c->stream, c->dXeff, n, d, npad,
-                                   c->dalpha_sol, c->dKinv, dH, dXq, mm, rows, dm, dv, ddm, dvar ? ddv : nullptr));
-    BGP_HIP(hipGetLastError());
-    const size_t w1 = (size_t)mm * sizeof(double), wd = (size_t)mm * d * sizeof(double);
-    BGP_HIP(bgp_memcpy2d_async(mean + m0, (size_t)m * sizeof(double), dm, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
-    BGP_HIP(bgp_memcpy2d_async(var + m0, (size_t)m * sizeof(double), dv, w1, w1, B, hipMemcpyDeviceToHost, c->stream));
-    BGP_HIP(bgp_memcpy2d_async(dmean + m0 * d, (size_t)m * d * sizeof(double), ddm, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
-    if (dvar)
-      BGP_HIP(bgp_memcpy2d_async(dvar + m0 * d, (size_t)m * d * sizeof(double), ddv, wd, wd, B, hipMemcpyDeviceToHost, c->stream));
-    BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the buffers)
-  }
-  return BGP_OK;
 }
 
 extern "C" int bgp_minimize_starts(bgp_ctx* c, int b, const double* h_kernel, double y_mean, double y_std, double kappa, int S_,
                                    const double* X0, const double* lo, const double* hi, double gtol, int max_iter, double* X_out,
                                    double* mean_out, double* var_out, int* iters, int* evals, int* status) {
-  BGP_REQUIRE_IDLE(c, "bgp_minimize_starts");
-  BGP_REFUSE_ROWWARP(c, "bgp_minimize_starts");
+  BGP_TRY(bgp_guard(c, "bgp_minimize_starts", BGP_POST_PLAIN));
   if (!c || !h_kernel || !X0 || !lo || !hi || !X_out || !mean_out || !var_out || !iters || !evals || !status || S_ <= 0 ||
       S_ > 65535 || b < 0 || max_iter < 0 || !(gtol >= 0.0)) {
     bgp_set_error("bgp_minimize_starts: bad argument");
     return BGP_ERR_INVALID;
   }
-  int rc = pg_check(c, "bgp_minimize_starts");
-  if (rc) return rc;
+  BGP_TRY(pg_check(c, "bgp_minimize_starts"));
   for (int t = 0; t < c->d; t++)
     if (!(lo[t] <= hi[t])) {
       bgp_set_error("bgp_minimize_starts: empty box in dimension %d", t);
       return BGP_ERR_INVALID;
     }
-  if (b >= c->post_B) {
-    bgp_set_error("bgp_minimize_starts: posterior %d not resident (%d resident)", b, c->post_B);
-    return BGP_ERR_STATE;
-  }
-  BGP_HIP(hipSetDevice(c->device));
-  const int n = c->n, d = c->d, npad = c->npad;
-  const size_t p = d + 2, Sd = (size_t)S_ * d;
-  const bool lds = n <= PG_NLDS;
-  double *dH, *dX0, *dXo, *dlo, *dhi, *dm, *dv, *rows = nullptr;
-  int *dit, *dev, *dst;
-  BgpScratch live(c);
-  rc = live.carve([&](BgpCarve& s) {
-    dH = s.take<double>(p);
-    dX0 = s.take<double>(Sd);
-    dXo = s.take<double>(Sd);
-    dlo = s.take<double>(d);
-    dhi = s.take<double>(d);
-    dm = s.take<double>(S_);
-    dv = s.take<double>(S_);
-    dit = s.take<int>(S_);
-    dev = s.take<int>(S_);
-    dst = s.take<int>(S_);
-    if (!lds) rows = s.take<double>((size_t)S_ * 2 * npad);
+  BGP_TRY(bgp_guard(c, "bgp_minimize_starts", BGP_POST_PLAIN, b + 1));
+  return post_call(c, [&]() -> int {
+    const int n = c->n, d = c->d, npad = c->npad;
+    const size_t p = d + 2, Sd = (size_t)S_ * d;
+    const bool lds = n <= PG_NLDS;
+    double *dH, *dX0, *dXo, *dlo, *dhi, *dm, *dv, *rows = nullptr;
+    int *dit, *dev, *dst;
+    BgpScratch live(c);
+    int rc = live.carve([&](BgpCarve& s) {
+      dH = s.take<double>(p);
+      dX0 = s.take<double>(Sd);
+      dXo = s.take<double>(Sd);
+      dlo = s.take<double>(d);
+      dhi = s.take<double>(d);
+      dm = s.take<double>(S_);
+      dv = s.take<double>(S_);
+      dit = s.take<int>(S_);
+      dev = s.take<int>(S_);
+      dst = s.take<int>(S_);
+      if (!lds) rows = s.take<double>((size_t)S_ * 2 * npad);
+    });
+    if (rc) return rc;
+    const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
+    hipStream_t st = c->stream;
+    BGP_HIP(bgp_memcpy_async(dH, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, st));
+    BGP_HIP(bgp_memcpy_async(dX0, X0, Sd * sizeof(double), hipMemcpyHostToDevice, st));
+    BGP_HIP(bgp_memcpy_async(dlo, lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+    BGP_HIP(bgp_memcpy_async(dhi, hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((pg_min_kernel<S, F>), dim3(S_), dim3(PG_NT), shmem, st, c->dXeff, n, d, npad,
+                                   c->dalpha_sol + (size_t)b * npad, c->dKinv + (size_t)b * npad * npad, dH, y_mean, y_std, kappa, dX0,
+                                   dlo, dhi, gtol, max_iter, rows, dXo, dm, dv, dit, dev, dst));
+    BGP_HIP(hipGetLastError());
+    BGP_HIP(bgp_memcpy_async(X_out, dXo, Sd * sizeof(double), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_memcpy_async(mean_out, dm, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_memcpy_async(var_out, dv, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_memcpy_async(iters, dit, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_memcpy_async(evals, dev, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_memcpy_async(status, dst, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
+    BGP_HIP(bgp_stream_sync(st));
+    return BGP_OK;
   });
-  if (rc) return rc;
-  const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
-  hipStream_t st = c->stream;
-  BGP_HIP(bgp_memcpy_async(dH, h_kernel, p * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dX0, X0, Sd * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dlo, lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dhi, hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
-  KB_DISPATCH(c->ks.stationary, c->ks.form,
-              hipLaunchKernelGGL((pg_min_kernel<S, F>), dim3(S_), dim3(PG_NT), shmem, st, c->dXeff, n, d, npad,
-                                 c->dalpha_sol + (size_t)b * npad, c->dKinv + (size_t)b * npad * npad, dH, y_mean, y_std, kappa, dX0,
-                                 dlo, dhi, gtol, max_iter, rows, dXo, dm, dv, dit, dev, dst));
-  BGP_HIP(hipGetLastError());
-  BGP_HIP(bgp_memcpy_async(X_out, dXo, Sd * sizeof(double), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_memcpy_async(mean_out, dm, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_memcpy_async(var_out, dv, (size_t)S_ * sizeof(double), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_memcpy_async(iters, dit, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_memcpy_async(evals, dev, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_memcpy_async(status, dst, (size_t)S_ * sizeof(int), hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_stream_sync(st));
-  return BGP_OK;
 }

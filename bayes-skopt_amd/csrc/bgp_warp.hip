@@ -67,29 +67,23 @@ int bgp_launch_warp(bgp_ctx* c, hipStream_t st, const double* dX, const double* 
 // Context-level warp: subsequent posterior / predict / pvrs / gradient / sample_y / un-warped LML calls
 // see the training inputs (and their query points) through this warp.  warp == NULL clears it.
 extern "C" int bgp_ctx_set_warp(bgp_ctx* c, const double* warp) {
-  BGP_REQUIRE_IDLE(c, "bgp_ctx_set_warp");
-  if (!c) {
-    bgp_set_error("bgp_ctx_set_warp: NULL ctx");
-    return BGP_ERR_INVALID;
-  }
-  BGP_HIP(hipSetDevice(c->device));
-  c->post_B = 0;
-  c->post_rowwarp = 0;
-  if (!warp) {
-    c->has_warp = 0;
-    c->dXeff = c->dX;
+  BGP_TRY(bgp_guard(c, "bgp_ctx_set_warp"));
+  c->post.drop();  // (ahead of everything that can fail)
+  return post_call(c, [&]() -> int {
+    if (!warp) {
+      c->has_warp = 0;
+      c->dXeff = c->dX;
+      return BGP_OK;
+    }
+    BGP_TRY(c->dXw1.ensure(c->dy.cap * c->d));  // (the training set's row capacity: alloc_data frees it when that grows)
+    BGP_TRY(c->dwarp.ensure(2 * (size_t)c->d));
+    BGP_HIP(bgp_memcpy_async(c->dwarp, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_TRY(bgp_launch_warp(c, c->stream, c->dX, c->dwarp, c->dXw1, c->n, 1, 0));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    c->has_warp = 1;
+    c->dXeff = c->dXw1;
     return BGP_OK;
-  }
-  int rc = c->dXw1.ensure(c->dy.cap * c->d);  // (the training set's row capacity: alloc_data frees it when that grows)
-  if (!rc) rc = c->dwarp.ensure(2 * (size_t)c->d);
-  if (rc) return rc;
-  BGP_HIP(bgp_memcpy_async(c->dwarp, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  rc = bgp_launch_warp(c, c->stream, c->dX, c->dwarp, c->dXw1, c->n, 1, 0);
-  if (rc) return rc;
-  BGP_HIP(bgp_stream_sync(c->stream));
-  c->has_warp = 1;
-  c->dXeff = c->dXw1;
-  return BGP_OK;
+  });
 }
 
 // Utility: Beta-CDF warp of m points on the device (host-side BayesGPR.warp()).
@@ -98,22 +92,21 @@ extern "C" int bgp_beta_cdf(bgp_ctx* c, int m, const double* X, const double* wa
     bgp_set_error("bgp_beta_cdf: bad argument");
     return BGP_ERR_INVALID;
   }
-  BGP_REQUIRE_IDLE(c, "bgp_beta_cdf");
-  BGP_HIP(hipSetDevice(c->device));
-  const size_t md = (size_t)m * c->d;
-  double *dXi, *dXo, *dW;
-  BgpScratch live(c);
-  int rc = live.carve([&](BgpCarve& s) {
-    dXi = s.take<double>(md);
-    dXo = s.take<double>(md);
-    dW = s.take<double>(2 * (size_t)c->d);
+  BGP_TRY(bgp_guard(c, "bgp_beta_cdf"));
+  return post_call(c, [&]() -> int {
+    const size_t md = (size_t)m * c->d;
+    double *dXi, *dXo, *dW;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dXi = s.take<double>(md);
+      dXo = s.take<double>(md);
+      dW = s.take<double>(2 * (size_t)c->d);
+    }));
+    BGP_HIP(bgp_memcpy_async(dXi, X, md * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_HIP(bgp_memcpy_async(dW, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BGP_TRY(bgp_launch_warp(c, c->stream, dXi, dW, dXo, m, 1, 0));
+    BGP_HIP(bgp_memcpy_async(out, dXo, md * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BGP_HIP(bgp_stream_sync(c->stream));
+    return BGP_OK;
   });
-  if (rc) return rc;
-  BGP_HIP(bgp_memcpy_async(dXi, X, md * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  BGP_HIP(bgp_memcpy_async(dW, warp, 2 * (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  rc = bgp_launch_warp(c, c->stream, dXi, dW, dXo, m, 1, 0);
-  if (rc) return rc;
-  BGP_HIP(bgp_memcpy_async(out, dXo, md * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  BGP_HIP(bgp_stream_sync(c->stream));
-  return BGP_OK;
 }
