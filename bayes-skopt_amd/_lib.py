@@ -53,6 +53,26 @@ class KernelSpecStruct(C.Structure):
     _fields_ = [("form", C.c_int), ("stationary", C.c_int), ("d", C.c_int)]
 
 
+PLAN_REPORT_COLS = 256  # include/bgp.h BGP_PLAN_REPORT_COLS
+
+
+class LmlPlanQuery(C.Structure):
+    """include/bgp.h bgp_lml_plan_query"""
+    _fields_ = [(k, C.c_int) for k in ("nb", "warped", "n", "d", "stationary", "form", "ncu", "timing", "persist", "panel_fused",
+                                       "panels", "nstreams", "ps_permitted")]
+
+
+class LmlPlanReport(C.Structure):
+    """include/bgp.h bgp_lml_plan_report"""
+    _fields_ = [(k, C.c_int) for k in ("nblk", "ncu", "fits", "path", "share", "gsz", "ngroups", "nb_last", "P", "gen_first",
+                                       "gen_last", "gen_groups", "pair", "Bpad", "nchain", "psplit", "dsplit", "ncrit_stream",
+                                       "ncrit", "ps_gen", "total", "tile_wgs", "gram_front", "kbuild", "potrf", "trsm", "syrk",
+                                       "columns", "fused", "generating", "launch_free")] + \
+               [("fused_wgs", C.c_int * PLAN_REPORT_COLS), ("fused_wgs_last", C.c_int * PLAN_REPORT_COLS)]
+
+
+PLAN_PATHS = ("small", "launch_free", "launches")  # bgp_lml_plan_report.path
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -137,6 +157,7 @@ SIGNATURES = {
     "bgp_persist_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_lml_gen_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_debug_ps_trace": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "bgp_debug_lml_plan": (C.c_int, [_vp, C.POINTER(LmlPlanQuery), C.POINTER(LmlPlanReport)]),
     "bgp_debug_pivot_root": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp]),
     "bgp_bench_mfma_f64": (C.c_int, [C.c_int, C.c_int, _dp]),
     "bgp_bench_hbm_copy": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _dp]),
@@ -185,6 +206,27 @@ def _p(a):
 
 def device_count():
     return int(load().bgp_device_count())
+
+
+def _lml_plan(handle, query):
+    rep = LmlPlanReport()
+    _check(load().bgp_debug_lml_plan(handle, C.byref(query), C.byref(rep)), "bgp_debug_lml_plan")
+    out = {k: int(getattr(rep, k)) for k, _ in LmlPlanReport._fields_[:-2]}
+    out["path"] = PLAN_PATHS[rep.path]
+    cols = min(rep.nblk, PLAN_REPORT_COLS)
+    out["fused_wgs"], out["fused_wgs_last"] = list(rep.fused_wgs[:cols]), list(rep.fused_wgs_last[:cols])
+    return out
+
+
+def lml_plan(n, nb, ncu, d=4, warped=False, form="product", stationary="matern52", timing=False, persist=-1, panel_fused=-1,
+             panels=0, nstreams=0, ps_permitted=True):
+    """``bgp_debug_lml_plan`` without a context (no device is touched): what the library would launch for an LML batch of ``nb``
+    matrices of ``n`` rows on a device of ``ncu`` CUs under the given modes (``panels`` / ``nstreams`` 0: the defaults) -- the
+    planner's fields and launch counts as a dict (include/bgp.h bgp_lml_plan_report; ``path`` by name)."""
+    q = LmlPlanQuery(nb=int(nb), warped=int(bool(warped)), n=int(n), d=int(d), stationary=STATIONARY[stationary], form=FORM[form],
+                     ncu=int(ncu), timing=int(bool(timing)), persist=int(persist), panel_fused=int(panel_fused), panels=int(panels),
+                     nstreams=int(nstreams), ps_permitted=int(bool(ps_permitted)))
+    return _lml_plan(None, q)
 
 
 def device_identity(device=0):
@@ -787,6 +829,11 @@ class Context:
         L = np.empty((mp.value, mp.value))
         _check(self._lib.bgp_debug_cov_factor(self._h, C.byref(mp), _p(L)), "bgp_debug_cov_factor")
         return L
+
+    def lml_plan(self, B, warped=False):
+        """What ``lml`` / ``lml_warped`` of ``B`` rows would launch on this context as it stands (``bgp_debug_lml_plan``; nothing is
+        enqueued): see ``_lib.lml_plan``."""
+        return _lml_plan(self._h, LmlPlanQuery(nb=int(B), warped=int(bool(warped))))
 
     def persist_stats(self):
         """Launch-free path bookkeeping (bgp_persist_stats): calls enqueued, time-outs, whether a time-out keeps the path off

@@ -151,7 +151,7 @@ hipError_t bgp_memcpy2d_async(void* dst, size_t dpitch, const void* src, size_t 
 
 int bgp_wait_spins() {
   static const int spins = [] {
-    const char* e = getenv("BGP_WAIT");
+    const char* e = bgp_switch(BGP_SW_WAIT);
     return (e && strcmp(e, "block") == 0) ? 0 : 1;
   }();
   return spins;
@@ -206,7 +206,7 @@ static int upload_data(bgp_ctx* c, int n, const double* X, const double* y, cons
     bgp_set_error("bgp: n must be > 0 and X, y, alpha_diag non-NULL");
     return BGP_ERR_INVALID;
   }
-  static const bool dbg = getenv("BGP_DEBUG_TIMES") != nullptr;
+  static const bool dbg = bgp_switch(BGP_SW_DEBUG_TIMES) != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
@@ -248,16 +248,11 @@ static void warn_unknown_env_once() {
   static bool done = false;
   if (done) return;
   done = true;
-  static const char* known[] = {"BGP_COMM_DIR", "BGP_COMM_PORT", "BGP_COMM_TCP", "BGP_DIST_BACKEND", "BGP_DIST_FORCE",
-                                "BGP_COMM_JOB", "BGP_BENCH_TIMEOUT", "BGP_DEBUG_TIMES", "BGP_PANELS", "BGP_PANEL_FUSED", "BGP_NO_ENV_DEFAULTS",
-                                "BGP_PERSIST", "BGP_PS_COOLDOWN", "BGP_PS_GEN", "BGP_SYRK_GEN", "BGP_PS_PAIR", "BGP_PS_TIMEOUT_MS", "BGP_PS_TIMEOUT_TICKS", "BGP_PS_TRACE", "BGP_STREAMS", "BGP_WAIT", "BGP_COMM_TIMEOUT_S"};
   for (char** e = environ; e && *e; e++) {
     if (strncmp(*e, "BGP_", 4) != 0) continue;
     const char* eq = strchr(*e, '=');
     const size_t len = eq ? (size_t)(eq - *e) : strlen(*e);
-    bool ok = false;
-    for (const char* k : known) ok = ok || (strlen(k) == len && strncmp(k, *e, len) == 0);
-    if (!ok) fprintf(stderr, "libbgp: warning: environment variable %.*s is not one this library reads\n", (int)len, *e);
+    if (!bgp_switch_known(*e, len)) fprintf(stderr, "libbgp: warning: environment variable %.*s is not one this library reads\n", (int)len, *e);
   }
 }
 
@@ -309,19 +304,17 @@ extern "C" int bgp_ctx_create(int device, int n, int d, const double* X, const d
     // the default while the second group's kernels filled the tails of the first group's launches; with the fused panel launches,
     // which take whole CUs, one group measured faster at BASELINE config C: 14.60-14.97 against 15.02-15.11 ms per step,
     // docs/EXPERIMENTS.md G29; results bit-identical either way)
-    const char* env = getenv("BGP_STREAMS");
+    const char* env = bgp_switch(BGP_SW_STREAMS);
     int ns = env ? atoi(env) : 1;
     c->streams_auto = env ? 0 : 1;
     if (ns < 1) ns = 1;
     if (ns > BGP_MAX_STREAMS) ns = BGP_MAX_STREAMS;
     c->nstreams = ns;
-    const char* envps = getenv("BGP_PERSIST");  // 0: never, 1: whenever the batch fits (<= 64 matrices, n > 128); unset: automatic
-    c->persist = envps ? (atoi(envps) != 0 ? 1 : 0) : -1;
-    const char* envpf = getenv("BGP_PANEL_FUSED");  // 0: never, 1: every block column with a solve; unset: bgp_panel_fused_rule
-    c->panel_fused = envpf ? (atoi(envpf) != 0 ? 1 : 0) : -1;
+    c->persist = bgp_switch_tristate(BGP_SW_PERSIST);  // 0: never, 1: whenever the batch fits (<= 64 matrices, n > 128); unset: automatic
+    c->panel_fused = bgp_switch_tristate(BGP_SW_PANEL_FUSED);  // 0: never, 1: every block column with a solve; unset: bgp_panel_fused_rule
     c->panels = 2;
     c->panels_auto = 1;
-    const char* envp = getenv("BGP_PANELS");
+    const char* envp = bgp_switch(BGP_SW_PANELS);
     if (envp && atoi(envp) >= 1 && atoi(envp) <= 64) {
       c->panels = atoi(envp);
       c->panels_auto = 0;
@@ -397,14 +390,12 @@ static int factor_chunk(bgp_ctx* c, int B, const double* h, int full_square) {
   return BGP_OK;
 }
 
-static int lml_batch_impl(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status);
-
-static bool bgp_persist_auto(const bgp_ctx* c, int nb) { return bgp_persist_auto_rule(c->nblk, nb); }
+static int lml_batch_impl(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status, bool own_pinned = false);
 
 int bgp_ps_cooldown_calls() {
   static int v = 0;
   if (!v) {
-    const char* e = getenv("BGP_PS_COOLDOWN");
+    const char* e = bgp_switch(BGP_SW_PS_COOLDOWN);
     v = (e && atoi(e) > 0) ? atoi(e) : 256;
   }
   return v;
@@ -482,68 +473,38 @@ extern "C" int bgp_lml_batch_warped(bgp_ctx* c, int B, const double* h, const do
 // transfers, the device-resident ensemble sampler (bgp_mcmc.hip) calls it between its own kernels.
 int bgp_lml_enqueue_dev(bgp_ctx* c, int nb, int warped) {
   const size_t nd = (size_t)c->n * c->d;
-  // walker groups on separate streams (sizes are multiples of 8: one matrix slot per XCD)
-  int ng = (c->streams_auto && nb < 64) ? 1 : c->nstreams;
-  int gsz = ((nb + ng - 1) / ng + 7) / 8 * 8;
-  if (ng == 1 || nb < 16 || warped) {
-  ng = 1;
-  gsz = nb;
-  }
-  const bool warp = warped != 0;
-  c->panel_groups = ng;  // (the groups' launches share the CUs: a fused panel launch sizes its grid for its share)
-  int rc = BGP_OK;
-  const bool fused_small = c->nblk == 1 && !warp;
-  // launch-free path (bgp_chol.hip, ps_chain_kernel): automatic below 64 matrices per call when the matrices have at
-  // least two block columns; never under per-launch timing (there are no launches to time) or after a timeout
-  const bool use_ps = !fused_small && !c->timing && !c->ps_forbid && bgp_persist_fits(c, nb) &&
-                      (c->persist == 1 || (c->persist == -1 && bgp_persist_auto(c, nb))) && bgp_ps_allowed(c);
-  if (use_ps) c->ps_calls++;
+  // which path, how many walker groups, what generates the Gram blocks: the planner's (bgp_plan.h).  Never launch-free while the
+  // resident sampler redoes a run (ps_forbid), under per-launch timing or while a time-out keeps the path off
+  const BgpLmlPlan plan = bgp_plan_for(c, bgp_lml_shape(c, nb, warped, 0), !c->ps_forbid);
+  if (plan.path == BGP_PATH_SMALL)  // (status is reset in the kernel)
+    return bgp_launch_lml_small(c, 0, nb, c->stream);
   // (ps_resident: the sampler's step kernel has reset the statuses in front of this batch)
-  if (!fused_small && !c->ps_resident) BGP_HIP(hipMemsetAsync(c->dstatus, 0, nb * sizeof(int), c->stream));
-  if (fused_small) {
-    // n <= 128: Gram generation, factorisation and LML fused into one launch (status is reset in the kernel)
-    rc = bgp_launch_lml_small(c, 0, nb, c->stream);
-    if (rc) return rc;
-  } else if (warp) {
-    // per-walker Beta-CDF warp of the design matrix, then the right-looking path on per-walker inputs
-    rc = bgp_launch_warp(c, c->stream, c->dX, c->dwarpB, c->dXwB, c->n, nb, nd);
-    if (rc) return rc;
-    const int gen = !use_ps && bgp_lml_gen_eligible(c, nb);
-    rc = bgp_launch_kbuild_x(c, 0, nb, c->stream, gen ? 2 : 0, 0, 1, c->dXwB, nd);
-    if (rc) return rc;
-    if (use_ps) {
-      rc = bgp_launch_cholesky_persist(c, nb, 0);
-      if (!rc) c->ps_inflight = 1;
-    } else {
-      rc = bgp_launch_cholesky_slice(c, 0, nb, c->stream, 0, gen);
-    }
-    if (rc) return rc;
-  } else if (use_ps) {
+  if (!c->ps_resident) BGP_HIP(hipMemsetAsync(c->dstatus, 0, nb * sizeof(int), c->stream));
+  // per-walker Beta-CDF warp of the design matrix: the Gram kernel reads per-walker inputs
+  if (warped) BGP_TRY(bgp_launch_warp(c, c->stream, c->dX, c->dwarpB, c->dXwB, c->n, nb, nd));
+  if (plan.path == BGP_PATH_LAUNCH_FREE) {
     // small batch: ONE launch-free kernel instead of ~3 launches per block column, the Gram build inside it or in front of it
-    rc = bgp_launch_cholesky_persist(c, nb, 1);
-    if (rc) return rc;
+    if (warped) BGP_TRY(bgp_launch_kbuild_x(c, 0, nb, c->stream, 0, 0, 1, c->dXwB, nd));
+    BGP_TRY(bgp_launch_cholesky_persist(c, plan));
     c->ps_inflight = 1;
-  } else if (ng == 1) {
-    // (gen: the Gram kernel builds block column 0, the first panel group's updates generate the rest in their accumulators)
-    const int gen = bgp_lml_gen_eligible(c, nb);
-    rc = bgp_launch_kbuild(c, nb, gen ? 2 : 0, 0, 1);
-    if (rc) return rc;
-    rc = bgp_launch_cholesky_slice(c, 0, nb, c->stream, 0, gen);
-    if (rc) return rc;
-  } else {
-    BGP_HIP(hipEventRecord(c->ev_ready, c->stream));
-    for (int g = 0, o = 0; o < nb; g++, o += gsz) {
-      const int gb = std::min(gsz, nb - o);
-      hipStream_t st = c->gstream[g];
-      BGP_HIP(hipStreamWaitEvent(st, c->ev_ready, 0));
-      const int gen = bgp_lml_gen_eligible(c, gb);
-      rc = bgp_launch_kbuild_slice(c, o, gb, st, gen ? 2 : 0, 0, 1);
-      if (rc) return rc;
-      rc = bgp_launch_cholesky_slice(c, o, gb, st, 0, gen);
-      if (rc) return rc;
-      BGP_HIP(hipEventRecord(c->ev_done[g], st));
-      BGP_HIP(hipStreamWaitEvent(c->stream, c->ev_done[g], 0));
-    }
+    return BGP_OK;
+  }
+  // launch schedule.  (gen: the Gram kernel builds block column 0, the first panel group's updates generate the rest in their
+  // accumulators)
+  if (plan.share == 1) {
+    const int fs = plan.gen(0) ? 2 : 0;
+    BGP_TRY(warped ? bgp_launch_kbuild_x(c, 0, nb, c->stream, fs, 0, 1, c->dXwB, nd) : bgp_launch_kbuild(c, nb, fs, 0, 1));
+    return bgp_launch_lml_group(c, plan, 0, c->stream);
+  }
+  // walker groups on streams of their own, between two events on the context's stream
+  BGP_HIP(hipEventRecord(c->ev_ready, c->stream));
+  for (int g = 0; g < plan.ngroups; g++) {
+    hipStream_t st = c->gstream[g];
+    BGP_HIP(hipStreamWaitEvent(st, c->ev_ready, 0));
+    BGP_TRY(bgp_launch_kbuild_slice(c, g * plan.gsz, plan.group_nb(g), st, plan.gen(g) ? 2 : 0, 0, 1));
+    BGP_TRY(bgp_launch_lml_group(c, plan, g, st));
+    BGP_HIP(hipEventRecord(c->ev_done[g], st));
+    BGP_HIP(hipStreamWaitEvent(c->stream, c->ev_done[g], 0));
   }
   return BGP_OK;
 }
@@ -554,70 +515,16 @@ int bgp_ensure_warp_buffers(bgp_ctx* c) {
   return rc ? rc : c->dwarpB.ensure((size_t)c->max_batch * 2 * c->d);
 }
 
-static int lml_batch_run(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status,
-                         hipEvent_t& e0, hipEvent_t& e1, int defer_sync = 0) {
-  if (B == 0) return BGP_OK;
-  BGP_HIP(hipSetDevice(c->device));
-  if (warp) {
-    const int rcw = bgp_ensure_warp_buffers(c);
-    if (rcw) return rcw;
-  }
-  const size_t p = c->d + 2;
-  for (int k = 0; k < 6; k++) c->t_ms[k] = 0.0;
-  for (int k = 0; k < 6; k++) c->t_cnt[k] = 0;
-  for (int off = 0; off < B; off += c->max_batch) {
-    const int nb = std::min(c->max_batch, B - off);
-    if (c->timing) {
-      (void)hipEventCreate(&e0);
-      (void)hipEventCreate(&e1);
-      (void)hipEventRecord(e0, c->stream);
-    }
-    // (the submit path hands over the context's own pinned blocks; a caller's pageable block goes through the arena)
-    const bool own = (h == c->hh);
-    if (own)
-      BGP_HIP(hipMemcpyAsync(c->dh, h + (size_t)off * p, nb * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    else
-      BGP_HIP(bgp_memcpy_async(c->dh, h + (size_t)off * p, nb * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (warp)
-      BGP_HIP(bgp_memcpy_async(c->dwarpB, warp + (size_t)off * 2 * c->d, (size_t)nb * 2 * c->d * sizeof(double),
-                               hipMemcpyHostToDevice, c->stream));
-    {
-      const int rc = bgp_lml_enqueue_dev(c, nb, warp ? 1 : 0);
-      if (rc) return rc;
-    }
-    if (own) {
-      BGP_HIP(hipMemcpyAsync(lml + off, c->dlml, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      if (status) BGP_HIP(hipMemcpyAsync(status + off, c->dstatus, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    } else {
-      BGP_HIP(bgp_memcpy_async(lml + off, c->dlml, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      if (status) BGP_HIP(bgp_memcpy_async(status + off, c->dstatus, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (c->timing) (void)hipEventRecord(e1, c->stream);
-    if (defer_sync) return BGP_OK;  // (single chunk, timing off: bgp_lml_batch_wait synchronises)
-    BGP_HIP(bgp_stream_sync(c->stream));
-    if (ps_check(c)) {
-      off -= c->max_batch;  // redo this chunk (ps_disabled is set: the multi-launch path takes it)
-      continue;
-    }
-    bgp_tcollect(c);
-    if (c->timing) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      c->t_ms[4] += ms;
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      e0 = e1 = nullptr;
-    }
-  }
-  return BGP_OK;
-}
-
-// One exit path: whatever step failed, the context's streams are drained (launches of the other walker group may
-// still be in flight), the per-launch timing events of the call are released and the sticky HIP error is cleared, so
-// that the context stays usable and nothing leaks.
-static int lml_batch_impl(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const int rc = lml_batch_run(c, B, h, warp, lml, status, e0, e1);
+// ONE exit path for the LML entry points, in the manner of post_call (bgp_common.h): the body runs on the context's device, and
+// whatever step failed, the context's streams are drained (launches of the other walker group may still be in flight), the
+// per-launch timing events of the call are released and the sticky HIP error is cleared, so that the context stays usable and
+// nothing leaks.  The success path is the body's own.
+template <class Body>
+static int lml_call(bgp_ctx* c, Body&& body) {
+  const int rc = [&]() -> int {
+    BGP_HIP(hipSetDevice(c->device));
+    return body();
+  }();
   if (rc != BGP_OK) {
     (void)hipStreamSynchronize(c->stream);
     for (int g = 0; g < BGP_MAX_STREAMS; g++)
@@ -625,11 +532,68 @@ static int lml_batch_impl(bgp_ctx* c, int B, const double* h, const double* warp
     for (hipEvent_t ev : c->ev) (void)hipEventDestroy(ev);
     c->ev.clear();
     c->evcat.clear();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipGetLastError();
   }
   return rc;
+}
+
+// the (start, stop) events around one chunk under per-launch timing (bgp_last_timing's "whole call on device")
+struct LmlChunkTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  explicit LmlChunkTimer(bool on) {
+    if (!on) return;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+  }
+  LmlChunkTimer(const LmlChunkTimer&) = delete;
+  ~LmlChunkTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+// The batch in chunks of max_batch: upload, bgp_lml_enqueue_dev, download, and -- unless the caller synchronises later (defer_sync:
+// a single chunk, timing off; bgp_lml_batch_wait) -- the wait and the collection of the timings.  own_pinned: h is the context's
+// own pinned block (the submit path and its redo), and h, lml and status are copied directly -- h alone decides, as before: on the
+// redo of bgp_lml_batch_wait lml and status are the caller's arrays all the same; else every block goes through the arena.
+static int lml_batch_run(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status, bool own_pinned,
+                         bool defer_sync) {
+  if (warp) BGP_TRY(bgp_ensure_warp_buffers(c));
+  const size_t p = c->d + 2;
+  for (int k = 0; k < 6; k++) c->t_ms[k] = 0.0;
+  for (int k = 0; k < 6; k++) c->t_cnt[k] = 0;
+  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    return own_pinned ? hipMemcpyAsync(dst, src, bytes, kind, c->stream) : bgp_memcpy_async(dst, src, bytes, kind, c->stream);
+  };
+  for (int off = 0; off < B; off += c->max_batch) {
+    const int nb = std::min(c->max_batch, B - off);
+    LmlChunkTimer t(c->timing);
+    do {
+      if (c->timing) (void)hipEventRecord(t.e0, c->stream);
+      BGP_HIP(copy(c->dh, h + (size_t)off * p, nb * p * sizeof(double), hipMemcpyHostToDevice));
+      if (warp)
+        BGP_HIP(bgp_memcpy_async(c->dwarpB, warp + (size_t)off * 2 * c->d, (size_t)nb * 2 * c->d * sizeof(double),
+                                 hipMemcpyHostToDevice, c->stream));
+      BGP_TRY(bgp_lml_enqueue_dev(c, nb, warp ? 1 : 0));
+      BGP_HIP(copy(lml + off, c->dlml, nb * sizeof(double), hipMemcpyDeviceToHost));
+      if (status) BGP_HIP(copy(status + off, c->dstatus, nb * sizeof(int), hipMemcpyDeviceToHost));
+      if (c->timing) (void)hipEventRecord(t.e1, c->stream);
+      if (defer_sync) return BGP_OK;
+      BGP_HIP(bgp_stream_sync(c->stream));
+    } while (ps_check(c));  // timed out: redo this chunk (ps_disabled is set: the multi-launch path takes it)
+    bgp_tcollect(c);
+    if (c->timing) {
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, t.e0, t.e1);
+      c->t_ms[4] += ms;
+    }
+  }
+  return BGP_OK;
+}
+
+static int lml_batch_impl(bgp_ctx* c, int B, const double* h, const double* warp, double* lml, int* status, bool own_pinned) {
+  if (B == 0) return BGP_OK;
+  return lml_call(c, [&] { return lml_batch_run(c, B, h, warp, lml, status, own_pinned, false); });
 }
 
 // Asynchronous form of bgp_lml_batch for the sampler's inner loop: submit enqueues the whole half-step (upload of the
@@ -652,28 +616,20 @@ static int lml_submit_impl(bgp_ctx* c, int B, const double* h, const double* war
     bgp_set_error("%s: B = %d exceeds max_batch = %d: use bgp_lml_batch", who, B, c->max_batch);
     return BGP_ERR_INVALID;
   }
-  BGP_HIP(hipSetDevice(c->device));
-  int rca = c->hlml.ensure(c->max_batch);
-  if (!rca) rca = c->hstatus.ensure(c->max_batch);
-  if (!rca) rca = c->hh.ensure((size_t)c->max_batch * (c->d + 2));
-  if (!rca && warp) rca = c->hwarp.ensure((size_t)c->max_batch * 2 * c->d);
-  if (rca) return rca;
-  // the proposals go up from pinned memory too: an asynchronous copy out of a pageable numpy array costs the runtime
-  // a page lock / unlock per call (tens of microseconds in front of every half-step)
-  memcpy(c->hh, h, (size_t)B * (c->d + 2) * sizeof(double));
-  if (warp) memcpy(c->hwarp, warp, (size_t)B * 2 * c->d * sizeof(double));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const int rc = lml_batch_run(c, B, c->hh, warp ? c->hwarp : nullptr, c->hlml, c->hstatus, e0, e1, 1);
-  if (rc != BGP_OK) {
-    (void)hipStreamSynchronize(c->stream);
-    for (int g = 0; g < BGP_MAX_STREAMS; g++)
-      if (c->gstream[g]) (void)hipStreamSynchronize(c->gstream[g]);
-    (void)hipGetLastError();
-    return rc;
-  }
-  c->pending_B = B;
-  c->pending_warped = warp ? 1 : 0;
-  return BGP_OK;
+  return lml_call(c, [&]() -> int {
+    BGP_TRY(c->hlml.ensure(c->max_batch));
+    BGP_TRY(c->hstatus.ensure(c->max_batch));
+    BGP_TRY(c->hh.ensure((size_t)c->max_batch * (c->d + 2)));
+    if (warp) BGP_TRY(c->hwarp.ensure((size_t)c->max_batch * 2 * c->d));
+    // the proposals go up from pinned memory too: an asynchronous copy out of a pageable numpy array costs the runtime
+    // a page lock / unlock per call (tens of microseconds in front of every half-step)
+    memcpy(c->hh, h, (size_t)B * (c->d + 2) * sizeof(double));
+    if (warp) memcpy(c->hwarp, warp, (size_t)B * 2 * c->d * sizeof(double));
+    BGP_TRY(lml_batch_run(c, B, c->hh, warp ? c->hwarp : nullptr, c->hlml, c->hstatus, true, true));
+    c->pending_B = B;
+    c->pending_warped = warp ? 1 : 0;
+    return BGP_OK;
+  });
 }
 
 extern "C" int bgp_lml_batch_submit(bgp_ctx* c, int B, const double* h) {
@@ -705,7 +661,7 @@ extern "C" int bgp_lml_batch_wait(bgp_ctx* c, double* lml, int* status) {
   BGP_HIP(bgp_stream_sync(c->stream));
   if (ps_check(c)) {  // redo on the multi-launch path (the submitted block is still in the pinned buffers)
     const double* wp = c->pending_warped ? c->hwarp : nullptr;
-    return lml_batch_impl(c, B, c->hh, wp, lml, status);
+    return lml_batch_impl(c, B, c->hh, wp, lml, status, true);
   }
   memcpy(lml, c->hlml, (size_t)B * sizeof(double));
   if (status) memcpy(status, c->hstatus, (size_t)B * sizeof(int));
@@ -717,7 +673,50 @@ extern "C" int bgp_lml_batch_wait(bgp_ctx* c, double* lml, int* status) {
 // multi-launch path.
 int bgp_lml_redo_if_abandoned(bgp_ctx* c, int B) {
   if (!ps_check(c)) return BGP_OK;
-  return lml_batch_impl(c, B, c->hh, c->pending_warped ? c->hwarp : nullptr, c->hlml, c->hstatus);
+  return lml_batch_impl(c, B, c->hh, c->pending_warped ? c->hwarp : nullptr, c->hlml, c->hstatus, true);
+}
+
+// See include/bgp.h: what bgp_lml_enqueue_dev would launch for the batch, from the planner alone.  Nothing is enqueued, counted or
+// changed -- the cool-down is looked at, not asked (bgp_ps_allowed counts).
+extern "C" int bgp_debug_lml_plan(bgp_ctx* c, const bgp_lml_plan_query* q, bgp_lml_plan_report* r) {
+  if (!q || !r || q->nb < 1 || (c && q->nb > c->max_batch) ||
+      (!c && (q->n < 1 || q->d < 1 || q->d > BGP_MAX_D || q->ncu < 1 || q->panels < 0 || q->panels > 64 || q->nstreams < 0 ||
+              q->nstreams > BGP_MAX_STREAMS || q->persist < -1 || q->persist > 1 || q->panel_fused < -1 || q->panel_fused > 1 ||
+              q->stationary < 0 || q->stationary > 3 || q->form < 0 || q->form > 1))) {
+    bgp_set_error("bgp_debug_lml_plan: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  BgpLmlShape s{};
+  if (c) {
+    s = bgp_lml_shape(c, q->nb, q->warped, 0);
+    s.ps_permitted = !c->ps_forbid && !c->ps_disabled;
+  } else {
+    s.n = q->n, s.nblk = (q->n + BGP_NB - 1) / BGP_NB, s.d = q->d, s.stationary = q->stationary, s.form = q->form, s.ncu = q->ncu;
+    s.nb = q->nb, s.warped = q->warped != 0;
+    s.timing = q->timing, s.persist = q->persist, s.panel_fused = q->panel_fused;
+    s.panels = q->panels ? q->panels : 2, s.panels_auto = q->panels == 0;
+    s.nstreams = q->nstreams ? q->nstreams : 1, s.streams_auto = q->nstreams == 0;
+    s.ps_permitted = q->ps_permitted != 0;
+    bgp_shape_read_call_switches(s);
+  }
+  if (bgp_plan_wants_launch_free(s)) bgp_shape_read_ps_switches(s);
+  const BgpLmlPlan p = bgp_plan_lml(s);
+  const BgpLmlLaunches n = bgp_plan_launches(p);
+  const int last = p.ngroups - 1;
+  *r = bgp_lml_plan_report{};
+  r->nblk = s.nblk, r->ncu = s.ncu, r->fits = bgp_persist_fits(s.nblk, s.ncu, s.nb);
+  r->path = p.path, r->share = p.share, r->gsz = p.gsz, r->ngroups = p.ngroups, r->nb_last = p.group_nb(last), r->P = p.P;
+  r->gen_first = p.gen(0), r->gen_last = p.gen(last);
+  for (int g = 0; g < p.ngroups; g++) r->gen_groups += p.gen(g);
+  r->pair = p.pair, r->Bpad = p.Bpad, r->nchain = p.nchain, r->psplit = p.psplit, r->dsplit = p.dsplit;
+  r->ncrit_stream = p.ncrit_stream, r->ncrit = p.ncrit, r->ps_gen = p.ps_gen, r->total = p.total, r->tile_wgs = p.tile_wgs;
+  r->gram_front = p.gram_front;
+  r->kbuild = n.kbuild, r->potrf = n.potrf, r->trsm = n.trsm, r->syrk = n.syrk, r->columns = n.columns, r->fused = n.fused;
+  r->generating = n.generating, r->launch_free = n.launch_free;
+  if (p.path == BGP_PATH_LAUNCHES)
+    for (int k = 0; k < s.nblk && k < BGP_PLAN_REPORT_COLS; k++)
+      r->fused_wgs[k] = p.fused_wgs(0, k), r->fused_wgs_last[k] = p.fused_wgs(last, k);
+  return BGP_OK;
 }
 
 extern "C" int bgp_kernel_matrix(bgp_ctx* c, const double* h, double* K) {
@@ -820,12 +819,7 @@ extern "C" int bgp_set_persist(bgp_ctx* c, int mode) {
     return BGP_ERR_INVALID;
   }
   BGP_TRY(bgp_guard(c, "bgp_set_persist"));
-  if (mode == -1) {
-    const char* envps = getenv("BGP_PERSIST");
-    c->persist = envps ? (atoi(envps) != 0 ? 1 : 0) : -1;
-  } else {
-    c->persist = mode;
-  }
+  c->persist = mode == -1 ? bgp_switch_tristate(BGP_SW_PERSIST) : mode;
   if (mode == 1) c->ps_disabled = c->ps_cooldown = 0;
   return BGP_OK;
 }
@@ -839,12 +833,7 @@ extern "C" int bgp_set_panel_fused(bgp_ctx* c, int mode) {
     return BGP_ERR_INVALID;
   }
   BGP_TRY(bgp_guard(c, "bgp_set_panel_fused"));
-  if (mode == -1) {
-    const char* envpf = getenv("BGP_PANEL_FUSED");
-    c->panel_fused = envpf ? (atoi(envpf) != 0 ? 1 : 0) : -1;
-  } else {
-    c->panel_fused = mode;
-  }
+  c->panel_fused = mode == -1 ? bgp_switch_tristate(BGP_SW_PANEL_FUSED) : mode;
   return BGP_OK;
 }
 

@@ -13,12 +13,13 @@
 //   panel solve   X_i = A_ik W_kk^T  (fp64 MFMA),  y_i -= X_i z_k
 //   trailing upd. A_ij -= X_i X_j^T  (fp64 MFMA; the n^3/3 bulk -- the kernel the roofline fraction is quoted on)
 // Panel solve and trailing update are trsm4_kernel / syrk4_kernel on the LDS-DMA ring (bgp_syrk4.hip):
-//   * LML path (bgp_lml_batch; the MCMC hot loop): scheduled in groups of P block columns by bgp_launch_cholesky_slice;
+//   * LML path (bgp_lml_batch; the MCMC hot loop): the schedule the planner chose (bgp_plan.h: bgp_plan_lml, bgp_lml_schedule),
+//     enqueued group by group by bgp_launch_lml_group;
 //   * posterior builds on the augmented matrix (bgp_post.hip; once per sample(), per hyper-posterior draw of an
 //     acquisition and per gradient evaluation): the same kernels in single-panel mode with the active-row remap of
 //     bgp_rowblk (bgp_device.h);
 //   * small batches of the LML path and sample_y's covariance: ONE persistent kernel instead of the launches
-//     (bgp_launch_cholesky_persist below, ps_kernel in bgp_syrk4.hip, the diagonal-block code of both in bgp_pf.h).
+//     (bgp_launch_cholesky_persist below, ps_kernel in bgp_ps.hip, the diagonal-block code of both in bgp_pf.h).
 // (Round 1's VGPR-staged trsm_kernel / syrk_kernel / syrk2_kernel / trsm8_kernel and the left-looking variant are A/B
 // references of the benches under tools/legacy/ now; they are not part of libbgp.so.)
 #include "bgp_common.h"
@@ -267,7 +268,7 @@ extern "C" int bgp_debug_pivot_root(int device, int n, const double* x, double* 
 
 // ------------------------------------------------------------------------------------------
 // Launch-free factorisation of SMALL batches (B <= 64 matrices, or one large matrix): ONE persistent kernel per batch
-// instead of ~3 dependent launches per block column (ps_kernel, bgp_syrk4.hip; the diagonal-block code is bgp_pf.h).
+// instead of ~3 dependent launches per block column (ps_kernel, bgp_ps.hip; the diagonal-block code is bgp_pf.h).
 //
 // Why: with few matrices the chain of dependent launches is the critical path -- potrf(k) keeps B of the 256 CUs busy
 // for 30 us while the rest idle, and the trailing update of step k cannot overlap the next panel (stream / event
@@ -276,7 +277,7 @@ extern "C" int bgp_debug_pivot_root(int device, int n, const double* x, double* 
 //   * chain role (workgroups 0 .. B-1, one per matrix; ps_chain_role, bgp_pf.h): walks the block columns J = 0 .. nblk-1:
 //     factorises block (J, J) (pf_block: the same code as potrf_kernel), publishes L_JJ / W_JJ / z_J (wready[J]), then
 //     solves block (J+1, J) and applies the last panel to block (J+1, J+1) ITSELF -- the next tile never leaves its LDS;
-//   * tile role (the other workgroups, one per remaining CU; ps_tile_role, bgp_syrk4.hip): draw left-looking block tasks
+//   * tile role (the other workgroups, one per remaining CU; ps_tile_role, bgp_ps.hip): draw left-looking block tasks
 //     from ticket counters in an order that is topological for the dependency graph -- panel solves S(I, J), I >= J+2, and
 //     the pre-updates that hand blocks (I, I-1) and (I, I) to the chain -- waiting on / raising xready, subrdy, diagrdy.
 // Both roles need a whole CU (157 / 128 KB of LDS, one array), the grid has at most one workgroup per CU and the
@@ -288,7 +289,6 @@ extern "C" int bgp_debug_pivot_root(int device, int n, const double* x, double* 
 // the batch on the multi-launch path.  Arithmetic, operand order and summation order are those of the multi-launch path:
 // the log-likelihoods are bit-identical (tests/test_gpu_persist.py).
 // ------------------------------------------------------------------------------------------
-int bgp_ps_total_tasks(int B, int nblk, int np, int gen);
 void bgp_launch_ps(hipStream_t st, const PsArgs& a, int nwg);
 
 // BGP_PS_TRACE=1: the time stamps of the last launch-free call (100 MHz wall clock): dims = {B, nblk, total tasks};
@@ -306,29 +306,22 @@ extern "C" int bgp_debug_ps_trace(bgp_ctx* c, int* dims, unsigned long long* out
   return BGP_OK;
 }
 
-// Can this batch take the launch-free path?  (at least two block columns; a CU per matrix and at least as many, and at
-// least 32, left for the tile workers -- a partitioned device with 32 CUs never takes it)
-int bgp_persist_fits(bgp_ctx* c, int B) {
-  return B >= 1 && B <= 64 && c->nblk >= 2 && c->nblk <= 255 && c->ncu - B >= std::max(32, B);
-}
-
-// Host side of the launch-free factorisation: the B Gram matrices of the batch are already on c->stream (K-build);
-// this enqueues ONE kernel behind them -- B chain workgroups + one tile workgroup for every other CU -- and the copy of
-// the error word to pinned memory (ctx->ps_herr): != 0 after the synchronisation means a wait timed out and the caller
-// redoes the batch on the multi-launch path.
 // the flag block of a launch-free call with B matrices exists (grown with 50 % head room; contents undefined)
 int bgp_ps_ensure_flags(bgp_ctx* c, int B) {
   const size_t words = ps_flag_words(B, c->nblk);
   return c->ps_flags.ensure(words, words + words / 2);
 }
 
-int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
-  const int nblk = c->nblk, ld = c->npad;
-  if (!bgp_persist_fits(c, B)) {
+// Host side of the launch-free factorisation as the planner laid it out (bgp_plan.h: chain pairs, critical pool, task total, tile
+// workgroups, Gram blocks inside the launch or by a kernel in front of it): ONE kernel on c->stream -- the chain workgroups + the
+// tile workgroups -- and the copy of the error word to pinned memory (ctx->ps_herr): != 0 after the synchronisation means a wait
+// timed out and the caller redoes the batch on the multi-launch path.  A warped batch's Gram matrices are on the stream already.
+int bgp_launch_cholesky_persist(bgp_ctx* c, const BgpLmlPlan& plan) {
+  const int nblk = c->nblk, ld = c->npad, B = plan.in.nb;
+  if (plan.path != BGP_PATH_LAUNCH_FREE) {
     bgp_set_error("bgp_launch_cholesky_persist: B = %d, nblk = %d outside the persistent path's range", B, nblk);
     return BGP_ERR_INVALID;
   }
-  const int ncu = c->ncu;
   if (!c->ps_herr) {
     const int rch = c->ps_herr.ensure(1);
     if (rch) return rch;
@@ -336,21 +329,10 @@ int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
   }
   std::fill(c->fused_col.begin(), c->fused_col.end(), 0);  // (this path leaves every block of L and z in place)
   const size_t words = ps_flag_words(B, nblk);
-  {
-    const int rcf = bgp_ps_ensure_flags(c, B);
-    if (rcf) return rcf;
-  }
+  BGP_TRY(bgp_ps_ensure_flags(c, B));
   // (the device-resident sampler's step kernel has zeroed the block in front of this call: one dispatch less per half-step)
   if (!c->ps_resident) BGP_HIP(hipMemsetAsync(c->ps_flags, 0, words * sizeof(unsigned), c->stream));
-  static unsigned long long limit = 0;
-  if (!limit) {
-    const char* e = getenv("BGP_PS_TIMEOUT_MS");
-    // 100 MHz wall clock; default 500 ms: a healthy call lasts at most ~20 ms, and two PROCESSES that share a GPU and meet in
-    // this path can block each other's resident workgroups (measured: one time-out in 1 800 calls each, results correct)
-    limit = 100000ull * (unsigned long long)((e && atoi(e) > 0) ? atoi(e) : 500);
-    const char* et = getenv("BGP_PS_TIMEOUT_TICKS");  // (tests: a bound no wait can meet)
-    if (et && atoll(et) > 0) limit = (unsigned long long)atoll(et);
-  }
+  if (plan.gram_front && !plan.in.warped) BGP_TRY(bgp_launch_kbuild(c, B, 0, 0, 1));
   PsArgs a;
   a.K = c->dK;
   a.W = c->dW;
@@ -365,95 +347,32 @@ int bgp_launch_cholesky_persist(bgp_ctx* c, int B, int build_gram) {
   a.B = B;
   a.ystride = ld;
   a.mstride = (size_t)ld * ld;
-  {
-    // chain pairs (bgp_pf.h): two workgroups per matrix alternate over the block columns, the idle one preparing the next
-    // diagonal block UNDER the other's factorisation; needs 2 * Bpad CUs and at least as many (and 32) left for the tile role.
-    // BGP_PS_PAIR = 0 / 1 fixes it.
-    static int want = -2;
-    if (want == -2) {
-      const char* e = getenv("BGP_PS_PAIR");
-      want = e ? (atoi(e) != 0 ? 1 : 0) : -1;
-    }
-    a.Bpad = 8 * ((B + 7) / 8);
-    // automatic: where the chain is the bound and the pairs measured faster (bgp_pair_auto_rule, bgp_common.h)
-    const bool fits = nblk >= 3 && ncu - 2 * a.Bpad >= std::max(32, B);
-    a.pair = (fits && (want == 1 || (want == -1 && bgp_pair_auto_rule(nblk, B)))) ? 1 : 0;
-    a.nchain = a.pair ? 2 * a.Bpad : B;
-    // P(I) -- the pre-update of block (I, I-1) that the chain waits for -- as ONE task behind a single chain workgroup, in four
-    // 64 x 64 quadrants (and Dg(I) in three) behind chain pairs, whose cycle runs THROUGH this task (the
-    // two-slice and the mixed variants measured slower and left the library in round 5)
-    a.psplit = a.pair ? 4 : 1;
-    a.dsplit = a.psplit == 4 ? 3 : 1;
-    a.total = bgp_ps_total_tasks(B, nblk, a.psplit, 0);
-    // pair mode: the panel solves S(J+2, J) and S(J+3, J) follow pf_block(J) row block by row block (S(J+3, J) feeds the
-    // quadrants ahead of the next column's critical solve; streaming fewer measured slower)
-    a.ncrit_stream = 3;
-  }
-  int tile_wgs = std::min(a.total, ncu - a.nchain);
-  {
-    // critical pool of the tile role: the three tasks at the head of a block column -- S(J+2, J), P(J+2), Dg(J+2) -- get
-    // workgroups of their own, one per task of a column.  Measured in round 3: with up to ~10 block columns the chain waits less
-    // (n = 1024 x 32: 0.63 -> 0.59 ms, 975 x 50: 0.93 -> 0.84); with more, these left-looking tasks are long and want the
-    // look-ahead the single list gives them (n = 2048 x 9: 1.20 -> 1.37 ms with the pool).
-    // Chain pairs with more block columns: their 12 critical tasks per column and matrix are SHORT (quadrants that follow their
-    // inputs) and numerous -- behind the long bulk solves of one list they start late: a pool of 48 (one matrix) / 96 workgroups
-    // (n = 4096 x 1: 1.361 -> 1.330 ms, x 2: 2.022 -> 1.861; 1536 x 4: 0.588 -> 0.545, x 8: 0.666 -> 0.578, x 9: 0.847 -> 0.651)
-    // One chain workgroup per matrix, re-measured at the end of round 4: the pool only pays from ~40 matrices on (975 x 50: 0.743 ->
-    // 0.725 ms, 896 x 48: 0.543 -> 0.527); below, the single list is 2-5 % faster now (1024 x 32: 0.528 -> 0.518, x 24: 0.518 ->
-    // 0.493, 1152 x 24: 0.580 -> 0.555, 975 x 25: 0.525 -> 0.508)
-    const int auto_crit = nblk <= 10 ? ((a.pair || B > 32) ? std::min((a.psplit + 1 + a.dsplit + (a.psplit == 4 ? 4 : 0)) * B, tile_wgs / 2) : 0)
-                                     : (a.pair && a.psplit == 4 ? std::min(B == 1 ? 48 : 96, tile_wgs / 2) : 0);
-    a.ncrit = auto_crit;
-    // (at least one workgroup is left for the bulk list whenever it has tasks: critical tasks spin-wait on bulk solves of the
-    // previous column)
-    if (a.ncrit > tile_wgs - 1) a.ncrit = std::max(0, tile_wgs - 1);
-  }
-  // build_gram: the caller has NOT built the Gram matrices (plain LML batch: unwarped inputs, c->dh, diagonal additions).  With one
-  // chain workgroup per matrix, one ticket list and the default kernel form the tile workers generate them block by block at the
-  // head of that list -- the chain starts on block (0, 0) ~10 us into the launch instead of behind a whole Gram kernel and a kernel
-  // boundary (n = 1024 x 32: 63 + ~15 us) -- else the Gram kernel goes in front as before.  BGP_PS_GEN = 0 / 1 fixes it.
-  a.gen = 0;
-  if (build_gram) {
-    static int want = -2;
-    if (want == -2) {
-      const char* e = getenv("BGP_PS_GEN");
-      want = e ? (atoi(e) != 0 ? 1 : 0) : -1;
-    }
-    const bool can = !a.pair && a.ncrit == 0 && a.total > 0 && c->ks.stationary == BGP_MATERN52 && c->ks.form == BGP_FORM_PRODUCT;
-    if (can && (want == 1 || (want == -1 && bgp_ps_gen_auto_rule(nblk, B)))) {
-      a.gen = 1;
-      a.total = bgp_ps_total_tasks(B, nblk, a.psplit, 1);
-    } else {
-      const int rck = bgp_launch_kbuild(c, B, 0, 0, 1);
-      if (rck) return rck;
-    }
-  }
+  a.total = plan.total;
+  a.ncrit = plan.ncrit;
+  a.pair = plan.pair;
+  a.Bpad = plan.Bpad;
+  a.nchain = plan.nchain;
+  a.psplit = plan.psplit;
+  a.dsplit = plan.dsplit;
+  a.ncrit_stream = plan.ncrit_stream;
+  a.gen = plan.ps_gen;
   a.d = c->d;
   a.X = c->dXeff;
   a.alpha = c->dalpha;
   a.H = c->dh;
   a.y = c->dy;
-  tile_wgs = std::min(a.total, ncu - a.nchain);  // (gen adds tasks)
-  a.spin_limit = limit;
+  a.spin_limit = bgp_switch_ps_spin_limit();
   a.trace = nullptr;
-  {
-    static int want = -1;
-    if (want < 0) {
-      const char* e = getenv("BGP_PS_TRACE");
-      want = (e && atoi(e) != 0) ? 1 : 0;
-    }
-    if (want) {
-      const size_t need = (size_t)B * nblk * 8 + (size_t)a.total * 8;
-      const int rct = c->ps_trace.ensure(need);
-      if (rct) return rct;
-      BGP_HIP(hipMemsetAsync(c->ps_trace, 0, need * sizeof(unsigned long long), c->stream));
-      a.trace = c->ps_trace;
-      c->ps_trace_B = B;
-      c->ps_trace_nblk = nblk;
-      c->ps_trace_total = a.total;
-    }
+  if (bgp_switch_ps_trace()) {
+    const size_t need = (size_t)B * nblk * 8 + (size_t)a.total * 8;
+    BGP_TRY(c->ps_trace.ensure(need));
+    BGP_HIP(hipMemsetAsync(c->ps_trace, 0, need * sizeof(unsigned long long), c->stream));
+    a.trace = c->ps_trace;
+    c->ps_trace_B = B;
+    c->ps_trace_nblk = nblk;
+    c->ps_trace_total = a.total;
   }
-  bgp_launch_ps(c->stream, a, a.nchain + tile_wgs);
+  bgp_launch_ps(c->stream, a, plan.nchain + plan.tile_wgs);
   if (!c->ps_resident)
     BGP_HIP(hipMemcpyAsync(c->ps_herr, c->ps_flags + PS_ERROR, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
   BGP_HIP(hipGetLastError());
@@ -494,98 +413,76 @@ int bgp_launch_lml_small(bgp_ctx* ctx, int off, int B, hipStream_t st) {
 void bgp_launch_syrk4_gen(hipStream_t st, int B8, double* dK, const int* dstatus, int ld, size_t mstride, int nblk, int kp,
                           int K, int jstart, int colmode, int B, const S4Gen& gen, int stationary, int form);
 
-int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented) {
-  ctx->panel_groups = 1;
-  return bgp_launch_cholesky_slice(ctx, 0, B, ctx->stream, augmented);
-}
-
-// gen != 0 (LML path): only block column 0 of the kernel matrices has been built (bgp_launch_kbuild_x, full_square = 2); the
-// updates of the first panel group generate every other block as they touch it first.
-int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int augmented, int gen) {
-  // augmented == 0: LML only (matrices npad x npad).  augmented != 0: posterior build on the
-  // (2 npad) x (2 npad) augmented matrices [[K, .], [I, 0]] (see bgp_rowblk).
-  const int nblk = ctx->nblk, npad = ctx->npad;
-  const int ld = augmented ? 2 * npad : npad;
+// Walker group g of a plan on the launch schedule (LML only: matrices npad x npad): the list of launches is the planner's
+// (bgp_lml_schedule, bgp_plan.h); here are the buffers of the group's slice, the launches, their timing brackets and the counters.
+int bgp_launch_lml_group(bgp_ctx* ctx, const BgpLmlPlan& plan, int g, hipStream_t st) {
+  const int nblk = ctx->nblk, ld = ctx->npad, off = g * plan.gsz, B = plan.group_nb(g);
   const size_t mstride = (size_t)ld * ld;
   const int ystride = ld;
   const int B8 = 8 * ((B + 7) / 8);
   double* dK = ctx->dK + (size_t)off * mstride;
   double* dW = ctx->dW + (size_t)off * nblk * (128 * 128);
   double* dyw = ctx->dyw + (size_t)off * ystride;
+  double* dzf = ctx->dzf + (size_t)off * ystride;  // z_k of the fused block columns (panel_kernel)
   double* dacc = ctx->dacc + (size_t)off * 4;
   double* dlml = ctx->dlml + off;
   int* dstatus = ctx->dstatus + off;
-  if (!augmented) {
-    // LML path: multi-panel trailing updates.  A group
-    // of P block columns is factorised with look-ahead column updates only, then everything to its right is
-    // updated ONCE with the whole K = 128 P panel (P times fewer passes over the trailing matrix):
-    //   potrf(k) trsm(k) | col k+1 (K=128) | potrf(k+1) trsm(k+1) | col k+2 (K=256) | ... | rest (K = 128 P)
-    // P block columns per trailing update: 4 from n = 1536 upwards (config C: 16.5 vs 17.1 ms per step against P = 2
-    // with the LDS-DMA kernels, whose look-ahead column launches are cheap enough), 2 below (P = 2, 3, 4 are equal
-    // within noise at n = 1024); BGP_PANELS fixes it.
-    const int P = ctx->panels_auto ? (nblk >= 12 ? 4 : 2) : ctx->panels;
-    double* dzf = ctx->dzf + (size_t)off * ystride;  // z_k of the fused block columns (panel_kernel)
-    if (ctx->fused_col.size() < (size_t)ctx->max_batch * nblk) ctx->fused_col.resize((size_t)ctx->max_batch * nblk, 0);
-    S4Gen ga{};
-    if (gen) {
-      const int rcg = bgp_lml_gen_args(ctx, off, &ga);
-      if (rcg) return rcg;
-      ctx->gen_batches++;
-    }
-    int k = 0;
-    while (k < nblk) {
-      const int np = std::min(P, nblk - k);
-      for (int j = 0; j < np; j++) {
-        const int nrb = nblk - (k + j) - 1;
-        const bool fuse = nrb > 0 && (ctx->panel_fused == 1 ||
-                                      (ctx->panel_fused == -1 && bgp_panel_fused_rule(nrb, B, ctx->ncu / std::max(1, ctx->panel_groups))));
-        for (int bb = 0; bb < B; bb++) ctx->fused_col[(size_t)(off + bb) * nblk + k + j] = fuse ? 1 : 0;
-        if (fuse) {
-          // diagonal block and panel solve in one launch (panel_kernel); timed as the panel phase under "trsm"
-          const int S = bgp_panel_fused_wgs(nrb, B, ctx->ncu / std::max(1, ctx->panel_groups));
-          bgp_tbegin(ctx, 2, st);
-          hipLaunchKernelGGL(panel_kernel, dim3(S * B8), dim3(PF_THREADS), 0, st, dK, dW, dyw, dzf, dacc, dlml, dstatus, ctx->n, ld,
-                             mstride, ystride, nblk, k + j, B, B8, S);
-          bgp_tend(ctx, st);
-          ctx->fused_launches++;
-        } else {
-          bgp_tbegin(ctx, 1, st);
-          hipLaunchKernelGGL((potrf_kernel<0, 0, 0>), dim3(B), dim3(PF_THREADS), 0, st, dK, dW, dyw, dacc, dlml, dstatus,
-                             ctx->n, ld, mstride, ystride, nblk, k + j, PfGen());
-          bgp_tend(ctx, st);
-          if (k + j + 1 >= nblk) break;
-          bgp_tbegin(ctx, 2, st);
-          bgp_launch_trsm4(st, B, dK, dW, dyw, dstatus, ld, mstride, ystride, nblk, k + j, 0);
-          bgp_tend(ctx, st);
-        }
-        if (j + 1 < np) {  // look-ahead: block column k+j+1 with the panels k .. k+j
-          bgp_tbegin(ctx, 5, st);
-          if (gen && k == 0) {
-            bgp_launch_syrk4_gen(st, B8, dK, dstatus, ld, mstride, nblk, k, 128 * (j + 1), k + j + 1, 1, B, ga, ctx->ks.stationary,
-                                 ctx->ks.form);
-            ctx->gen_launches++;
-          } else
-            bgp_launch_syrk4(st, B8, dK, dstatus, ld, mstride, nblk, k, 128 * (j + 1), k + j + 1, 1, B);
-          bgp_tend(ctx, st);
-        }
-      }
-      const int nt = nblk - (k + np);
-      if (nt > 0) {
-        bgp_tbegin(ctx, 3, st);
-        if (gen && k == 0) {
-          bgp_launch_syrk4_gen(st, B8, dK, dstatus, ld, mstride, nblk, k, 128 * np, k + np, 0, B, ga, ctx->ks.stationary, ctx->ks.form);
-          ctx->gen_launches++;
-        } else
-          bgp_launch_syrk4(st, B8, dK, dstatus, ld, mstride, nblk, k, 128 * np, k + np, 0, B);
-        bgp_tend(ctx, st);
-      }
-      k += np;
-    }
-    BGP_HIP(hipGetLastError());
-    return BGP_OK;
+  if (ctx->fused_col.size() < (size_t)ctx->max_batch * nblk) ctx->fused_col.resize((size_t)ctx->max_batch * nblk, 0);
+  S4Gen ga{};
+  if (plan.gen(g)) {
+    BGP_TRY(bgp_lml_gen_args(ctx, off, &ga));
+    ctx->gen_batches++;
   }
-  // posterior build: nblk steps on the augmented matrix, the ring kernels in single-panel mode with the active-row
-  // remap of bgp_rowblk (nblk active row blocks at every step)
+  // the update of block columns j .. with the panels kp .. (K = their width); colmode 1: block column j alone
+  auto update = [&](const BgpStep& s, int colmode) {
+    if (s.gen) {
+      bgp_launch_syrk4_gen(st, B8, dK, dstatus, ld, mstride, nblk, s.k, s.K, s.j, colmode, B, ga, ctx->ks.stationary, ctx->ks.form);
+      ctx->gen_launches++;
+    } else
+      bgp_launch_syrk4(st, B8, dK, dstatus, ld, mstride, nblk, s.k, s.K, s.j, colmode, B);
+  };
+  bgp_lml_schedule(plan, g, [&](const BgpStep& s) {
+    if (s.kind == BGP_STEP_PANEL || s.kind == BGP_STEP_POTRF)
+      for (int bb = 0; bb < B; bb++) ctx->fused_col[(size_t)(off + bb) * nblk + s.k] = s.kind == BGP_STEP_PANEL;
+    switch (s.kind) {
+      case BGP_STEP_PANEL:  // (timed as the panel phase under "trsm")
+        bgp_tbegin(ctx, 2, st);
+        hipLaunchKernelGGL(panel_kernel, dim3(s.S * B8), dim3(PF_THREADS), 0, st, dK, dW, dyw, dzf, dacc, dlml, dstatus, ctx->n, ld,
+                           mstride, ystride, nblk, s.k, B, B8, s.S);
+        ctx->fused_launches++;
+        break;
+      case BGP_STEP_POTRF:
+        bgp_tbegin(ctx, 1, st);
+        hipLaunchKernelGGL((potrf_kernel<0, 0, 0>), dim3(B), dim3(PF_THREADS), 0, st, dK, dW, dyw, dacc, dlml, dstatus, ctx->n, ld,
+                           mstride, ystride, nblk, s.k, PfGen());
+        break;
+      case BGP_STEP_TRSM:
+        bgp_tbegin(ctx, 2, st);
+        bgp_launch_trsm4(st, B, dK, dW, dyw, dstatus, ld, mstride, ystride, nblk, s.k, 0);
+        break;
+      case BGP_STEP_COLUMN:
+        bgp_tbegin(ctx, 5, st);
+        update(s, 1);
+        break;
+      case BGP_STEP_UPDATE:
+        bgp_tbegin(ctx, 3, st);
+        update(s, 0);
+        break;
+    }
+    bgp_tend(ctx, st);
+  });
+  BGP_HIP(hipGetLastError());
+  return BGP_OK;
+}
+
+// Posterior build: nblk steps on the (2 npad) x (2 npad) augmented matrices [[K, .], [I, 0]], the ring kernels in single-panel
+// mode with the active-row remap of bgp_rowblk (nblk active row blocks at every step).  Nothing to decide: no plan.
+static int launch_cholesky_augmented(bgp_ctx* ctx, int B) {
+  const int nblk = ctx->nblk, ld = 2 * ctx->npad, ystride = ld, B8 = 8 * ((B + 7) / 8);
+  const size_t mstride = (size_t)ld * ld;
+  hipStream_t st = ctx->stream;
+  double *dK = ctx->dK, *dW = ctx->dW, *dyw = ctx->dyw, *dacc = ctx->dacc, *dlml = ctx->dlml;
+  int* dstatus = ctx->dstatus;
   std::fill(ctx->fused_col.begin(), ctx->fused_col.end(), 0);
   for (int k = 0; k < nblk; k++) {
     bgp_tbegin(ctx, 1, st);
@@ -601,4 +498,10 @@ int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int 
   }
   BGP_HIP(hipGetLastError());
   return BGP_OK;
+}
+
+// B matrices that are in the workspace already (host Gram matrices; augmented: a posterior build), by launches on the context's stream
+int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented) {
+  if (augmented) return launch_cholesky_augmented(ctx, B);
+  return bgp_launch_lml_group(ctx, bgp_plan_lml(bgp_lml_shape(ctx, B, 0, 1)), 0, ctx->stream);
 }

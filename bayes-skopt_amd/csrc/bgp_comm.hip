@@ -112,7 +112,7 @@ struct bgp_comm {
 static double comm_timeout_s() {
   static double v = 0.0;
   if (v == 0.0) {
-    const char* e = getenv("BGP_COMM_TIMEOUT_S");
+    const char* e = bgp_switch(BGP_SW_COMM_TIMEOUT_S);
     v = (e && atof(e) > 0.0) ? atof(e) : 300.0;
   }
   return v;

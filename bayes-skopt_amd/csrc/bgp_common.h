@@ -13,6 +13,7 @@
 
 #include "../../include/bgp.h"
 #include "bgp_mem.h"
+#include "bgp_plan.h"
 
 #define BGP_NB 128          // block size of the right-looking Cholesky == tile edge
 #define BGP_TILE_LD 129     // LDS leading dimension of a 128x128 tile (odd -> conflict-free columns)
@@ -213,7 +214,6 @@ struct bgp_ctx {
   // launch schedule, LML path: diagonal block + panel solve of a block column in one launch (panel_kernel, bgp_chol.hip)
   // (0 here: a context made without bgp_ctx_create -- the covariance workspace of sample_y -- is READ in place and never fuses)
   int panel_fused = 0;          // bgp_ctx_create, env BGP_PANEL_FUSED: 0 never, 1 every block column that has a solve, -1 (unset) bgp_panel_fused_rule
-  int panel_groups = 1;         // walker-group streams that factorise side by side: a launch takes its share of the CUs (bgp_lml_enqueue_dev)
   long long fused_launches = 0; // panel_kernel launches enqueued by this context (bgp_panel_fused_stats)
   BgpDev<double> dzf;           // max_batch * npad: z_k of the fused block columns (segment k of dyw keeps y_k there)
   std::vector<unsigned char> fused_col;  // [slot * nblk + k] = 1: the last factorisation of the slot left L_kk in dW and z_k in dzf
@@ -323,60 +323,7 @@ struct PsArgs {
 };
 //   genrdy[(b * nblk + I) * nblk + J]   gen = 1: block (I, J) of matrix b has been generated (behind s2rdy)
 #define PS_GEN(B, nblk) (PS_HDR + (size_t)(B) * (nblk) * (8 + (nblk)))
-// Shapes at which the tile workers generate the Gram blocks inside the launch-free kernel (PsArgs::gen) instead of a Gram kernel in
-// front of it: where the chain is the bound and the tile side has the slack to take the extra work (measured: bgp_chol.hip)
-// (tools/gen_probe.py, ms per LML call without -> with: 1024 x 24 0.488 -> 0.464, x 16 0.476 -> 0.456, x 8 0.460 -> 0.449; 768 x 32
-// 0.383 -> 0.362; 1536 x 16 0.729 -> 0.719; 2048 x 8 0.927 -> 0.884; 512 x 32 0.260 -> 0.250; but 1024 x 32 0.522 -> 0.527, 2048 x 16
-// 1.308 -> 1.357 and 3072 x 8 1.921 -> 1.936: there the tile side is the bound already and the blocks are extra work for it)
-static inline bool bgp_ps_gen_auto_rule(int nblk, int B) { return nblk >= 4 && nblk <= 16 && B <= 32 && B * nblk <= 192; }
-// Block columns of the launch schedule's LML path that take ONE fused launch (panel_kernel, bgp_chol.hip) instead of potrf_kernel +
-// trsm4_kernel: nrb = row blocks under the diagonal block, B = matrices of the launch, ncu = the CUs the launch can count on (the
-// device's, divided by the walker-group streams that factorise side by side).  bgp_panel_fused_wgs = workgroups per matrix, S.
-// Measured per block column (config C: n = 2048 x 128 matrices, S = 2, one stream, rocprofv3 kernel trace, us, potrf + trsm4 -> fused):
-//   nrb = 15: 31.8 + 130.7 -> 129.4   14: 31.0 + 113.9 -> 116.3   13: 30.6 + 105.9 -> 114.4   12: 30.8 + 100.5 -> 104.4
-//   11: 31.9 + 92.5 -> 107.3   10: 31.7 + 84.1 -> 98.5   9: 31.2 + 72.6 -> 95.2   8: 30.8 + 65.4 -> 84.0   7: 31.1 + 60.4 -> 83.1
-//   6: 30.9 + 47.6 -> 70.6   5: 31.1 + 44.5 -> 71.8   4: 31.2 + 37.5 -> 59.6   3: 31.0 + 27.9 -> 57.7   2: 31.0 + 18.2 -> 46.7
-//   but nrb = 1: 30.8 + 12.3 -> 44.6 (one row block: 13 us behind the diagonal block's 31 either way, and the separate solve splits
-//   it over two workgroups per matrix).  A fused launch costs the diagonal block plus ~12.3 us per row block of its busiest
-//   workgroup: 1.481 -> 1.284 ms per half-step over the fifteen columns.
-// So: at least two row blocks and at least two workgroups per matrix.  (One workgroup per matrix -- more than ncu / 2 matrices --
-// leaves the solve to as many CUs as there are matrices, one row block after the other: ahead in two whole-call probes (1536 x 200:
-// 5.48 -> 5.36 ms, 640 x 256: 0.89 -> 0.85), no per-column table yet: not taken.  docs/EXPERIMENTS.md G29.)
-static inline int bgp_panel_fused_wgs(int nrb, int B, int ncu) {
-  const int B8 = 8 * ((B + 7) / 8), s = ncu / B8;
-  return s < 1 ? 1 : (s > nrb ? (nrb < 1 ? 1 : nrb) : s);
-}
-static inline bool bgp_panel_fused_rule(int nrb, int B, int ncu) { return nrb >= 2 && bgp_panel_fused_wgs(nrb, B, ncu) >= 2; }
 static inline size_t ps_flag_words(int B, int nblk) { return PS_HDR + (size_t)B * nblk * (8 + 2 * (size_t)nblk); }
-// Batch sizes at which the launch-free factorisation wins over the multi-launch schedule (tools/persist_probe.py on MI355X,
-// DESIGN.md section 4; wall time per LML call, launch schedule / launch-free, by n and number of matrices):
-//   n =  768: 8: 0.91, 32: 1.07;   896: 16: 1.02, 48: 1.11
-//   n = 1024: 1: 0.93, 4: 0.95, 8: 0.98, 16: 1.06, 24: 1.12, 32: 1.19, 48: 1.09, 64: 0.97;  975 x 50 (config E): 1.10
-//   n = 1280: 8: 1.04, 32: 1.15, 48: 0.96;   1536: 1: 1.01, 4: 1.06, 16: 1.29, 32: 1.06, 48: 0.92
-//   n = 2048: 1: 1.02, 4: 1.12, 9: 1.40, 16: 1.22, 24: 1.07, 32: 0.99, 48: 0.88;   3072: 1: 1.08, 8: 1.25, 16: 1.06, 24: 0.95
-//   n = 4096: 1: 1.15, 2: 1.12, 4: 1.08, 8: 1.13, 16: 0.98;  one 10 112 x 10 112 covariance (sample_y): 1.15;  n <= 640: 0.92-0.97
-// So: at least 6 block columns, matrices x block columns <= 400 (beyond that the tile side is the bound and the launch
-// schedule's kernels are the better tile workers), and >= 100 unless there are at least 12 block columns.
-// Chain PAIRS (two chain workgroups per matrix that alternate over the block columns; the critical pre-updates in quadrants that
-// follow the chain's and the streamed solves' blocks column block by column block, on a critical pool of their own: bgp_pf.h,
-// bgp_chol.hip) win where the chain is the bound -- few matrices.  Wall ms per LML call, best of {launches, launch-free} ->
-// pairs (tools/persist_probe.py, MI355X, round 4):
-//   n =  384 x 1: 0.173 -> 0.159;   512 x 1 / 4 / 8: 0.220 / 0.225 / 0.223 -> 0.197 / 0.203 / 0.218;   768 x 1 / 16: 0.318 / 0.356 -> 0.271 / 0.317
-//   n = 1024 x 1 / 8 / 16 (32: 0.528 -> 0.630): 0.413 / 0.447 / 0.475 -> 0.349 / 0.414 / 0.430;   1280 x 12: 0.601 -> 0.554;   1152 x 14: 0.543 -> 0.500
-//   n = 1408 x 9 / 12 (16: 0.663 -> 0.671): 0.639 / 0.652 -> 0.611 / 0.624;   1536 x 1 / 4 / 8 / 9 / 12 (16: 0.763 -> 0.789): 0.650 / 0.664 / 0.675 / 0.712 / 0.729 -> 0.506 / 0.546 / 0.579 / 0.659 / 0.722
-//   n = 1792 x 4 / 8 (12: 0.919 -> 0.953): 0.765 / 0.789 -> 0.623 / 0.662;   2048 x 1 / 2 / 4 / 8 (12: 1.207 -> 1.284, 16: 1.305 -> 1.503): 0.861 / 0.865 / 0.889 / 0.925 -> 0.653 / 0.673 / 0.746 / 0.839
-//   n = 2560 x 4 / 6 (8: 1.275 -> 1.381): 1.154 / 1.234 -> 1.081 / 1.230;   3072 x 1 / 2 / 3 / 4 (6: 1.798 -> 1.908): 1.326 / 1.341 / 1.473 / 1.639 -> 1.023 / 1.195 / 1.399 / 1.609
-//   n = 3584 x 2 / 3 (4: 2.191 -> 2.179): 1.636 / 1.904 -> 1.504 / 1.817;   4096 x 1 / 2 / 3 (4: 2.831 -> 2.969): 1.730 / 2.112 / 2.472 -> 1.327 / 1.862 / 2.398
-//   n = 4992 x 1 / 5120 x 1 (x 2: 2.906 -> 2.893) / 6144 x 1: 2.113 / 2.190 / 2.629 -> 1.601 / 1.641 / 2.326;   not 7168 x 1 (3.195 -> 3.189), 8192 x 1 (4.201 -> 4.406), 10 112 x 1
-static inline bool bgp_pair_auto_rule(int nblk, int nb) {
-  if (nblk < 3) return false;
-  if (nblk <= 10) return nb <= 16 && nb * nblk * nblk <= 1200;
-  if (nblk <= 12) return nb <= 12;
-  return nb <= 8 && nb * nblk * nblk <= (nb <= 3 ? 3100 : 2400);  // (the tile side's work goes with matrices x block columns^2)
-}
-static inline bool bgp_persist_auto_rule(int nblk, int nb) {
-  return bgp_pair_auto_rule(nblk, nb) || (nblk >= 6 && nb * nblk <= 400 && (nblk >= 12 || nb * nblk >= 100));
-}
 // A launch-free call timed out (a wait outlasted BGP_PS_TIMEOUT_MS: its workgroups were not co-resident -- another context,
 // process or RCCL kernel held CUs -- or the device was oversubscribed).  One transient event must not cost the context
 // the path for life: the next BGP_PS_COOLDOWN eligible calls go by launches, then the launch-free path is tried again;
@@ -406,7 +353,30 @@ static inline bool bgp_ps_allowed(bgp_ctx* c) {
   if (c->ps_cooldown > 0 && --c->ps_cooldown == 0) c->ps_disabled = 0;
   return false;
 }
-int bgp_launch_cholesky_persist(bgp_ctx* ctx, int B, int build_gram);
+static_assert(BGP_PLAN_MATERN52 == BGP_MATERN52 && BGP_PLAN_FORM_PRODUCT == BGP_FORM_PRODUCT, "bgp_plan.h restates include/bgp.h");
+// What the planner (bgp_plan.h) reads of a context: nb matrices of w's shape under w's modes and the live switches.
+static inline BgpLmlShape bgp_lml_shape(const bgp_ctx* w, int nb, int warped, int given) {
+  BgpLmlShape s{};
+  s.n = w->n, s.nblk = w->nblk, s.d = w->d, s.stationary = w->ks.stationary, s.form = w->ks.form, s.ncu = w->ncu, s.nb = nb;
+  s.warped = warped != 0, s.given = given != 0;
+  s.timing = w->timing, s.persist = w->persist, s.panel_fused = w->panel_fused;
+  s.panels = w->panels, s.panels_auto = w->panels_auto, s.nstreams = w->nstreams, s.streams_auto = w->streams_auto;
+  bgp_shape_read_call_switches(s);
+  return s;
+}
+// The plan of a batch that is about to be enqueued.  `permitted`: the caller does not rule the launch-free path out; the planner
+// says whether the batch is eligible otherwise, the cool-down of `c` -- asked, and counted, for eligible batches only -- has the last
+// word, and a launch-free call is counted on `c`.
+static inline BgpLmlPlan bgp_plan_for(bgp_ctx* c, BgpLmlShape s, bool permitted) {
+  s.ps_permitted = permitted;  // (for the planner's answer "eligible but for the cool-down")
+  s.ps_permitted = bgp_plan_wants_launch_free(s) && bgp_ps_allowed(c);
+  if (s.ps_permitted) {
+    c->ps_calls++;
+    bgp_shape_read_ps_switches(s);
+  }
+  return bgp_plan_lml(s);
+}
+int bgp_launch_cholesky_persist(bgp_ctx* ctx, const BgpLmlPlan& plan);
 int bgp_lml_redo_if_abandoned(bgp_ctx* ctx, int B);
 int bgp_lml_enqueue_dev(bgp_ctx* ctx, int nb, int warped);  // bgp_api.hip: Gram build + factorisation + LML of c->dh[0 .. nb), on the device only
 int bgp_ensure_warp_buffers(bgp_ctx* ctx);                  // bgp_api.hip: the per-walker warp buffers of a warped LML batch exist
@@ -418,7 +388,6 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
   c->ps_inflight = 0;
   if (c->ps_herr) *c->ps_herr = 0;
 }
-int bgp_persist_fits(bgp_ctx* ctx, int B);
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
@@ -550,12 +519,12 @@ int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented);
 int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows);
 // n <= 128: K-build + factorisation + LML of the slice [off, off+B) in ONE launch (bgp_chol.hip, potrf_kernel<1,..>)
 int bgp_launch_lml_small(bgp_ctx* ctx, int off, int B, hipStream_t st);
-int bgp_launch_cholesky_slice(bgp_ctx* ctx, int off, int B, hipStream_t st, int augmented, int gen = 0);
+// walker group g of a plan on the launch schedule, on stream st (bgp_chol.hip; the Gram build of the group is in front of it)
+int bgp_launch_lml_group(bgp_ctx* ctx, const BgpLmlPlan& plan, int g, hipStream_t st);
 struct S4Gen {           // what the trailing update's Gram generator reads (S4GenF, bgp_s4.h)
   const double* Xs;     // scaled inputs, k-major: dpad x npad doubles per matrix slot
   const double* H;      // canonical hyper-parameters, d + 2 per matrix
   const double* alpha;  // per-point jitter added to the diagonal (nullable)
   int n, d, dpad, npad;
 };
-int bgp_lml_gen_eligible(const bgp_ctx* ctx, int B);
 int bgp_lml_gen_args(const bgp_ctx* ctx, int off, S4Gen* out);

@@ -265,18 +265,9 @@ int bgp_launch_kbuild_x(bgp_ctx* ctx, int off, int B, hipStream_t st, int full_s
   return BGP_OK;
 }
 
-// Gram generation inside the trailing update (bgp_launch_cholesky_slice's `gen`): where the pipelined build would run anyway
-// (the same threshold), on matrices of at least two block columns with at most 16 input dimensions (one staging pass; at d = 32
-// the generator measured +1.2 % / -0.1 % at n = 4096 x 8 / 16 matrices, against -2 .. -4.5 % at d <= 16 from 32 matrices on:
-// tools/gen_shapes_probe.py); BGP_SYRK_GEN=0 switches it off (A/B measurements).
-int bgp_lml_gen_eligible(const bgp_ctx* ctx, int B) {
-  const char* e = getenv("BGP_SYRK_GEN");  // (read per call: the tests flip it inside one process)
-  const int on = (e && e[0] == '0') ? 0 : 1;
-  const int B8 = 8 * ((B + 7) / 8);
-  return on && ctx->d <= KB_DK && ctx->nblk >= 2 && B8 * (ctx->nblk * (ctx->nblk + 1) / 2) >= 2048;
-}
-
-// ... and what the generator reads: the scaled inputs of the batch slice at `off` (written by the build of block column 0)
+// What the Gram generator inside the trailing update reads (where it runs is the planner's: BgpLmlPlan::gen, bgp_plan.h): the scaled
+// inputs of the batch slice at `off` (written by the build of block column 0)
+static_assert(BGP_PLAN_GEN_MAX_D == KB_DK, "the planner's bound is one staging pass of the generator");
 int bgp_lml_gen_args(const bgp_ctx* ctx, int off, S4Gen* out) {
   const int dpad = ((ctx->d + KB_DK - 1) / KB_DK) * KB_DK;
   if (!ctx->dXs || (size_t)ctx->max_batch * dpad * ctx->npad > ctx->dXs.cap) {

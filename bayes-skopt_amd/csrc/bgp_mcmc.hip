@@ -345,7 +345,7 @@ extern "C" int bgp_mcmc_begin_ex(bgp_ctx* c, bgp_comm* comm, int nwarp, int W, i
     }
     BGP_HIP(bgp_memcpy_async(const_cast<int*>(a.lml_idx), idx.data(), Ns * sizeof(int), hipMemcpyHostToDevice, st));
   }
-  if (c->nblk > 1 && a.row_n > 0 && bgp_persist_fits(c, a.row_n)) {  // a launch-free call may follow: its flag block is reset by the step kernel
+  if (c->nblk > 1 && a.row_n > 0 && bgp_persist_fits(c->nblk, c->ncu, a.row_n)) {  // a launch-free call may follow: its flag block is reset by the step kernel
     const int rcf = bgp_ps_ensure_flags(c, a.row_n);
     if (rcf) return rcf;
     a.ps_flags = c->ps_flags;

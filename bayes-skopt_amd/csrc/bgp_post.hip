@@ -206,7 +206,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
     for (int b = 0; b < nb; b++)
       BGP_HIP(hipMemsetAsync(c->dK + (size_t)b * ld * ld + (size_t)npad * ld, 0, (size_t)npad * ld * sizeof(double),
                              c->stream));
-    // (no kernel of the augmented factorisation reads c->dXeff: bgp_launch_cholesky_slice generates nothing there)
+    // (no kernel of the augmented factorisation reads c->dXeff: bgp_launch_cholesky generates nothing there)
     rc = Kgram  ? bgp_gram_load(c, nb, Kgram + (size_t)off * n * n, 1, use_alpha)
          : warp ? bgp_launch_kbuild_x(c, 0, nb, c->stream, 0, 1, use_alpha, c->dXwP + (size_t)off * nd, nd)
                 : bgp_launch_kbuild(c, nb, 0, 1, use_alpha);
@@ -1008,7 +1008,7 @@ static int post_child(bgp_ctx* c, int m, int nb, bgp_ctx** out) {
 }
 
 // Cholesky of the child's nb matrices in place (rhs and statuses cleared in front of it), the statuses on their way to the host right
-// behind it.  allow_launch_free: where bgp_lml_enqueue_dev's rule takes the shape, ONE launch-free kernel (a single covariance of 79
+// behind it.  allow_launch_free: where the planner (bgp_plan.h) takes the shape, ONE launch-free kernel (a single covariance of 79
 // block columns at 10 000 candidates is the longest launch chain of a tell: 12.6 -> 10.9 ms per call, same draws) -- then the call waits
 // for it, and should a wait inside it have timed out, `rebuild` restores the matrices, they are factorised by launches, and the context
 // stays on them (bgp_ps_note_timeout).
@@ -1017,14 +1017,14 @@ static int post_factor_child(bgp_ctx* c, bgp_ctx* w, int nb, bool allow_launch_f
   for (;;) {
     BGP_HIP(hipMemsetAsync(w->dyw, 0, (size_t)nb * w->npad * sizeof(double), c->stream));
     BGP_HIP(hipMemsetAsync(w->dstatus, 0, (size_t)nb * sizeof(int), c->stream));
-    // (after a time-out bgp_ps_allowed refuses, and the redo counts as one eligible call of the cool-down)
-    const bool ps = allow_launch_free && bgp_persist_fits(w, nb) &&
-                    (c->persist == 1 || (c->persist == -1 && bgp_persist_auto_rule(w->nblk, nb))) && bgp_ps_allowed(c);
-    if (ps) {
-      c->ps_calls++;
-      w->persist = 1;
-    }
-    BGP_TRY(ps ? bgp_launch_cholesky_persist(w, nb, 0) : bgp_launch_cholesky(w, nb, 0));
+    // the child's shape under the parent's mode; the cool-down and the call count are the parent's (after a time-out bgp_ps_allowed
+    // refuses, and the redo counts as one eligible call of the cool-down)
+    BgpLmlShape shape = bgp_lml_shape(w, nb, 0, 1);
+    shape.persist = c->persist;
+    const BgpLmlPlan plan = bgp_plan_for(c, shape, allow_launch_free);
+    const bool ps = plan.path == BGP_PATH_LAUNCH_FREE;
+    if (ps) w->persist = 1;
+    BGP_TRY(ps ? bgp_launch_cholesky_persist(w, plan) : bgp_launch_lml_group(w, plan, 0, c->stream));
     BGP_HIP(bgp_memcpy_async(status, w->dstatus, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (!ps) return BGP_OK;
     BGP_HIP(bgp_stream_sync(c->stream));

@@ -36,15 +36,7 @@
 // Per C element the operations and their order are those of syrk4_kernel / trsm4_kernel (accumulator = C, MFMA k-steps
 // ascending, A-negate): bit-identical factors.
 // ------------------------------------------------------------------------------------------
-// critical tasks per block column and matrix: S(J+2, J), the np parts of P(J+2) (np = PsArgs::psplit: 2 column slices or 4
-// quadrants), the PS_ND(np) parts of Dg(J+2) and the PS_NQ(np) quadrants Q ahead of S(J+2, J)
-#define PS_ND(np) ((np) == 4 ? 3 : 1)
-#define PS_NQ(np) ((np) == 4 ? 4 : 0)
-static __host__ __device__ __forceinline__ int ps_crit_per_matrix(int nblk, int np) {
-  return nblk > 2 ? (np + 1 + PS_ND(np) + PS_NQ(np)) * (nblk - 2) : 0;
-}
-static __host__ __device__ __forceinline__ int ps_bulk_per_matrix(int nblk) { return nblk > 3 ? (nblk - 3) * (nblk - 2) / 2 : 0; }
-static __host__ __device__ __forceinline__ int ps_tasks_per_matrix(int nblk, int np) { return ps_crit_per_matrix(nblk, np) + ps_bulk_per_matrix(nblk); }
+// (the task counts per matrix -- ps_crit_per_matrix, ps_bulk_per_matrix, ps_tasks_per_matrix, PS_ND, PS_NQ -- are the planner's: bgp_plan.h)
 
 // vmcnt(N) with a compile-time N
 template <int N>
@@ -744,5 +736,4 @@ void bgp_launch_ps(hipStream_t st, const PsArgs& a, int nwg) {
   else
     hipLaunchKernelGGL(ps_kernel<0>, dim3(nwg), dim3(512), 0, st, a);
 }
-int bgp_ps_total_tasks(int B, int nblk, int np, int gen) { return B * (ps_tasks_per_matrix(nblk, np) + (gen ? nblk * (nblk + 1) / 2 : 0)); }
 

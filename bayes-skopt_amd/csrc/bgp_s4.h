@@ -145,7 +145,7 @@ struct S4GenF {
 #pragma unroll
       for (int j = 0; j < NC; j++) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
     const int sk = tid >> 4, sseg = tid & 15;  // staging: dimension sk, rows 4 sseg .. 4 sseg + 3 of both slices
-    {  // (dpad == 16: one pass over the input dimensions -- bgp_lml_gen_eligible)
+    {  // (dpad == 16: one pass over the input dimensions -- BgpLmlPlan::gen, bgp_plan.h)
       {
         const double* src = Xb + (size_t)sk * g.npad;
         const d2 a0 = *reinterpret_cast<const d2*>(src + cur.gi0 + 4 * sseg), a1 = *reinterpret_cast<const d2*>(src + cur.gi0 + 4 * sseg + 2);

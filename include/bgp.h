@@ -385,7 +385,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  * more in round 6); the fused panel launches (bgp_set_panel_fused) take whole CUs, and one group measured faster with them
  * (docs/EXPERIMENTS.md G29).  This call, or the environment variable BGP_STREAMS read at context creation, fixes the count.
  *
- * Environment switches the library reads (a BGP_* variable it does not read is reported once on stderr).  Schedule switches --
+ * Environment switches the library reads (a BGP_* variable it does not read is reported once on stderr; the table of all of
+ * them, with the moment each is read, is bgp_switches in csrc/bgp_plan.h and DESIGN.md section 19).  Schedule switches --
  * each selects between code paths whose results are bit-identical (tests/test_gpu_edge.py, tests/test_gpu_persist.py):
  *   BGP_STREAMS (this call), BGP_PANELS (block columns per trailing update, 1..64; default 4 from n = 1536, else 2), BGP_PERSIST
  *   (bgp_set_persist), BGP_PANEL_FUSED (bgp_set_panel_fused), BGP_PS_PAIR (0 / 1: one or two chain workgroups per matrix on the launch-free path; default by shape),
@@ -419,7 +420,7 @@ int bgp_last_timing_columns(bgp_ctx* ctx, double* ms, int* launches);
  * bgp_sample_y -- instead of ~3 launches per block column; same bits): 1 = whenever the batch fits (<= 64 matrices,
  * n > 128), 0 = never, -1 = as BGP_PERSIST says (unset: where it measured faster on MI355X: at least 6 block columns of
  * 128, matrices x block columns <= 400; and -- with two chain workgroups per matrix -- few matrices from 3 block columns on:
- * bgp_persist_auto_rule / bgp_pair_auto_rule).  Replaces nothing in the reference; a scheduling choice behind cholesky() of
+ * bgp_persist_auto_rule / bgp_pair_auto_rule in csrc/bgp_plan.h).  Replaces nothing in the reference; a scheduling choice behind cholesky() of
  * sklearn/_gpr.py:587. */
 int bgp_set_persist(bgp_ctx* ctx, int mode);
 /* Bookkeeping of that path: out[0] = launch-free calls enqueued by this context, out[1] = of which timed out (a wait
@@ -449,6 +450,38 @@ int bgp_set_timing(bgp_ctx* ctx, int enable);
  * block columns, tile tasks}; out (may be NULL to query dims) receives 8 stamps per (matrix, block column) of the chain
  * role, then 8 per tile task; cap = capacity of out in 64-bit words.  Read by tools/persist_trace.py. */
 int bgp_debug_ps_trace(bgp_ctx* ctx, int* dims, unsigned long long* out, size_t cap);
+/* What the library would launch for one LML batch of nb matrices (one chunk: nb <= max_batch), from the launch planner alone
+ * (csrc/bgp_plan.h; DESIGN.md sections 3, 4 and 19): nothing is enqueued, counted or changed.  With a context, the shape, the
+ * device and the modes are the context's and the query supplies nb and warped; the launch-free path counts as permitted unless a
+ * time-out or an open resident sampler redo keeps it off right now.  With ctx == NULL the query is complete and no device is
+ * touched (a machine without a GPU answers).  Either way the live switches (BGP_SYRK_GEN, BGP_PS_PAIR, BGP_PS_GEN) are the
+ * environment's, read as an LML call reads them. */
+typedef struct bgp_lml_plan_query {
+  int nb, warped;
+  /* ctx == NULL only: */
+  int n, d, stationary, form; /* rows, input dimensions, BGP_RBF .., BGP_FORM_.. */
+  int ncu;                    /* compute units of the device */
+  int timing, persist, panel_fused; /* bgp_set_timing; bgp_set_persist, bgp_set_panel_fused: -1 by shape, 0, 1 */
+  int panels, nstreams;       /* BGP_PANELS, bgp_set_streams; 0: the default */
+  int ps_permitted;           /* no time-out keeps the launch-free path off */
+} bgp_lml_plan_query;
+#define BGP_PLAN_REPORT_COLS 256
+typedef struct bgp_lml_plan_report {
+  int nblk, ncu, fits;  /* block columns of 128, CUs planned for, the batch could take the launch-free path at all */
+  int path;             /* 0: n <= 128, one fused launch; 1: launch-free; 2: launch schedule */
+  /* launch schedule: `share` walker-group streams share the CUs; ngroups groups of gsz matrices (the last: nb_last); P block
+   * columns per trailing update; Gram blocks generated inside the trailing update by the first / the last group / by how many */
+  int share, gsz, ngroups, nb_last, P, gen_first, gen_last, gen_groups;
+  /* launch-free path: PsArgs of csrc/bgp_common.h, the tile workgroups, and whether the Gram kernel goes in front */
+  int pair, Bpad, nchain, psplit, dsplit, ncrit_stream, ncrit, ps_gen, total, tile_wgs, gram_front;
+  /* launches the plan enqueues, by the categories of bgp_last_timing (a fused panel launch under trsm, a look-ahead column
+   * under syrk too), the fused and the generating ones among them, and the launch-free kernel */
+  int kbuild, potrf, trsm, syrk, columns, fused, generating, launch_free;
+  /* launch schedule: workgroups per matrix of the fused launch of block column k in the first / the last group, 0: separate
+   * potrf + trsm launches (the first BGP_PLAN_REPORT_COLS block columns) */
+  int fused_wgs[BGP_PLAN_REPORT_COLS], fused_wgs_last[BGP_PLAN_REPORT_COLS];
+} bgp_lml_plan_report;
+int bgp_debug_lml_plan(bgp_ctx* ctx, const bgp_lml_plan_query* query, bgp_lml_plan_report* report);
 /* Debugging aid: working matrix (npad x npad doubles; L in the lower triangle after an LML call) and working right-hand
  * side (npad doubles, z = L^-1 y) of batch slot b as the last bgp_lml_batch left them; either pointer may be NULL. */
 int bgp_debug_workspace(bgp_ctx* ctx, int b, double* L, double* z);
