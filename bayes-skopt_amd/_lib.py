@@ -119,6 +119,7 @@ SIGNATURES = {
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
+    "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -721,6 +722,28 @@ class Context:
             res.append(out[:, o:o + sz].reshape((B,) + s).copy())
             o += sz
         return res
+
+    # ---- cross-validation from the resident inverses (bgp_cv.hip)
+    def cross_validate(self, B, folds):
+        """``bgp_cross_validate``: the predictive of the held-out observations of every fold (``folds``: index arrays, disjoint,
+        1 .. 128 points each) under the first ``B`` resident posteriors, without a refit.  Returns ``(mean (B, n), var (B, n),
+        fold_lpd (B, K), status (B, K))`` in normalised-target units; mean / var are NaN at points no fold covers, and
+        ``status != 0`` marks a (posterior, fold) whose block of the inverse is not positive definite (its outputs are NaN)."""
+        folds = [np.ascontiguousarray(np.asarray(f).reshape(-1), dtype=np.int32) for f in folds]
+        K = len(folds)
+        ptr = np.zeros(K + 1, dtype=np.int32)
+        if K:
+            ptr[1:] = np.cumsum([len(f) for f in folds])
+        idx = np.ascontiguousarray(np.concatenate(folds) if K else np.zeros(0), dtype=np.int32)
+        if len(idx) == 0:
+            idx = np.zeros(1, dtype=np.int32)  # (a pointer to hand over; the C layer names the fault)
+        B = int(B)
+        mean, var = np.empty((max(B, 0), self.n)), np.empty((max(B, 0), self.n))
+        lpd = np.empty((max(B, 0), K))
+        st = np.zeros((max(B, 0), K), dtype=np.int32)
+        _check(self._lib.bgp_cross_validate(self._h, B, K, _p(ptr), _p(idx), _p(mean), _p(var), _p(lpd), _p(st)),
+               "bgp_cross_validate")
+        return mean, var, lpd, st
 
     # ---- pathwise posterior function draws (bgp_paths_*; DESIGN.md section 14)
     def paths_begin(self, pidx, H_kernel, log_s2, omega, phase, w, eps):

@@ -227,6 +227,26 @@ class CanonicalPosterior:
             H = self.build_rows(gp, thetas)
         return gp._ctx.partial_dependence(H, Xs, grids, panels), "device"
 
+    def cross_validate(self, gp, thetas, folds, warps=None):
+        """(mean (B, n), var (B, n), fold_lpd (B, K), status (B, K)) of the held-out observations, normalised-target units
+        (``bgp_cross_validate``).  ``thetas=None``: the resident median GP; a block of chain rows (``warps``
+        (B, 2d): every row with its own input warp): the batched build, ``max_batch`` rows at a time, each followed by ONE device
+        call over its rows."""
+        if thetas is None:
+            self.make_resident(gp)
+            return gp._ctx.cross_validate(1, folds)
+        thetas = np.atleast_2d(thetas)
+        parts, step = [], max(1, int(gp._ctx.max_batch))
+        for lo in range(0, len(thetas), step):
+            T = thetas[lo : lo + step]
+            if warps is None:
+                self.build_rows(gp, T)
+            else:
+                res = gp._ctx.posterior(gp._canonical(T), want_alpha=False, warps=np.ascontiguousarray(warps[lo : lo + step]))
+                raise_if_not_pd(res["status"], gp.kernel_)
+            parts.append(gp._ctx.cross_validate(len(T), folds))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
     def pvrs(self, gp, X, T, has_alpha_vec):
         Hk = gp._canonical(gp._kernel_theta_for_predict())
         raise_if_not_pd(gp._ctx.pvrs_prepare(Hk, has_alpha_vec))
@@ -316,6 +336,22 @@ class GramPosterior:
 
     def partial_dependence(self, gp, thetas, Xs, grids, panels):
         return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, "generic kernel tree"), "host"
+
+    def cross_validate(self, gp, thetas, folds, warps=None):
+        """As ``CanonicalPosterior.cross_validate``: the device call reads the resident inverses alone, so host kernel matrices
+        serve it as they are.  Chain rows: their matrices ``max_batch`` at a time (under ``warp_inputs`` the caller installs one
+        row's warp after the other and passes one row)."""
+        if thetas is None:
+            self.make_resident(gp)
+            return gp._ctx.cross_validate(1, folds)
+        thetas = np.atleast_2d(thetas)
+        Xt = gp.X_train_
+        parts, step = [], max(1, int(gp._ctx.max_batch))
+        for lo in range(0, len(thetas), step):
+            T = thetas[lo : lo + step]
+            raise_if_not_pd(self._posterior_gram(gp, gp._gram_stack(T, Xt), want_alpha=False)["status"], gp.kernel_)
+            parts.append(gp._ctx.cross_validate(len(T), folds))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
 
     def pvrs(self, gp, X, T, has_alpha_vec):
         """PVRS through the bordered-inverse identity of ``bgp_pvrs``,

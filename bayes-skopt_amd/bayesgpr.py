@@ -27,6 +27,7 @@ from sklearn.utils import check_random_state
 
 from . import _lib, distributed
 from ._posterior import CanonicalPosterior, GramPosterior, noise_off, raise_if_not_pd
+from .crossval import check_folds, combine_rows, split_folds
 from .kernels import ConstantKernel, WhiteKernel, analyse_kernel, param_for_white_kernel_in_sum
 from .kernels import RBF as _RBF
 from .sampler import EnsembleSampler
@@ -738,6 +739,66 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         if thetas is None:
             vals = [v[0] for v in vals]
         return (vals, path) if return_path else vals
+
+    def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
+        """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the
+        held-out OBSERVATIONS ``y_F`` given the remaining points -- without a refit: it follows from the resident ``K^-1`` and
+        ``alpha`` alone (``bgp_cross_validate``), so canonical kernels, generic kernel trees and warped
+        inputs are served alike.  The hyper-parameters stay those fitted on ALL points.  The predictive is that of the
+        observation: its std includes the white level and the point's own ``alpha`` (``noise_vector``), which ``predict``'s
+        std does not.
+
+        ``folds``: a list of disjoint index arrays (1 .. 128 points each; they need not cover every point); ``n_folds=K``: a
+        shuffled split into K near-equal folds seeded by ``random_state``; neither: leave-one-out.  ``thetas=None``: the median
+        GP, as ``predict`` uses it; a (B, p) block of chain rows (under ``warp_inputs`` the rows carry their warps, as
+        ``chain_`` holds them): every row's predictive, built ``max_batch`` rows at a time, and their combination --
+        ``weights="is"``: rows weighted per fold by ``1 / p(y_F | y_-F, theta_b)``, the importance weights that carry the
+        hyper-posterior from ``p(theta | y)`` to ``p(theta | y_-F)`` (``fold_lpd = -log mean_b exp(-lpd_bF)``); ``"equal"``:
+        the plug-in mixture (``fold_lpd = log mean_b exp(lpd_bF)``).  With one row both coincide.
+
+        Returns a dict, everything in y units: ``folds``; ``row_mean``, ``row_std`` (B, n) and ``row_fold_lpd`` (B, K) per row;
+        the combined ``mean``, ``std``, ``point_lpd``, ``z = (y - mean) / std`` (n,; NaN where no fold covers the point),
+        ``fold_lpd`` (K,; log density of the whole fold, correlations included), ``elpd = sum(fold_lpd)`` and the effective
+        number of rows ``ess`` (K,) behind every fold's weights.  A fold whose block of the inverse is not numerically positive
+        definite raises ``LinAlgError``."""
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        if weights not in ("is", "equal"):
+            raise ValueError(f"weights must be 'is' or 'equal', got {weights!r}")
+        n = self._X_train_.shape[0]
+        if folds is not None and n_folds is not None:
+            raise ValueError("give folds or n_folds, not both")
+        if folds is None:
+            folds = split_folds(n, n if n_folds is None else n_folds, random_state)
+        folds = check_folds(folds, n)
+        post = self._post
+        if thetas is None:
+            out = post.cross_validate(self, None, folds)
+        else:
+            rows = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+            n_theta = len(self.kernel_.theta)
+            if not self.warp_inputs:
+                out = post.cross_validate(self, rows, folds)
+            elif post.canonical:
+                out = post.cross_validate(self, rows[:, :n_theta], folds, warps=np.ascontiguousarray(rows[:, n_theta:]))
+            else:  # a generic kernel tree sees a row's warp through the estimator's warpers: one row after the other
+                saved = (self._post_theta, self.alpha_)
+                try:
+                    with self._row_warps() as install:
+                        parts = [post.cross_validate(self, install(r), folds) for r in rows]
+                finally:
+                    self._post_theta, self.alpha_ = saved
+                out = tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+        mean, var, lpd, status = out
+        raise_if_not_pd(status.ravel(), self.kernel_)
+        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        sizes = np.array([len(f) for f in folds], dtype=np.float64)
+        row_mean, row_var = mean * y_std + y_mean, var * y_std**2
+        row_lpd = lpd - sizes[None, :] * np.log(y_std)
+        res = {"folds": folds, "row_mean": row_mean, "row_std": np.sqrt(row_var), "row_fold_lpd": row_lpd}
+        res.update(combine_rows(row_mean, row_var, row_lpd, folds, np.asarray(self.y_train_) * y_std + y_mean,
+                                "equal" if len(row_lpd) == 1 else weights))
+        return res
 
     @contextmanager
     def _row_warps(self):

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import construct_default_kernel, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence
+from .utils import construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence
 
 __all__ = ["Optimizer"]
 
@@ -250,6 +250,12 @@ class Optimizer:
         """What the surrogate looks like right now: 1-D curves and 2-D maps of its partial dependence
         (``utils.partial_dependence`` on the current result, same keyword arguments)."""
         return partial_dependence(self._result(), **kw)
+
+    def cross_validate(self, **kw):
+        """Does the surrogate predict the observations it has not seen?  Held-out predictives of the training points, fold by fold,
+        without a refit (``utils.cross_validate`` on the current result, same keyword arguments; the optimizer's own random state
+        is not consumed)."""
+        return cross_validate(self._result(), **kw)
 
     def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed, minimizer="scipy"):
         """Function draws (device ``sample_y``) at [expected optimum, n_space_samples random points]:

@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -293,6 +293,24 @@ def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, 
     for (a, b), v in zip(pairs, vals[len(dims):]):
         out["pairs"][(a, b)] = (both[a][0], both[b][0], v)
     return out
+
+
+def cross_validate(res, n_folds=None, n_samples=0, folds=None, weights="is", random_state=None):
+    """Cross-validation of the surrogate ``res.models[-1]`` on its own training points ``res.x_iters`` (the indices of ``folds`` and
+    of the result refer to ``Xi``): the held-out predictive of every fold from the resident inverse, without a refit
+    (``BayesGPR.cross_validate``, ``bgp_cross_validate``).  ``n_folds=None`` and no ``folds``: leave-one-out.
+    ``n_samples = 0``: the median GP, which ``res.models[-1]`` predicts with; ``n_samples > 0``: that many rows of ``chain_``,
+    drawn -- like the fold split -- with a generator made from ``random_state``, combined with ``weights``.  Returns
+    ``BayesGPR.cross_validate``'s dict (y units; ``z``, ``point_lpd``, ``elpd`` are the calibration and the score)."""
+    from sklearn.utils import check_random_state
+
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    thetas = None
+    if n_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_samples))]
+    return reg.cross_validate(folds=folds, n_folds=n_folds, thetas=thetas, weights=weights, random_state=rng)
 
 
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):

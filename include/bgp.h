@@ -105,7 +105,8 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *
  * Per-row-warped posteriors (bgp_posterior_batch_warped, below): posterior b is built from the un-warped training inputs
  *   through ITS OWN warp and keeps them resident; a context-level warp is replaced for that call, not composed.  While such
- *   posteriors are resident only bgp_predict_batch_warped reads them: every entry point that would combine resident posteriors
+ *   posteriors are resident only bgp_predict_batch_warped reads them (and bgp_cross_validate, which needs neither the inputs nor
+ *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
  *   bgp_partial_dependence -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
@@ -335,6 +336,35 @@ int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, 
  */
 int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
                            const double* grid, int P, const int* panels, double* out);
+
+/*
+ * Cross-validation from the resident inverses (csrc/bgp_cv.hip): for each of the first B resident posteriors
+ * and each fold F (fold f holds the training indices fold_idx[fold_ptr[f] .. fold_ptr[f + 1])), the predictive of the held-out
+ * OBSERVATIONS y_F given all the other ones, without a refit.  With A = K^-1 (K with the alpha diagonal and the white level) and
+ * a = A y, both resident after any posterior build:
+ *   Sigma_F = (A_FF)^-1,  r_F = Sigma_F a_F,  mean_F = y_F - r_F,  var_i = (Sigma_F)_ii,
+ *   fold_lpd = log N(y_F; mean_F, Sigma_F) = -1/2 a_F^T r_F + sum_k log C_kk - (|F| / 2) log 2 pi,   A_FF = C C^T.
+ * One point per fold is the textbook leave-one-out: mean_i = y_i - a_i / A_ii, var_i = 1 / A_ii.  The variance is that of the
+ * observation: the white level and the point's own alpha are in it (bgp_predict_batch's variance has neither alpha nor, with the
+ * white level at -inf in h_kernel, the noise).  Everything is in the context's (normalised) y units.
+ *   folds     disjoint index sets of [0, n), in any order, not necessarily contiguous, 1 .. 128 points each; they need not cover
+ *             every point.  fold_ptr: n_folds + 1 ascending offsets from 0; fold_idx: fold_ptr[n_folds] indices.
+ *   mean, var B*n, at the points' own positions; NaN where no fold covers the point.
+ *   fold_lpd, status   B*n_folds.  status != 0: A_FF of that (posterior, fold) is not numerically positive definite (the 1-based
+ *             failing pivot); its fold_lpd, mean and var are NaN and no other fold is affected.
+ * Neither the training inputs nor the kernel are read, so plain, per-row-warped (bgp_posterior_batch_warped) and host-Gram
+ * (bgp_posterior_batch_gram) posteriors are served alike.  A (posterior, fold) result depends on that posterior and that fold alone:
+ * the same bits whatever B is and in whatever order the folds are listed.  When every fold is one point, one thread per
+ * (posterior, point) reads the diagonal of the inverse; otherwise one workgroup per (posterior, fold) factorises A_FF in LDS sized
+ * by the call's largest fold.
+ * BGP_ERR_INVALID (before anything is launched, and before the residency answer): B < 1, an empty fold, a fold of more than 128
+ * points (10-fold cross-validation beyond n = 1280), an index outside [0, n), an index listed twice.  BGP_ERR_STATE: fewer than B
+ * resident posteriors, or a submitted batch pending.
+ *   Replaces: nothing in the reference -- there the route is a refit per fold (theta setter on the remaining points + predict,
+ *   bask/bayesgpr.py:200-217, 622-635).
+ */
+int bgp_cross_validate(bgp_ctx* ctx, int B, int n_folds, const int* fold_ptr, const int* fold_idx, double* mean, double* var,
+                       double* fold_lpd, int* status);
 
 /*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
