@@ -119,6 +119,7 @@ SIGNATURES = {
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
+    "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
@@ -722,6 +723,29 @@ class Context:
             res.append(out[:, o:o + sz].reshape((B,) + s).copy())
             o += sz
         return res
+
+    # ---- Sobol' sensitivity of the surrogate mean (bgp_sobol.hip)
+    def sobol_indices(self, H_kernel, A, Bm, masks):
+        """``bgp_sobol_indices``: the pick-freeze sums of the mean of the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2)) over
+        the sample matrices ``A``, ``Bm`` (N, d) for the terms ``masks`` (T,; bit k set: dimension k is taken from ``Bm``).  Returns
+        ``(f0 (B,), V (B,), closed (B, T), total (B, T))`` in normalised-target units: the mean and the variance of the surrogate
+        over the 2N rows, the closed (Saltelli 2010) and the total (Jansen 1999) effect of every term, not yet divided by V.
+        Needs d <= 32."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        A, Bm = _c(np.atleast_2d(A)), _c(np.atleast_2d(Bm))
+        if A.shape[1] != self.d or Bm.shape != A.shape:
+            raise ValueError(f"A and Bm must both be (N, {self.d}), got {A.shape} and {Bm.shape}")
+        masks = np.ascontiguousarray(np.asarray(masks).reshape(-1), dtype=np.uint32)
+        T = len(masks)
+        if T == 0:
+            masks = np.zeros(1, dtype=np.uint32)  # (a pointer to hand over; the C layer names the fault)
+        f0, V = np.empty(B), np.empty(B)
+        closed, total = np.empty((B, T)), np.empty((B, T))
+        up = C.POINTER(C.c_uint)
+        _check(self._lib.bgp_sobol_indices(self._h, B, _p(H), A.shape[0], _p(A), _p(Bm), T, masks.ctypes.data_as(up), _p(f0), _p(V),
+                                           _p(closed), _p(total)), "bgp_sobol_indices")
+        return f0, V, closed, total
 
     # ---- cross-validation from the resident inverses (bgp_cv.hip; DESIGN.md section 20)
     def cross_validate(self, B, folds):

@@ -85,6 +85,82 @@ def partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why):
     return out
 
 
+_sens_told = []
+SENS_DMAX = 32  # dimensions of the device call: one bit of a 32-bit mask each (bgp_sobol.hip)
+
+
+def _sens_tell_once(why):
+    """One line on stderr, once per process: sensitivity indices computed through ``predict`` on synthesised rows."""
+    if not _sens_told:
+        _sens_told.append(True)
+        print("[bayes_skopt_amd] sensitivity: through predict on synthesised rows (%s)" % why, file=sys.stderr, flush=True)
+
+
+def sobol_masks(terms, d):
+    """The terms of a sensitivity analysis -- each a dimension or a tuple of dimensions of ``d``, the empty tuple included -- as a
+    list of Python ints with bit k set for dimension k.  ValueError for an empty list and for a dimension outside [0, d)."""
+    masks = []
+    for term in terms:
+        m = 0
+        for k in np.atleast_1d(np.asarray(term, dtype=np.int64)).reshape(-1):
+            if not 0 <= int(k) < d:
+                raise ValueError(f"term {term!r} names dimension {int(k)} outside [0, {d})")
+            m |= 1 << int(k)
+        masks.append(m)
+    if not masks:
+        raise ValueError("sensitivity needs at least one term")
+    return masks
+
+
+def sobol_rows(A, Bm, mask):
+    """The synthetic rows of one term: ``A`` with the columns whose bits are set in ``mask`` taken from ``Bm``."""
+    pick = np.array([(mask >> k) & 1 for k in range(A.shape[1])], dtype=bool)
+    return np.where(pick[None, :], Bm, A)
+
+
+def sobol_estimator(fA, fB, fT):
+    """The pick-freeze estimator on means ``fA``, ``fB`` (..., N) and ``fT`` (..., T, N): ``(f0 (...), V (...), closed (..., T),
+    total (..., T))`` -- the identities of DESIGN.md section 21 (Saltelli et al. 2010 for the closed effect, Jansen 1999 for the
+    total one), not yet divided by V."""
+    fA, fB, fT = np.asarray(fA), np.asarray(fB), np.asarray(fT)
+    N = fA.shape[-1]
+    f0 = (fA + fB).sum(axis=-1) / (2.0 * N)
+    ca, cb = fA - f0[..., None], fB - f0[..., None]
+    V = (ca * ca + cb * cb).sum(axis=-1) / (2.0 * N)
+    dt = fT - fA[..., None, :]
+    closed = (cb[..., None, :] * dt).sum(axis=-1) / N
+    total = (dt * dt).sum(axis=-1) / (2.0 * N)
+    return f0, V, closed, total
+
+
+def sensitivity_by_predict(gp, thetas, A, Bm, masks, why):
+    """The fallback of ``sensitivity``: the means of A, Bm and every term's synthetic rows through ``predict``, at most ``PD_ROWS``
+    rows per call, then ``sobol_estimator`` in numpy.  ``thetas=None``: the resident posterior with ``kernel_`` as it is; otherwise
+    one item per chain row -- under ``warp_inputs`` one row at a time with the row's own warp (``BayesGPR._row_warps``).  Returns
+    (f0 (B,), V (B,), closed (B, T), total (B, T)) in normalised-target units."""
+    _sens_tell_once(why)
+    A, Bm = np.atleast_2d(np.asarray(A, dtype=np.float64)), np.atleast_2d(np.asarray(Bm, dtype=np.float64))
+    N = A.shape[0]
+    rows = None if thetas is None else np.atleast_2d(thetas)
+
+    def means(X):
+        if rows is None:
+            return np.atleast_2d(gp._post.predict(gp, X, False)[0])
+        if gp.warp_inputs:
+            saved = (gp._post_theta, gp.alpha_)  # (installing a warp forgets the median GP's posterior: as BayesGPR.cross_validate)
+            try:
+                with gp._row_warps() as install:
+                    return np.stack([gp._post.rows_predict(gp, install(r), X, True)[0][0] for r in rows])
+            finally:
+                gp._post_theta, gp.alpha_ = saved
+        return np.asarray(gp._post.hyper_predict(gp, rows, X, True)[0])
+
+    X = np.concatenate([A, Bm] + [sobol_rows(A, Bm, m) for m in masks])
+    F = np.concatenate([means(X[r0:r0 + PD_ROWS]) for r0 in range(0, len(X), PD_ROWS)], axis=1)
+    F = F.reshape(F.shape[0], len(masks) + 2, N)
+    return sobol_estimator(F[:, 0], F[:, 1], F[:, 2:])
+
+
 class PendingLml:
     """A block's LML between ``lml_begin`` and ``lml_finish``; ``submitted``: the device is already working on it."""
 
@@ -227,6 +303,21 @@ class CanonicalPosterior:
             H = self.build_rows(gp, thetas)
         return gp._ctx.partial_dependence(H, Xs, grids, panels), "device"
 
+    def sensitivity(self, gp, thetas, A, Bm, masks):
+        """((f0 (B,), V (B,), closed (B, T), total (B, T)) in normalised-target units, "device" | "host").  ``thetas=None``: the
+        resident median GP (B = 1); a block of chain rows: one batched build, then ONE device call over all of them
+        (``bgp_sobol_indices``).  More than 32 dimensions, and chain rows under ``warp_inputs`` (every row
+        has its own training inputs), go through ``predict``."""
+        if gp._X_train_.shape[1] > SENS_DMAX or (thetas is not None and gp.warp_inputs):
+            why = "more than 32 dimensions" if gp._X_train_.shape[1] > SENS_DMAX else "hyper-posterior rows with input warping"
+            return sensitivity_by_predict(gp, thetas, A, Bm, masks, why), "host"
+        if thetas is None:
+            self.make_resident(gp)
+            H = gp._canonical(gp._kernel_theta_for_predict())
+        else:
+            H = self.build_rows(gp, thetas)
+        return gp._ctx.sobol_indices(H, A, Bm, masks), "device"
+
     def cross_validate(self, gp, thetas, folds, warps=None):
         """(mean (B, n), var (B, n), fold_lpd (B, K), status (B, K)) of the held-out observations, normalised-target units
         (``bgp_cross_validate``).  ``thetas=None``: the resident median GP; a block of chain rows (``warps``
@@ -336,6 +427,9 @@ class GramPosterior:
 
     def partial_dependence(self, gp, thetas, Xs, grids, panels):
         return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, "generic kernel tree"), "host"
+
+    def sensitivity(self, gp, thetas, A, Bm, masks):
+        return sensitivity_by_predict(gp, thetas, A, Bm, masks, "generic kernel tree"), "host"
 
     def cross_validate(self, gp, thetas, folds, warps=None):
         """As ``CanonicalPosterior.cross_validate``: the device call reads the resident inverses alone, so host kernel matrices

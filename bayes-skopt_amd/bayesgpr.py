@@ -26,7 +26,7 @@ from sklearn.base import BaseEstimator, RegressorMixin, clone
 from sklearn.utils import check_random_state
 
 from . import _lib, distributed
-from ._posterior import CanonicalPosterior, GramPosterior, noise_off, raise_if_not_pd
+from ._posterior import CanonicalPosterior, GramPosterior, noise_off, raise_if_not_pd, sobol_masks
 from .crossval import check_folds, combine_rows, split_folds
 from .kernels import ConstantKernel, WhiteKernel, analyse_kernel, param_for_white_kernel_in_sum
 from .kernels import RBF as _RBF
@@ -739,6 +739,35 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         if thetas is None:
             vals = [v[0] for v in vals]
         return (vals, path) if return_path else vals
+
+    def sensitivity(self, A, Bm, terms=None, thetas=None, return_path=False):
+        """Variance-based (Sobol') sensitivity of the predictive mean by the pick-freeze design: ``A``, ``Bm`` are two independent
+        sample matrices (N, d; transformed space), ``terms`` a list of dimensions or tuples of dimensions (default: every single
+        dimension; the empty tuple and all dimensions are legal).  Returns ``(mean, variance, closed, total)`` in y units: the
+        mean and the variance of the surrogate over the 2N rows and, per term, the closed effect (Saltelli et al. 2010: the
+        variance explained by the term's dimensions alone, first order for one dimension) and the total effect (Jansen 1999:
+        everything those dimensions take part in); the indices are ``closed / variance`` and ``total / variance``.  Scalars and
+        (T,) arrays for the median GP (``thetas=None``), (B,) and (B, T) for a block of B chain rows.  Canonical kernels in up
+        to 32 dimensions: ONE device call for all terms and rows (``bgp_sobol_indices``; the context-level
+        warp of ``warp_inputs`` is applied to both matrices on the device).  Generic kernel trees, more dimensions, and chain
+        rows under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" |
+        "host"."""
+        A, Bm = np.atleast_2d(np.asarray(A, dtype=np.float64)), np.atleast_2d(np.asarray(Bm, dtype=np.float64))
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        d = self._X_train_.shape[1]
+        if A.shape[1] != d or Bm.shape != A.shape or A.shape[0] < 1:
+            raise ValueError(f"A and Bm must both be (N, {d}) with N >= 1, got {A.shape} and {Bm.shape}")
+        if self.warp_inputs:
+            validate_zeroone(A)
+            validate_zeroone(Bm)
+        masks = sobol_masks([(k,) for k in range(d)] if terms is None else terms, d)
+        (f0, V, closed, total), path = self._post.sensitivity(self, thetas, A, Bm, masks)
+        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        out = (y_std * f0 + y_mean, y_std**2 * V, y_std**2 * closed, y_std**2 * total)
+        if thetas is None:
+            out = tuple(v[0] for v in out)
+        return (*out, path) if return_path else out
 
     def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
         """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the

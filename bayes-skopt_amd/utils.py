@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -292,6 +292,54 @@ def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, 
         out["dims"][k] = (both[k][0], v)
     for (a, b), v in zip(pairs, vals[len(dims):]):
         out["pairs"][(a, b)] = (both[a][0], both[b][0], v)
+    return out
+
+
+def sensitivity_indices(res, dims=None, pairs=None, n_samples=4096, n_gp_samples=0, random_state=None):
+    """Which dimensions matter, and which interact: variance-based (Sobol') sensitivity indices of the surrogate mean of
+    ``res.models[-1]`` over the space, by the pick-freeze design on two successive ``space.rvs_transformed(n_samples,
+    random_state)`` draws (Integer and Categorical dimensions keep their snapped values; a dimension is one column).  ``dims``: the
+    dimensions (default all); ``pairs``: None, "all" (every k1 < k2 of ``dims``) or a list of pairs -- a pair adds the term {a, b}
+    (and its two dimensions, where ``dims`` leaves them out).  Returns a dict: ``"first"`` {k: S_k}, the share of the variance
+    explained by dimension k alone; ``"total"`` {k: T_k}, the share of everything k takes part in -- a dimension with a small
+    total index can be frozen; ``"interaction"`` {(a, b): S_ab - S_a - S_b}; ``"mean"`` and ``"variance"`` of the surrogate over
+    the samples (y units); and ``"path"``: "device" when every term came from ONE device call (``bgp_sobol_indices``, DESIGN.md
+    section 21), "host" when they came through ``predict`` on synthesised rows.  The indices are NaN when the variance is 0.
+    ``n_gp_samples > 0``: the averages over that many rows drawn from ``chain_`` with ``random_state``, and under ``"band"``
+    {"first": {k: (5 %, 95 %)}, "total": {k: (5 %, 95 %)}} the per-draw band; the default is the median GP, which
+    ``res.models[-1]`` predicts with."""
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    d = space.n_dims
+    dims = list(range(d)) if dims is None else [int(k) for k in dims]
+    if pairs == "all":
+        pairs = [(a, b) for i, a in enumerate(dims) for b in dims[i + 1:]]
+    pairs = [] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    singles = dims + [k for k in dict.fromkeys(v for pr in pairs for v in pr) if k not in dims]
+    A = space.rvs_transformed(n_samples, random_state=rng)
+    Bm = space.rvs_transformed(n_samples, random_state=rng)
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    mean, var, closed, total, path = reg.sensitivity(A, Bm, [(k,) for k in singles] + pairs, thetas=thetas, return_path=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        S, Tt = closed / np.asarray(var)[..., None], total / np.asarray(var)[..., None]
+    at = {k: i for i, k in enumerate(singles)}
+    inter = np.stack([S[..., len(singles) + i] - S[..., at[a]] - S[..., at[b]] for i, (a, b) in enumerate(pairs)], axis=-1) \
+        if pairs else np.zeros(S.shape[:-1] + (0,))
+    out = {"path": path}
+    if thetas is not None:
+        out["band"] = {"first": {k: tuple(np.percentile(S[:, at[k]], [5.0, 95.0])) for k in dims},
+                       "total": {k: tuple(np.percentile(Tt[:, at[k]], [5.0, 95.0])) for k in dims}}
+        mean, var, S, Tt, inter = (np.mean(v, axis=0) for v in (mean, var, S, Tt, inter))
+    out["first"] = {k: float(S[at[k]]) for k in dims}
+    out["total"] = {k: float(Tt[at[k]]) for k in dims}
+    out["interaction"] = {pr: float(inter[i]) for i, pr in enumerate(pairs)}
+    out["mean"], out["variance"] = float(mean), float(var)
     return out
 
 

@@ -109,7 +109,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -336,6 +336,28 @@ int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, 
  */
 int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
                            const double* grid, int P, const int* panels, double* out);
+
+/*
+ * Variance-based (Sobol') sensitivity of the surrogate mean by the pick-freeze design (csrc/bgp_sobol.hip),
+ * for the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read).  With two
+ * sample matrices A, Bm (N*d each, row-major) and T terms, term t the set of dimensions whose bits are set in masks[t]:
+ *   fA_i = mu_b(A_i),  fB_i = mu_b(Bm_i),  fT_ti = mu_b(A_i with the columns in masks[t] taken from Bm_i)    (normalised-y units)
+ *   f0_b = (1 / 2N) sum_i (fA_i + fB_i)                 V_b     = (1 / 2N) sum_i ((fA_i - f0)^2 + (fB_i - f0)^2)
+ *   closed_bt = (1 / N) sum_i (fB_i - f0) (fT_ti - fA_i)     total_bt = (1 / 2N) sum_i (fA_i - fT_ti)^2
+ * (Saltelli et al. 2010 for the closed effect -- the first-order one for a single dimension --, Jansen 1999 for the total one; the
+ * indices are closed / V and total / V, the caller's division.)  Every mean comes out of one routine applied to a synthetic row
+ * whose squared distance to a training point is a sum of squares in x / l, ascending dimension: an empty mask gives fA and a full
+ * one fB bit for bit (closed = total = 0 for the empty mask, and for every term when A == Bm).  The means (B*(T + 2)*N doubles of
+ * device scratch) are reduced in a fixed order: chunks of 256 samples, a fixed tree inside a chunk, chunk partials in ascending
+ * order, f0 before the centred sums.  f0, V and a term's closed / total depend on the posterior, A, Bm and that term alone: the same
+ * bits whatever else shares the call, wherever the term stands in the list, whatever B is.  A and Bm go through the context-level
+ * warp as predict's queries do.  f0, V: B;  closed, total: B*T, posterior-major.
+ * Needs d <= 32, 1 <= N <= 2^24, 1 <= T <= 4096, 1 <= B <= 65535, B (T + 2) N <= 2^30, no mask bit at or above d (BGP_ERR_INVALID
+ * before anything is launched) and B resident posteriors (BGP_ERR_STATE).
+ *   Replaces: nothing in the reference -- there the route is predict on N (T + 2) synthesised rows and a reduction on the host.
+ */
+int bgp_sobol_indices(bgp_ctx* ctx, int B, const double* h_kernel, int N, const double* A, const double* Bm, int T,
+                      const unsigned* masks, double* f0, double* V, double* closed, double* total);
 
 /*
  * Cross-validation from the resident inverses (csrc/bgp_cv.hip): for each of the first B resident posteriors
