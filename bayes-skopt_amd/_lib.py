@@ -120,6 +120,7 @@ SIGNATURES = {
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
+    "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
@@ -746,6 +747,28 @@ class Context:
         _check(self._lib.bgp_sobol_indices(self._h, B, _p(H), A.shape[0], _p(A), _p(Bm), T, masks.ctypes.data_as(up), _p(f0), _p(V),
                                            _p(closed), _p(total)), "bgp_sobol_indices")
         return f0, V, closed, total
+
+    # ---- posterior covariance of the gradient and the active-subspace sums (bgp_gcov.hip)
+    def grad_cov(self, H_kernel, Xq, want_dmean=True, want_cov=True, want_csum=False):
+        """``bgp_grad_cov``: for the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2)) at the rows of ``Xq`` (m, d) the gradient of
+        the mean ``dmean`` (B, m, d), the posterior covariance of the latent function's gradient ``cov`` (B, m, d, d; exactly
+        symmetric, diagonal clipped at 0) and ``csum`` (B, 2, d, d): the averages over the rows of ``dmean dmean^T`` and of ``cov``
+        (C_mean, C_cov of the active-subspace matrix).  Normalised-target units; an output that is not wanted is None and is
+        neither downloaded nor, where nothing needs it, computed.  Needs d <= 32, m d <= 2^24, a differentiable family (not
+        Matern 1/2) and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xq = _c(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"query points must have {self.d} columns, got {Xq.shape[1]}")
+        m, d = Xq.shape[0], self.d
+        dmean = np.empty((B, m, d)) if want_dmean else None
+        cov = np.empty((B, m, d, d)) if want_cov else None
+        csum = np.empty((B, 2, d, d)) if want_csum else None
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_grad_cov(self._h, B, _p(H), m, _p(Xq), _p(dmean) if want_dmean else null,
+                                      _p(cov) if want_cov else null, _p(csum) if want_csum else null), "bgp_grad_cov")
+        return dmean, cov, csum
 
     # ---- cross-validation from the resident inverses (bgp_cv.hip; DESIGN.md section 20)
     def cross_validate(self, B, folds):

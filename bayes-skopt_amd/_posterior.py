@@ -9,6 +9,7 @@ import sys
 import numpy as np
 from sklearn.base import clone
 
+from . import gradcov
 from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
 
 _PD_MESSAGE = (
@@ -318,6 +319,32 @@ class CanonicalPosterior:
             H = self.build_rows(gp, thetas)
         return gp._ctx.sobol_indices(H, A, Bm, masks), "device"
 
+    gradient_cov_path = "auto"  # "host": always numpy on the downloaded inverse (tests compare the two paths)
+
+    def gradient_cov(self, gp, thetas, X, want):
+        """((dmean (B, m, d) | None, cov (B, m, d, d) | None, csum (B, 2, d, d) | None) in normalised-target units, "device" |
+        "host"); ``want``: which of the three.  ``thetas=None``: the resident median GP (B = 1); a block of chain rows: one batched
+        build and ONE device call per ``max_batch`` rows (``bgp_grad_cov``).  More than 32 dimensions, or
+        ``gradient_cov_path = "host"``: ``gradcov.gradient_cov_host``, said once.  Matern 1/2: ValueError; ``warp_inputs``:
+        NotImplementedError (the chain rule through the Beta pdf is not built)."""
+        gradcov.check_differentiable(gp._plan.stationary)
+        if gp.warp_inputs:
+            raise NotImplementedError("the gradient covariance is not available with warp_inputs=True: the derivative with respect "
+                                      "to the un-warped coordinates needs the chain rule through the Beta pdf")
+        d = gp._X_train_.shape[1]
+        if d > gradcov.GCOV_DMAX or self.gradient_cov_path == "host":
+            dmean, cov = gradcov.host_rows(gp, thetas, X, "more than 32 dimensions" if d > gradcov.GCOV_DMAX else "forced")
+            csum = np.stack(gradcov.subspace_sums(dmean, cov), axis=1) if want[2] else None
+            return (dmean if want[0] else None, cov if want[1] else None, csum), "host"
+        call = lambda H: gp._ctx.grad_cov(H, X, want_dmean=want[0], want_cov=want[1], want_csum=want[2])  # noqa: E731
+        if thetas is None:
+            self.make_resident(gp)
+            return call(gp._canonical(gp._kernel_theta_for_predict())), "device"
+        thetas = np.atleast_2d(thetas)
+        step = max(1, int(gp._ctx.max_batch))  # (the batched build holds max_batch rows: one build and one call per block)
+        parts = [call(self.build_rows(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]
+        return tuple(np.concatenate([p[i] for p in parts]) if want[i] else None for i in range(3)), "device"
+
     def cross_validate(self, gp, thetas, folds, warps=None):
         """(mean (B, n), var (B, n), fold_lpd (B, K), status (B, K)) of the held-out observations, normalised-target units
         (``bgp_cross_validate``).  ``thetas=None``: the resident median GP; a block of chain rows (``warps``
@@ -430,6 +457,10 @@ class GramPosterior:
 
     def sensitivity(self, gp, thetas, A, Bm, masks):
         return sensitivity_by_predict(gp, thetas, A, Bm, masks, "generic kernel tree"), "host"
+
+    def gradient_cov(self, gp, thetas, X, want):
+        raise NotImplementedError("the gradient covariance needs a canonical kernel: a generic kernel tree has no closed-form "
+                                  "cross derivative")
 
     def cross_validate(self, gp, thetas, folds, warps=None):
         """As ``CanonicalPosterior.cross_validate``: the device call reads the resident inverses alone, so host kernel matrices

@@ -769,6 +769,43 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out = tuple(v[0] for v in out)
         return (*out, path) if return_path else out
 
+    def _gradient_cov(self, X, thetas, want):
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        d = self._X_train_.shape[1]
+        if X.shape[1] != d or X.shape[0] < 1:
+            raise ValueError(f"the points must be (m, {d}) with m >= 1, got {X.shape}")
+        return self._post.gradient_cov(self, thetas, X, want)
+
+    def gradient_posterior(self, X, thetas=None, return_path=False):
+        """The posterior distribution of the gradient of the latent function at the rows of ``X`` (m, d; transformed space):
+        ``(grad_mean (m, d), grad_cov (m, d, d))`` in y units per unit of the transformed coordinate -- grad f(x) is normal with
+        that mean (the ``grad_mean`` of ``predict_gradients``) and that covariance (exactly symmetric, diagonal clipped at 0), so
+        ``grad_mean[:, k] / sqrt(grad_cov[:, k, k])`` says whether the slope in dimension k is distinguishable from zero.  For the
+        median GP (``thetas=None``), or (B, m, d) and (B, m, d, d) for a block of B chain rows.  Canonical kernels in up to 32
+        dimensions: ONE device call (``bgp_grad_cov``); more dimensions: numpy on the downloaded inverse,
+        said once on stderr.  Matern 1/2 is not differentiable: ValueError.  Generic kernel trees and ``warp_inputs=True``:
+        NotImplementedError.  ``return_path``: also "device" | "host"."""
+        (dmean, cov, _), path = self._gradient_cov(X, thetas, (True, True, False))
+        y_std = float(np.ravel(self.y_train_std_)[0])
+        out = (y_std * dmean, y_std**2 * cov)
+        if thetas is None:
+            out = tuple(v[0] for v in out)
+        return (*out, path) if return_path else out
+
+    def active_subspace(self, Xs, thetas=None, return_path=False):
+        """The two parts of the active-subspace matrix ``C = E_x[grad f grad f^T]`` over the sample rows ``Xs`` (m, d; transformed
+        space): ``(C_mean, C_cov)``, the average of ``grad_mean grad_mean^T`` and of ``grad_cov`` (``gradient_posterior``), each
+        (d, d) in y units squared per unit of transformed coordinate squared, or (B, d, d) for a block of B chain rows.  On the
+        device path only the two sums come back.  Paths and refusals as ``gradient_posterior``."""
+        (_, _, csum), path = self._gradient_cov(Xs, thetas, (False, False, True))
+        y_std = float(np.ravel(self.y_train_std_)[0])
+        out = (y_std**2 * csum[:, 0], y_std**2 * csum[:, 1])
+        if thetas is None:
+            out = tuple(v[0] for v in out)
+        return (*out, path) if return_path else out
+
     def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
         """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the
         held-out OBSERVATIONS ``y_F`` given the remaining points -- without a refit: it follows from the resident ``K^-1`` and

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, sensitivity_indices
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, sensitivity_indices
 
 __all__ = ["Optimizer"]
 
@@ -250,6 +250,11 @@ class Optimizer:
         """What the surrogate looks like right now: 1-D curves and 2-D maps of its partial dependence
         (``utils.partial_dependence`` on the current result, same keyword arguments)."""
         return partial_dependence(self._result(), **kw)
+
+    def active_subspace(self, **kw):
+        """Which directions matter: the eigen-decomposition of the active-subspace matrix of the current surrogate
+        (``utils.active_subspace`` on the current result, same keyword arguments)."""
+        return active_subspace(self._result(), **kw)
 
     def sensitivity_indices(self, **kw):
         """Which dimensions matter and which interact: first-order, total and pair-interaction Sobol' indices of the current

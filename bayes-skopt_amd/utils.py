@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "active_subspace", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -341,6 +341,34 @@ def sensitivity_indices(res, dims=None, pairs=None, n_samples=4096, n_gp_samples
     out["interaction"] = {pr: float(inter[i]) for i, pr in enumerate(pairs)}
     out["mean"], out["variance"] = float(mean), float(var)
     return out
+
+
+def active_subspace(res, n_samples=1024, samples=None, n_gp_samples=0, random_state=None):
+    """Which DIRECTIONS matter: the active-subspace matrix ``C = E_x[grad f grad f^T]`` of the surrogate ``res.models[-1]`` over
+    ``n_samples`` points of the space (``space.rvs_transformed(n_samples, random_state)``, or the given ``samples`` in the original
+    space), in transformed coordinates.  Under the GP, ``C = C_mean + C_cov``: the average of the mean gradient's outer product and
+    of the gradient's posterior covariance (``BayesGPR.active_subspace``, ``bgp_grad_cov``) -- without the
+    second term the eigenvalues are understated exactly where the space is unexplored.  Where Sobol' indices call two dimensions
+    "important and interacting", the eigenvectors show an objective that moves along ``x_1 + x_2`` and is flat along ``x_1 - x_2``.
+    Returns a dict: ``"C"``, ``"C_mean"``, ``"C_cov"`` (d, d; y units squared); ``"eigenvalues"`` in descending order;
+    ``"eigenvectors"`` as columns, each signed so that its largest-magnitude component is positive; ``"explained"``, the cumulative
+    eigenvalue share; ``"diag_share"`` {k: C_kk / trace}; ``"path"``: "device" | "host".  ``n_gp_samples > 0``: the matrices
+    averaged over that many rows drawn from ``chain_`` with ``random_state``, and under ``"band"`` the per-draw (5 %, 95 %) band of
+    each ranked eigenvalue; the default is the median GP, which ``res.models[-1]`` predicts with."""
+    from sklearn.utils import check_random_state
+
+    from .gradcov import assemble
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    Xs = space.rvs_transformed(n_samples, random_state=rng) if samples is None else space.transform(samples)
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    C_mean, C_cov, path = reg.active_subspace(Xs, thetas=thetas, return_path=True)
+    return assemble(C_mean, C_cov, path)
 
 
 def cross_validate(res, n_folds=None, n_samples=0, folds=None, weights="is", random_state=None):

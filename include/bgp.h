@@ -109,7 +109,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -360,6 +360,28 @@ int bgp_sobol_indices(bgp_ctx* ctx, int B, const double* h_kernel, int N, const 
                       const unsigned* masks, double* f0, double* V, double* closed, double* total);
 
 /*
+ * Posterior covariance of the surrogate's gradient, and the active-subspace sums (csrc/bgp_gcov.hip), for the
+ * resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read: the latent function) at the m
+ * query rows Xq (m*d, row-major).  With G_jk(x) = d k(x, X_j) / dx_k as in bgp_predict_grad_batch (cf = c in the product form, 1 in
+ * the sum form; the constant and white terms add nothing) and phi = 1 (RBF), 3 (Matern 3/2), 5/3 (Matern 5/2):
+ *   g(x)     = G(x)^T alpha                                   dmean  B*m*d        gradient of the mean
+ *   Sigma(x) = diag(cf phi / l_k^2) - G(x)^T K^-1 G(x)        cov    B*m*d*d      posterior covariance of grad f(x)
+ *   C_mean = (1 / m) sum_s g(x_s) g(x_s)^T,  C_cov = (1 / m) sum_s Sigma(x_s)      csum   B*2*d*d      C_mean, then C_cov
+ * in normalised-y units per unit of the (transformed) input; K^-1 and alpha are the resident ones (alpha diagonal and noise as built).
+ * Any output may be NULL, not all three.  Sigma is exactly symmetric (the lower triangle is computed and mirrored) and its diagonal
+ * is clipped at 0 as bgp_predict_batch clips the variance.  The product G K^-1 runs on the fp64 MFMA ring; every sum has a fixed
+ * order: a point's dmean and cov are the same bits whatever m and B are, whatever else shares the call and however the call is
+ * chunked, and csum depends on the posterior and the ordered list of points alone (chunks of 256 points by their index in Xq, a
+ * fixed tree inside a chunk, chunk partials in ascending order, one division by m).
+ * Needs d <= 32, 1 <= m, m d <= 2^24, 1 <= B <= 65535, a family with a mean-square derivative -- Matern 1/2 is not differentiable
+ * and is refused, never approximated -- and no context-level warp (warped inputs are refused as by the other gradient entry
+ * points): BGP_ERR_INVALID before anything is launched; B resident posteriors: BGP_ERR_STATE.  A refused call leaves the resident
+ * posteriors as they were.
+ *   Replaces: nothing in the reference -- skopt's predict(return_std_grad) stops at the gradient of the std at one point.
+ */
+int bgp_grad_cov(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* dmean, double* cov, double* csum);
+
+/*
  * Cross-validation from the resident inverses (csrc/bgp_cv.hip): for each of the first B resident posteriors
  * and each fold F (fold f holds the training indices fold_idx[fold_ptr[f] .. fold_ptr[f + 1])), the predictive of the held-out
  * OBSERVATIONS y_F given all the other ones, without a refit.  With A = K^-1 (K with the alpha diagonal and the white level) and
@@ -445,7 +467,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   BGP_PS_GEN (0 / 1: the Gram blocks of a launch-free LML batch are built by a kernel in front of it / by its own tile workers
  *   at the head of their ticket list; default by shape), BGP_SYRK_GEN (0 / 1: on the launch schedule, every Gram block by the
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
- *   pipelined Gram kernel would run, see bgp_lml_gen_stats).
+ *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
+ *   256; default by n and d; read at every call).
  * Runtime switch set by the PYTHON package, not read by this library: bayes-skopt_amd/_lib.py exports HIP_FORCE_DEV_KERNARG=1 (kernel
  *   arguments in device memory: -6 % per call on the launch schedule at n = 1024 x 32) at import unless the user has set it --
  *   a process-wide setting that every other HIP user of the process inherits, effective only if the GPU has not been initialised
