@@ -131,6 +131,7 @@ SIGNATURES = {
     "bgp_mcmc_begin": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp]),
     "bgp_mcmc_begin_ex": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp]),
     "bgp_mcmc_progress": (C.c_int, [_vp, _ip]),
+    "bgp_mcmc_form": (C.c_int, [_vp, _ip]),
     "bgp_comm_init_loopback": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(_vp)]),
     "bgp_comm_bench_lml_gather": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp]),
     "bgp_mcmc_steps": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _dp, _dp]),
@@ -242,6 +243,7 @@ def device_identity(device=0):
 ACQ_EI, ACQ_MEAN, ACQ_LCB, ACQ_STD = 0, 1, 2, 3  # include/bgp.h BGP_ACQ_*
 ACQ_MAX = 8
 BGP_LIE_VALUE, BGP_LIE_KB = 0, 1  # include/bgp.h BGP_LIE_* (bgp_fantasy_step)
+MCMC_FORMS = ("step_lds", "step_hbm", "fused")  # include/bgp.h bgp_mcmc_form
 
 
 _live_contexts = weakref.WeakSet()
@@ -355,6 +357,9 @@ class Context:
         _check(self._lib.bgp_mcmc_begin_ex(self._h, comm._h if comm is not None else None, int(nwarp), W, p, int(nsteps), _p(h_src),
                                            _p(h_fixed), _p(prior_kind), _p(prior_par), _p(coords), _p(logp)), "bgp_mcmc_begin")
         self._mcmc = (W, p, int(nsteps))
+        form = C.c_int(-1)
+        _check(self._lib.bgp_mcmc_form(self._h, C.byref(form)), "bgp_mcmc_form")
+        self.mcmc_form = MCMC_FORMS[form.value]  # (of the run opened last: what the tests read)
 
     def mcmc_progress(self):
         """Steps of the open run the device has worked through (``bgp_mcmc_progress``; never blocks)."""

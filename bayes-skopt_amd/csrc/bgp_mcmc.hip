@@ -439,6 +439,16 @@ extern "C" int bgp_mcmc_progress(bgp_ctx* c, int* steps_done) {
   return BGP_OK;
 }
 
+// Which form of the half-step the open run takes (include/bgp.h): what a test reads to know that it ran the form it was written for.
+extern "C" int bgp_mcmc_form(bgp_ctx* c, int* form) {
+  if (!c || !c->mcmc || !form) {
+    bgp_set_error("bgp_mcmc_form: no run is open (bgp_mcmc_begin), or NULL argument");
+    return BGP_ERR_STATE;
+  }
+  *form = c->mcmc->small ? 2 : (c->mcmc->hbm ? 1 : 0);
+  return BGP_OK;
+}
+
 extern "C" int bgp_mcmc_end(bgp_ctx* c, double* chain, double* logp, double* coords_out, double* logp_out, long long* naccepted,
                             int* info) {
   if (!c || !c->mcmc) {

@@ -650,6 +650,8 @@ int bgp_lml_batch_wait_allgather(bgp_ctx* ctx, bgp_comm* comm, int per_rank, int
  * bgp_ctx_destroy drops an open run.  bgp_mcmc_run = begin + one bgp_mcmc_steps with the whole plan + end.
  * bgp_mcmc_progress: steps of the open run whose segment the device has worked through (never blocks): what a progress bar shows
  * while the run is resident (emcee's tqdm bar, bask/bayesgpr.py:522-524 with progress=True, the default of fit, :550-564).
+ * bgp_mcmc_form (debugging aid): the form of the half-step the open run takes -- 0 the step kernel with the ensemble in LDS, 1 the
+ * step kernel on the arrays in HBM, 2 the fused one-launch half-step.
  *
  * bgp_mcmc_begin_ex adds the two things that change the SHAPE of a half-step:
  *   nwarp = 2 d   walkers that carry their own input warp (warp_inputs=True, bask/bayesgpr.py:353-365): the last 2 d entries of a
@@ -671,6 +673,7 @@ int bgp_mcmc_begin_ex(bgp_ctx* ctx, bgp_comm* comm, int nwarp, int W, int p, int
                       const double* h_fixed, const int* prior_kind, const double* prior_par, const double* coords0,
                       const double* logp0);
 int bgp_mcmc_progress(bgp_ctx* ctx, int* steps_done);
+int bgp_mcmc_form(bgp_ctx* ctx, int* form);
 int bgp_mcmc_begin(bgp_ctx* ctx, int W, int p, int nsteps, const int* h_src, const double* h_fixed, const int* prior_kind,
                    const double* prior_par, const double* coords0, const double* logp0);
 int bgp_mcmc_steps(bgp_ctx* ctx, int nseg, const int* movers, const int* partners, const double* zz, const double* factors,
