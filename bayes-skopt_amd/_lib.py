@@ -121,6 +121,7 @@ SIGNATURES = {
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "bgp_knowledge_gradient": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
@@ -774,6 +775,28 @@ class Context:
         _check(self._lib.bgp_grad_cov(self._h, B, _p(H), m, _p(Xq), _p(dmean) if want_dmean else null,
                                       _p(cov) if want_cov else null, _p(csum) if want_csum else null), "bgp_grad_cov")
         return dmean, cov, csum
+
+    # ---- knowledge-gradient acquisition (bgp_kg.hip)
+    def knowledge_gradient(self, H_kernel, noise, Xcand, Xref, y_std, n_samples, want_rows=True):
+        """``bgp_knowledge_gradient``: for the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2), white level at -inf) the expected
+        decrease of the minimum of the posterior mean over ``Xref`` (M, d; 0 <= M <= 255) and the candidate itself after one
+        observation with variance ``var(x) + noise[b]`` at each row of ``Xcand`` (m, d).  Returns ``(kg (B, m) | None, avg (m,))``
+        in y units (``y_std`` times the normalised value); ``avg`` adds the rows in order, each divided by ``n_samples``.  Needs
+        d <= 32 and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        noise = _c(np.asarray(noise, dtype=np.float64).reshape(B))
+        Xc = _c(np.atleast_2d(Xcand))
+        Xr = _c(np.asarray(Xref, dtype=np.float64).reshape(-1, self.d))
+        if Xc.shape[1] != self.d:
+            raise ValueError(f"candidates must have {self.d} columns, got {Xc.shape[1]}")
+        m, M = Xc.shape[0], Xr.shape[0]
+        kg = np.empty((B, m)) if want_rows else None
+        avg = np.empty(m)
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_knowledge_gradient(self._h, B, _p(H), _p(noise), m, _p(Xc), M, _p(Xr) if M else null, float(y_std),
+                                                int(n_samples), _p(kg) if want_rows else null, _p(avg)), "bgp_knowledge_gradient")
+        return kg, avg
 
     # ---- cross-validation from the resident inverses (bgp_cv.hip; DESIGN.md section 20)
     def cross_validate(self, B, folds):

@@ -11,8 +11,11 @@ Mirrors ``bask/acquisition.py``: the same class hierarchy (``UncertaintyAcquisit
 * ``PVRS`` / ``VarianceReduction`` replace the per-candidate (n+1)x(n+1) Cholesky loop
   (``:287-300,328-338``) by the bordered-inverse identity evaluated with tile GEMMs on the device
   (``bgp_pvrs``; SURVEY.md 3.5) -- same numbers to rounding;
-* the closed forms on (mu, std) (EI, TopTwoEI, LCB, mean, MES) are elementwise numpy on the host.
+* the closed forms on (mu, std) (EI, TopTwoEI, LCB, mean, MES) are elementwise numpy on the host;
+* ``KnowledgeGradient`` is not in the reference: the expected decrease of the minimum of the posterior mean after one more noisy
+  observation, one device call for all candidates and hyper-posterior rows (``bgp_knowledge_gradient``).
 """
+import sys
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -31,6 +34,8 @@ __all__ = [
     "ThompsonSampling",
     "VarianceReduction",
     "PVRS",
+    "KnowledgeGradient",
+    "knowledge_gradient_values",
 ]
 
 
@@ -291,3 +296,175 @@ class PVRS(FullGPAcquisition):
         thompson_sample = gp.sample_y(X, sample_mean=True, n_samples=n_thompson, random_state=random_state)
         thompson_points = X[np.argmin(thompson_sample, axis=0)]
         return _device_pvrs(gp, X, thompson_points), thompson_points
+
+
+# ---- knowledge gradient ----------------------------------------------------------------------------------
+KG_DMAX, KG_MMAX = 32, 255  # limits of the device call (bgp_kg.hip)
+KG_HOST_ROWS = 2048         # rows of [reference points; candidates] per predict(return_cov=True) of the host path
+_kg_told = []
+
+
+def _kg_tell_once(why):
+    """One line on stderr, once per process: a knowledge gradient computed on the host from ``predict(return_cov=True)``."""
+    if not _kg_told:
+        _kg_told.append(True)
+        print("[bayes_skopt_amd] knowledge_gradient: on the host from predict(return_cov=True) (%s)" % why, file=sys.stderr, flush=True)
+
+
+def knowledge_gradient_values(p, q):
+    """``min_j p_j - E[min_j (p_j + q_j Z)]``, Z ~ N(0, 1), for line arrays ``p``, ``q`` of shape (..., L): the sorted-breakpoint
+    form (Frazier, Powell & Dayanik 2009, algorithm 1, stated for the minimum).  The lines are sorted by slope (equal slopes: the
+    lower intercept stays), the lower envelope is built by one pass with a stack, and with ``c_k`` the breakpoint between the
+    envelope's lines k and k + 1 the value is ``sum_k |q_(k+1) - q_(k)| f(-|c_k|)``, ``f(z) = z Phi(z) + phi(z)``.  Returns (...)
+    values >= 0 in the units of ``p``."""
+    p, q = np.broadcast_arrays(np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64))
+    shape, L = p.shape[:-1], p.shape[-1]
+    a, b = -p.reshape(-1, L), -q.reshape(-1, L)  # E[max_j (a_j + b_j Z)] - max_j a_j
+    N = a.shape[0]
+    if N == 0 or L < 2:
+        return np.zeros(shape)
+    # slope ascending; among equal slopes the largest intercept first (the others never reach the envelope)
+    o1 = np.argsort(-a, axis=1, kind="stable")
+    o2 = np.argsort(np.take_along_axis(b, o1, axis=1), axis=1, kind="stable")
+    order = np.take_along_axis(o1, o2, axis=1)
+    a, b = np.take_along_axis(a, order, axis=1), np.take_along_axis(b, order, axis=1)
+    skip = np.zeros((N, L), dtype=bool)
+    skip[:, 1:] = b[:, 1:] == b[:, :-1]
+    stack = np.zeros((N, L), dtype=np.intp)  # envelope so far: sorted line indices, bottom = the smallest slope (z -> -inf)
+    cs = np.zeros((N, L))                    # cs[:, k]: where stack[:, k] takes over from stack[:, k - 1]
+    cs[:, 0] = -np.inf
+    top = np.zeros(N, dtype=np.intp)
+    for j in range(1, L):
+        idx = np.flatnonzero(~skip[:, j])
+        while idx.size:  # (a row leaves when its line is pushed; every pass pops one line of each row left: <= L passes per row in all)
+            t = stack[idx, top[idx]]
+            with np.errstate(invalid="ignore", over="ignore"):
+                z = (a[idx, t] - a[idx, j]) / (b[idx, j] - b[idx, t])
+            pop = z <= cs[idx, top[idx]]
+            push = idx[~pop]
+            top[push] += 1
+            stack[push, top[push]] = j
+            cs[push, top[push]] = z[~pop]
+            idx = idx[pop]
+            top[idx] -= 1
+    valid = np.arange(1, L)[None, :] <= top[:, None]
+    db = np.take_along_axis(b, stack[:, 1:], axis=1) - np.take_along_axis(b, stack[:, :-1], axis=1)
+    z = -np.abs(cs[:, 1:])
+    z = np.where(np.isinf(z), -1e300, z)  # (a breakpoint that overflowed: f is 0 there, not -inf * 0)
+    with np.errstate(over="ignore", under="ignore"):
+        f = z * ndtr(z) + np.exp(-(z * z) / 2.0) / _SQRT_2PI
+    return np.where(valid, db * f, 0.0).sum(axis=1).reshape(shape)
+
+
+def _kg_white_level(gp, theta):
+    """The white level of the kernel at ``theta`` (0 without one): what a row's fantasy observation carries beside alpha."""
+    if gp._post.canonical:
+        return float(np.exp(gp._canonical(np.atleast_2d(theta))[0, -1]))
+    from .kernels import WhiteKernel, param_for_white_kernel_in_sum
+
+    k = gp._kernel_at(theta)
+    if isinstance(k, WhiteKernel):
+        return float(k.noise_level)
+    present, name = param_for_white_kernel_in_sum(k)
+    return float(k.get_params()[name].noise_level) if present else 0.0
+
+
+def _kg_host(gp, rows, X, A, n_samples, why):
+    """The host path: per row the latent joint moments of [A; chunk] from ``predict(return_cov=True)`` (the device's predictive
+    products, the kernel on the host where it is a generic tree), the lines, ``knowledge_gradient_values``.  ``rows=None``: the
+    median GP.  Under ``warp_inputs`` a chain row is installed with its own warp, one row after the other.  Returns (m,) in y
+    units, averaged as ``evaluate_acquisitions`` averages (a row that is not all finite contributes nothing)."""
+    from ._posterior import noise_off
+
+    _kg_tell_once(why)
+    post = gp._post
+    y_std = float(np.ravel(gp.y_train_std_)[0])
+    m, M = X.shape[0], A.shape[0]
+    step = max(1, KG_HOST_ROWS - M)
+
+    def row_values(theta_row, noise):
+        out = np.zeros(m)
+        for lo in range(0, m, step):
+            Q = np.vstack([A, X[lo : lo + step]])
+            if theta_row is None and post.canonical:
+                post.make_resident(gp)
+                mean, var, cov = gp._ctx.predict(noise_off(gp._canonical(gp._kernel_theta_for_predict())), Q, return_cov=True)
+            else:
+                mean, var, cov = post.rows_predict(gp, theta_row, Q, noise_zero=True, return_cov=True)
+            mean, var, cov = mean[0], var[0], cov[0]
+            v = var[M:]
+            s = v + noise
+            ok = s > 0.0
+            if not ok.any():
+                continue
+            rs = 1.0 / np.sqrt(s[ok])
+            pl = np.concatenate([np.broadcast_to(mean[:M], (int(ok.sum()), M)), mean[M:][ok][:, None]], axis=1)
+            ql = np.concatenate([cov[:M, M:].T[ok], v[ok][:, None]], axis=1) * rs[:, None]
+            out[lo + np.flatnonzero(ok)] = np.maximum(knowledge_gradient_values(pl, ql), 0.0) * y_std
+        return out
+
+    base = gp._fantasy_base_alpha()
+    if rows is None:
+        return row_values(None, base + _kg_white_level(gp, gp._post_theta))
+    total = np.zeros(m)
+    n_theta = len(gp.kernel_.theta)
+    saved = (gp._post_theta, gp.alpha_)
+    try:
+        if gp.warp_inputs:
+            with gp._row_warps() as install:
+                vals = [row_values(install(r), base + _kg_white_level(gp, r[:n_theta])) for r in rows]
+        else:
+            vals = [row_values(r[None, :], base + _kg_white_level(gp, r)) for r in rows]
+    finally:
+        gp._post_theta, gp.alpha_ = saved
+    for v in vals:
+        if np.all(np.isfinite(v)):
+            total += v / n_samples
+    return total
+
+
+class KnowledgeGradient(FullGPAcquisition):
+    """Knowledge gradient for minimisation under noise (Frazier, Powell & Dayanik 2009; Scott, Frazier & Powell 2011): how much one
+    more noisy observation at x is expected to lower the minimum of the posterior MEAN over a reference set and x itself,
+    ``KG(x) = min_j mu(a_j) - E[min_j mu_+(a_j)]`` -- the quantity ``expected_optimum`` reports at the end of a noisy run.
+
+    ``reference_points`` (M, d), or by default the ``min(n_reference, m)`` candidates of lowest posterior mean under the median GP
+    (stable argsort); every row shares them.  ``n_gp_samples = 0``: the median GP; ``n_gp_samples > 0``: the average over that many
+    chain rows drawn without replacement from ``random_state``, ONE batched posterior build and ONE device call
+    (``bgp_knowledge_gradient``).  The observation at x carries the noise a ``tell`` with noise 0 would give
+    it (the scalar alpha + the row's white level).  Values in y units, >= 0.  Generic kernel trees, ``warp_inputs=True``, more than
+    32 dimensions or more than 255 reference points: the host path (``knowledge_gradient_values`` on ``predict(return_cov=True)``),
+    said once on stderr.  ``return_path``: also "device" | "host"."""
+
+    path = "auto"  # "host": always the host path (tests compare the two)
+
+    def __call__(self, X, gp, *args, n_reference=63, reference_points=None, n_gp_samples=0, random_state=None, return_path=False,
+                 **kwargs):
+        from ._posterior import noise_off
+
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        m, d = X.shape
+        if reference_points is None:
+            mean = np.asarray(gp._post.predict(gp, X, False)[0])[0]
+            A = X[np.argsort(mean, kind="stable")[: max(0, min(int(n_reference), m))]]
+        else:
+            A = np.asarray(reference_points, dtype=np.float64).reshape(-1, d)
+        rows = None
+        if n_gp_samples > 0:
+            rng = check_random_state(random_state)
+            rows = gp.chain_[rng.choice(len(gp.chain_), replace=False, size=int(n_gp_samples))]
+        why = ("forced" if self.path == "host" else "generic kernel tree" if not gp._post.canonical else "input warping"
+               if gp.warp_inputs else "more than 32 dimensions" if d > KG_DMAX else "more than 255 reference points"
+               if len(A) > KG_MMAX else None)
+        if why is not None:
+            vals = _kg_host(gp, rows, X, A, max(int(n_gp_samples), 1), why)
+            return (vals, "host") if return_path else vals
+        y_std = float(np.ravel(gp.y_train_std_)[0])
+        if rows is None:
+            gp._post.make_resident(gp)
+            H = gp._canonical(gp._post_theta)
+        else:
+            H = gp._post.build_rows(gp, rows)
+        noise = gp._fantasy_base_alpha() + np.exp(H[:, -1])
+        vals = gp._ctx.knowledge_gradient(noise_off(H), noise, X, A, y_std, len(H), want_rows=False)[1]
+        return (vals, "device") if return_path else vals

@@ -23,6 +23,7 @@ __all__ = ["Optimizer"]
 
 ACQUISITION_FUNC = {
     "ei": acquisition.ExpectedImprovement(),
+    "kg": acquisition.KnowledgeGradient(),
     "lcb": acquisition.LCB(),
     "mean": acquisition.Expectation(),
     "mes": acquisition.MaxValueSearch(),

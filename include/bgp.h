@@ -109,7 +109,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -382,6 +382,26 @@ int bgp_sobol_indices(bgp_ctx* ctx, int B, const double* h_kernel, int N, const 
 int bgp_grad_cov(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* dmean, double* cov, double* csum);
 
 /*
+ * Knowledge-gradient acquisition (csrc/bgp_kg.hip) of the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as
+ * in bgp_acq_batch: the white level at -inf, the latent function) at the m candidates Xcand (m*d, row-major) against the M reference
+ * points Xref (M*d; not read at M = 0).  noise (B): the variance of a fantasy observation per posterior, as bgp_fantasy_begin takes
+ * it (constructor alpha + the row's white level).  In normalised-y units, for minimisation, with s = var_b(x) + noise_b and the
+ * M + 1 lines  p_j = mu_b(a_j), q_j = cov_b(a_j, x) / sqrt(s)  (j < M),  p_M = mu_b(x), q_M = var_b(x) / sqrt(s)  (latent moments):
+ *   KG_b(x) = min_j p_j - E_Z[min_j (p_j + q_j Z)],  Z ~ N(0, 1)      kg   B*m   y_std KG_b(x_i)
+ *                                                                     avg  m     sum over b, ascending, of kg[b][i] / n_samples
+ * clipped at 0, exactly 0 where s <= 0 and at M = 0.  A posterior whose values are not all finite contributes nothing to avg (the
+ * rule of bgp_acq_batch).  Either output may be NULL, not both.  Lines of equal slope: the lower intercept wins; exact duplicates:
+ * the lower index.  The product k_b(x, X) (K_b^-1 k_b(X, A)) runs on the fp64 MFMA ring; every sum has a fixed order: a candidate's
+ * value is the same bits whatever m and B are, whatever else shares the call and however the call is chunked.
+ * Needs d <= 32, 0 <= M <= 255, 1 <= m <= 2^24, 1 <= B <= 65535, 1 <= n_samples and no context-level warp: BGP_ERR_INVALID before
+ * anything is launched; B resident posteriors that are not per-row warped: BGP_ERR_STATE.  A refused call leaves the resident
+ * posteriors as they were; a successful one does not change them either.
+ *   Replaces: nothing in the reference -- it has no acquisition that looks at the minimum of the posterior mean.
+ */
+int bgp_knowledge_gradient(bgp_ctx* ctx, int B, const double* h_kernel, const double* noise, int m, const double* Xcand, int M,
+                           const double* Xref, double y_std, int n_samples, double* kg, double* avg);
+
+/*
  * Cross-validation from the resident inverses (csrc/bgp_cv.hip): for each of the first B resident posteriors
  * and each fold F (fold f holds the training indices fold_idx[fold_ptr[f] .. fold_ptr[f + 1])), the predictive of the held-out
  * OBSERVATIONS y_F given all the other ones, without a refit.  With A = K^-1 (K with the alpha diagonal and the white level) and
@@ -468,7 +488,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   at the head of their ticket list; default by shape), BGP_SYRK_GEN (0 / 1: on the launch schedule, every Gram block by the
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
- *   256; default by n and d; read at every call).
+ *   256; default by n and d; read at every call), BGP_KG_CHUNK (candidates per chunk of bgp_knowledge_gradient, rounded up to 128;
+ *   default by n; read at every call).
  * Runtime switch set by the PYTHON package, not read by this library: bayes-skopt_amd/_lib.py exports HIP_FORCE_DEV_KERNARG=1 (kernel
  *   arguments in device memory: -6 % per call on the launch schedule at n = 1024 x 32) at import unless the user has set it --
  *   a process-wide setting that every other HIP user of the process inherits, effective only if the GPU has not been initialised
