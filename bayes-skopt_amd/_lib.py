@@ -115,6 +115,7 @@ SIGNATURES = {
     "bgp_paths_end": (C.c_int, [_vp]),
     "bgp_paths_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_paths_minimize": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "bgp_paths_select": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_int, _ip, _dp, _dp]),
     "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
@@ -244,6 +245,8 @@ def device_identity(device=0):
 ACQ_EI, ACQ_MEAN, ACQ_LCB, ACQ_STD = 0, 1, 2, 3  # include/bgp.h BGP_ACQ_*
 ACQ_MAX = 8
 BGP_LIE_VALUE, BGP_LIE_KB = 0, 1  # include/bgp.h BGP_LIE_* (bgp_fantasy_step)
+SELECT_KINDS = {"improvement": 0, "thompson": 1}  # include/bgp.h BGP_SELECT_* (bgp_paths_select)
+SELECT_MAX_DOUBLES = 1 << 27  # include/bgp.h BGP_SELECT_MAX_DOUBLES: the resident draw matrix, paths x candidates padded to 256
 MCMC_FORMS = ("step_lds", "step_hbm", "fused")  # include/bgp.h bgp_mcmc_form
 
 
@@ -870,6 +873,33 @@ class Context:
                                             _p(grad) if want_grad else C.cast(None, _dp), _p(iters), _p(evals), _p(status)),
                "bgp_paths_minimize")
         return {"x": x, "fun": fun, "grad": grad, "iters": iters, "evals": evals, "status": status}
+
+    def paths_select(self, Xcand, q, kind="improvement", incumbent=None, forced=(), want_values=True, want_incumbents=True):
+        """``bgp_paths_select``: ``q`` greedy picks among the rows of ``Xcand`` on the joint draw of the open
+        paths, in normalised-y units.  ``kind``: "improvement" (Monte-Carlo q-EI gains) or "thompson" (step j is path j mod P's
+        minimiser).  ``incumbent``: None -- every path's own minimum over the training inputs -- or a number, the same for every path.
+        ``forced``: candidate indices taken as chosen before the first step.  Returns (picks (q,), values (q, m) | None, incumbents
+        (P,) | None).  ``ValueError`` when paths x candidates (padded to 256) exceed ``SELECT_MAX_DOUBLES``."""
+        Xcand = _c(np.atleast_2d(Xcand))
+        if Xcand.shape[1] != self.d:
+            raise ValueError(f"candidates must have {self.d} columns, got {Xcand.shape[1]}")
+        if isinstance(kind, str) and kind not in SELECT_KINDS:
+            raise ValueError(f"kind must be one of {tuple(SELECT_KINDS)}, got {kind!r}")
+        kind = SELECT_KINDS[kind] if isinstance(kind, str) else int(kind)  # (a number goes to the C layer as it is)
+        P, m, q = self._paths_P, Xcand.shape[0], int(q)
+        if P * (-(-m // 256) * 256) > SELECT_MAX_DOUBLES:
+            raise ValueError(f"{P} paths x {m} candidates exceed the {SELECT_MAX_DOUBLES} doubles of the resident draw matrix")
+        forced = np.ascontiguousarray(forced, dtype=np.int32).ravel()
+        picks = np.full(max(q, 0), -1, dtype=np.int32)
+        values = np.empty((max(q, 0), m)) if want_values else None
+        inc = np.empty(P) if want_incumbents else None
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_paths_select(self._h, m, _p(Xcand), kind, 0 if incumbent is not None else 1,
+                                          float(incumbent) if incumbent is not None else 0.0, len(forced),
+                                          _p(forced) if len(forced) else C.cast(None, _ip), q, _p(picks),
+                                          _p(values) if want_values else null, _p(inc) if want_incumbents else null),
+               "bgp_paths_select")
+        return picks, values, inc
 
     def paths_end(self):
         self._paths_P = 0

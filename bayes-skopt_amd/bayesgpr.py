@@ -1360,6 +1360,31 @@ class PosteriorPaths:
         return {"x": out["x"][rows, best], "fun": fun_all[rows, best], "x_all": out["x"], "fun_all": fun_all,
                 "status": out["status"], "iters": out["iters"], "evals": out["evals"], "best": best}
 
+    def select_batch(self, X, q, kind="improvement", incumbent="paths", forced=(), return_values=False):
+        """``q`` rows of ``X`` picked greedily on the JOINT draw of the paths over {training inputs, rows of X}, on the device
+        (``bgp_paths_select``); the draw matrix does not leave it.  ``kind="improvement"``: step j picks the
+        row that adds most to the Monte-Carlo q-EI ``mean_s max(0, c_s - min_{k chosen} f_s(x_k))`` -- greedy on a monotone
+        submodular set function --, ties to the lower index; ``incumbent="paths"``: c_s is path s's own minimum over the training
+        inputs (the incumbent of noisy EI: uncertain, and integrated over whatever hyper-posterior rows the paths carry); a
+        number: that value, in y units, for every path.  ``kind="thompson"``: step j picks path ``j mod n_paths``'s lowest row
+        among those left.  ``forced``: row indices taken as chosen before the first step (points under evaluation): they lower
+        the incumbents and are never picked.  Returns a dict: ``picks`` (q,), ``incumbents`` (n_paths,) in y units (before the
+        forced rows lower them) and ``values`` (q, m) in y units -- the step's gain of every row, or ``-f`` of the step's path
+        for Thompson; chosen rows included -- or None without ``return_values``."""
+        X = self._X(X)
+        if kind not in _lib.SELECT_KINDS:
+            raise ValueError("kind must be one of %r, got %r" % (tuple(_lib.SELECT_KINDS), kind))
+        if isinstance(incumbent, str):
+            if incumbent != "paths":
+                raise ValueError("incumbent must be 'paths' or a number in y units, got %r" % (incumbent,))
+            inc = None
+        else:
+            inc = (float(incumbent) - self._y_mean) / self._y_std
+        picks, values, incs = self._ctx.paths_select(X, q, kind=kind, incumbent=inc, forced=forced, want_values=return_values)
+        if values is not None:
+            values = self._y_std * values if kind == "improvement" else -(self._y_std * (-values) + self._y_mean)
+        return {"picks": picks.astype(np.intp), "values": values, "incumbents": self._y_std * incs + self._y_mean}
+
     def close(self):
         ctx, self._ctx = self._ctx, None
         if ctx is not None:

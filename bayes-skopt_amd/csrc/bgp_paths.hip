@@ -21,18 +21,13 @@
 #include "bgp_common.h"
 #include "bgp_device.h"
 #include "bgp_bfgs.h"
+#include "bgp_paths_int.h"
 
 #define PT_TF 64       // features per LDS tile of the feature kernel
 #define PT_TP 64       // training points per LDS tile of the update kernel
 #define PT_DMAX 32     // input dimensions held in registers
 #define PT_FMAX 65536  // features per path
 #define PT_PMAX 65535  // paths per state (a grid dimension)
-
-struct bgp_paths_state {
-  int P = 0, F = 0, n = 0, d = 0;
-  BgpDev<char> mem;  // one allocation, carved by bgp_paths_begin
-  double *dX, *dH, *dOm, *dPh, *dAw, *dC0, *dV;
-};
 
 static void paths_free(bgp_ctx* c) {
   if (!c->paths) return;
@@ -435,9 +430,27 @@ extern "C" int bgp_paths_begin(bgp_ctx* c, int P, const int* pidx, const double*
   return post_call(c, [&] { return paths_begin_run(c, P, pidx, h_kernel, s2, F, omega, phase, w, eps); });
 }
 
+// f0 + the update at device rows (bgp_paths_int.h): what bgp_paths_eval launches per chunk, and bgp_paths_select for its matrix
+int bgp_paths_launch_eval(bgp_ctx* c, const bgp_paths_state* s, const double* dXq, int m, double* out, size_t so, double* dout) {
+  BGP_TRY(paths_launch_feat(c, s, dXq, m, out, so, dout));
+  const int n = s->n, d = s->d;
+  const dim3 grid((m + 255) / 256, s->P);
+  hipStream_t q = c->stream;
+  if (dout)
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((paths_upd_kernel<S, F, 1>), grid, dim3(256), 0, q, s->dX, n, d, dXq, m, s->dH, s->dV, out, so,
+                                   dout));
+  else
+    KB_DISPATCH(c->ks.stationary, c->ks.form,
+                hipLaunchKernelGGL((paths_upd_kernel<S, F, 0>), grid, dim3(256), 0, q, s->dX, n, d, dXq, m, s->dH, s->dV, out, so,
+                                   dout));
+  BGP_HIP(hipGetLastError());
+  return BGP_OK;
+}
+
 static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, double* dout) {
   const bgp_paths_state* s = c->paths;
-  const int P = s->P, d = s->d, n = s->n;
+  const int P = s->P, d = s->d;
   // chunks of query rows: staged outputs of P mc (1 + d) doubles under the budget of the prediction gradients (2^24 doubles)
   size_t mc = std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)P * (1 + (size_t)d)));
   if (mc >= 256) mc &= ~(size_t)255;
@@ -454,17 +467,7 @@ static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, doub
   for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
     const int mm = (int)std::min(mc, (size_t)m - m0);
     BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, q));
-    BGP_TRY(paths_launch_feat(c, s, dXq, mm, dO, mc, dG));
-    const dim3 grid((mm + 255) / 256, P);
-    if (dout)
-      KB_DISPATCH(c->ks.stationary, c->ks.form,
-                  hipLaunchKernelGGL((paths_upd_kernel<S, F, 1>), grid, dim3(256), 0, q, s->dX, n, d, dXq, mm, s->dH, s->dV, dO, mc,
-                                     dG));
-    else
-      KB_DISPATCH(c->ks.stationary, c->ks.form,
-                  hipLaunchKernelGGL((paths_upd_kernel<S, F, 0>), grid, dim3(256), 0, q, s->dX, n, d, dXq, mm, s->dH, s->dV, dO, mc,
-                                     dG));
-    BGP_HIP(hipGetLastError());
+    BGP_TRY(bgp_paths_launch_eval(c, s, dXq, mm, dO, mc, dG));
     const size_t w1 = (size_t)mm * sizeof(double), wd = w1 * d;
     BGP_HIP(bgp_memcpy2d_async(out + m0, (size_t)m * sizeof(double), dO, mc * sizeof(double), w1, P, hipMemcpyDeviceToHost, q));
     if (dout)

@@ -35,6 +35,7 @@ ACQUISITION_FUNC = {
 
 _INT32_MAX = np.iinfo(np.int32).max
 BATCH_STRATEGIES = ("cl_min", "cl_mean", "cl_max", "kb")
+JOINT_STRATEGIES = ("joint_ei", "thompson")  # batches picked on joint pathwise draws (PosteriorPaths.select_batch)
 
 
 class Optimizer:
@@ -86,7 +87,7 @@ class Optimizer:
         return create_result(self.Xi, self.yi, self.space, self.rng, models=[self.gp])
 
     # ---- ask ---------------------------------------------------------------------------------------------------
-    def ask(self, n_points=1, strategy="cl_min"):
+    def ask(self, n_points=1, strategy="cl_min", pending=None, n_paths=256, n_features=1024):
         """Next point to evaluate (``bask/optimizer.py:177-226``): a point of the initial design while it lasts, then
         the maximiser of the acquisition function found by the last ``tell``.
 
@@ -109,10 +110,29 @@ class Optimizer:
           generator state the proposal handed it.  ``n_points`` may not exceed the number of candidates.  This does not
           consume ``rng`` and changes nothing on the optimizer: asking twice gives the same list, and telling the first
           point alone continues exactly as after ``ask()``.  Sample acquisitions (Thompson sampling, "ts") have no
-          batch form.
+          batch form under these strategies.
+
+        ``strategy="joint_ei" | "thompson"`` builds the batch, for every acquisition function, on ONE
+        joint draw of ``n_paths`` posterior functions of ``n_features`` random features each
+        (``gp.sample_paths(n_paths, sample_mean=False, ...)``: every path with its own hyper-posterior row) over the training
+        inputs and the candidates of the last proposal, instead of on a lie: "joint_ei" adds, step by step, the candidate that
+        raises the Monte-Carlo q-EI most, each path's incumbent being its own minimum over the training inputs (noisy EI);
+        "thompson" gives step j to path j's minimiser among the candidates left.  Point 1 is ``ask()``, the other points are
+        the greedy picks given it.  ``pending``: points (original space) that are being evaluated right now; with it only
+        those points are taken as chosen -- a pending point that is a candidate row by its index, any other appended to the
+        candidates --, no returned point is one of them, and ``n_points == 1`` still returns a single point.  The paths are
+        seeded from a copy of ``rng``'s state: ``rng`` is not consumed and asking twice gives the same list.  Where
+        ``sample_paths`` cannot run (input warping, generic kernel trees, more than 32 dimensions) its ``ValueError`` passes
+        through.  ``pending`` with any other strategy is a ``ValueError``.
         """
-        if n_points > 1 and strategy not in BATCH_STRATEGIES:
-            raise ValueError(f"strategy must be one of {BATCH_STRATEGIES}, got {strategy!r}")
+        joint = strategy in JOINT_STRATEGIES
+        if pending is not None and not joint:
+            raise ValueError(f"pending points need a joint strategy {JOINT_STRATEGIES}, got {strategy!r}")
+        if n_points > 1 and not joint and strategy not in BATCH_STRATEGIES:
+            raise ValueError(f"strategy must be one of {BATCH_STRATEGIES + JOINT_STRATEGIES}, got {strategy!r}")
+        if joint and (n_points > 1 or pending is not None) and self._n_initial_points <= 0 and self.gp.kernel_:
+            points = self._ask_joint(n_points, strategy, pending, n_paths, n_features)
+            return points if n_points > 1 else points[0]
         if n_points > 1:
             if self._n_initial_points > 0 or not self.gp.kernel_:
                 return self._ask_design(n_points)
@@ -168,6 +188,43 @@ class Optimizer:
             path=self._batch_path, want_moments=self._batch_moments)
         self._last_batch_info = dict(info, picks=picks, values=step_values, path=path)
         return [self.space.inverse_transform(cand[i].reshape((1, -1)))[0] for i in picks]
+
+    def _ask_joint(self, n_points, strategy, pending, n_paths, n_features):
+        """Batch on joint pathwise draws over the last proposal's candidates (``PosteriorPaths.select_batch``); a list."""
+        if self._last_candidates is None:
+            raise RuntimeError("No proposal to extend: tell() has not fit a model and proposed a point yet.")
+        cand = self._last_candidates
+        if pending is None:
+            forced = [int(np.argmax(self._last_acq_values))]
+        else:
+            pend = self.space.transform([list(p) for p in pending]) if len(pending) else np.empty((0, cand.shape[1]))
+            # a pending point is a candidate when it is the point ask() would return for that row, or transforms to the row itself
+            known = {}
+            for i, x in enumerate(self.space.inverse_transform(cand)):
+                known.setdefault(tuple(x), i)
+            forced, extra = [], []
+            for x, row in zip(pending, np.atleast_2d(pend)):
+                hit = [known[tuple(x)]] if tuple(x) in known else list(np.flatnonzero(np.all(cand == row[None, :], axis=1)))
+                hit = [int(i) for i in hit if int(i) not in forced]
+                if hit:
+                    forced.append(hit[0])
+                else:
+                    forced.append(len(cand) + len(extra))
+                    extra.append(row)
+            if extra:
+                cand = np.vstack([cand, np.asarray(extra, dtype=np.float64)])
+        q = n_points - (1 if pending is None else 0)
+        if q + len(forced) > len(cand):
+            raise ValueError(f"n_points={n_points} exceeds the {len(cand)} candidates of a proposal (Optimizer.n_points)")
+        clone = np.random.RandomState()
+        clone.set_state(self.rng.get_state())
+        with self.gp.sample_paths(n_paths=n_paths, sample_mean=False, n_features=n_features, random_state=clone) as paths:
+            out = paths.select_batch(cand, q, kind="improvement" if strategy == "joint_ei" else "thompson",
+                                     incumbent="paths", forced=forced, return_values=True)
+        chosen = ([] if pending is not None else forced) + [int(i) for i in out["picks"]]
+        self._last_batch_info = dict(picks=chosen, values=out["values"], incumbents=out["incumbents"], path="pathwise",
+                                     forced=list(forced), candidates=cand)
+        return [self.space.inverse_transform(cand[i].reshape((1, -1)))[0] for i in chosen]
 
     # ---- tell --------------------------------------------------------------------------------------------------
     def _record(self, x, y, noise_vector):

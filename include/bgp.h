@@ -318,6 +318,38 @@ int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, 
                        double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status);
 
 /*
+ * Joint batch selection on the open paths (csrc/bgp_paths_select.hip): q candidates picked greedily on the
+ * joint draw of the P paths over {training inputs, candidates}, instead of one fantasy "lie" per point (bgp_fantasy_*).  Serves
+ * Optimizer.ask(n_points > 1) (bask/optimizer.py:177-226, where the reference has no batch at all) with strategy "joint_ei" /
+ * "thompson", and gives the Thompson draws of evaluate_acquisitions (bask/acquisition.py:132-136) a batch form.
+ * The P paths are evaluated at the m candidates Xcand (m*d, row-major) into a device matrix F[s, i] by the launches of
+ * bgp_paths_eval (the same bits), normalised-y units.  Incumbent of path s, c_s: incumbent = 0: the scalar y_opt; incumbent = 1: the
+ * path's own minimum over the n training inputs (the same evaluator on the state's copy of them; min is exact): the incumbent of
+ * "noisy EI", one per draw of function AND hyper-parameters.  inc_out (P, may be NULL) receives these c_s, before any candidate lowers
+ * them.  Then the n_forced candidates forced[k] (points under evaluation; each index once) are applied in order: c_s = min(c_s,
+ * F[s, forced[k]]), candidate marked chosen.  Then q greedy steps, j = 0 .. q - 1, without host synchronisation in between:
+ *   kind = BGP_SELECT_IMPROVEMENT:  a_j(i) = (sum over s = 0 .. P - 1, ASCENDING, of max(0, c_s - F[s, i])) / P
+ *       -- rounded differences, added one by one to a running sum that starts at 0, one division at the end, no contraction: the
+ *       order is part of the contract, the same for every m, q and P (no chunking).  pick_j = the unchosen i of largest a_j(i), ties
+ *       to the lowest index (np.argmax's order, bgp_fantasy_step's); then c_s = min(c_s, F[s, pick_j]).  a_j(i) is the gain of the
+ *       Monte-Carlo q-EI  mean_s max(0, inc_s - min_{k in chosen} F[s, k])  when i joins the chosen set; a chosen candidate, or a row
+ *       equal to one, has value exactly 0 at every later step, and a candidate's values never increase from step to step.
+ *   kind = BGP_SELECT_THOMPSON:     a_j(i) = -F[j mod P, i];  pick_j = the unchosen argmax, same tie rule; c is not used (inc_out
+ *       is still written).
+ * picks: q indices.  values: q*m (may be NULL), row j = a_j over ALL candidates, chosen ones included.  a_j(i) depends on column i
+ * of F and on c alone: not on the other candidates, nor on m.  Picks, values and incumbents come back in one transfer at the end.
+ * F lives in one owned allocation for the duration of the call: P * mpad doubles, mpad = m rounded up to 256, at most
+ * BGP_SELECT_MAX_DOUBLES (1 GiB) -- BGP_ERR_INVALID beyond, checked before anything is read.  BGP_ERR_INVALID also for: kind or
+ * incumbent out of range, m < 1, q < 1, n_forced < 0, q + n_forced > m, a forced index outside [0, m) or repeated, a non-finite y_opt
+ * with incumbent = 0.  BGP_ERR_STATE without a paths state.  Neither the paths state nor the resident posteriors are modified.
+ */
+#define BGP_SELECT_IMPROVEMENT 0
+#define BGP_SELECT_THOMPSON 1
+#define BGP_SELECT_MAX_DOUBLES ((size_t)1 << 27)
+int bgp_paths_select(bgp_ctx* ctx, int m, const double* Xcand, int kind, int incumbent, double y_opt, int n_forced,
+                     const int* forced, int q, int* picks, double* values, double* inc_out);
+
+/*
  * Partial dependence of the surrogate mean on one or two input dimensions: the data of the "plot objective"
  * figure, for the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read: cross
  * values carry none).  With S sample rows Xs (S*d) and a panel D = {k1} or {k1, k2} with grid values g (normalised-y units):
