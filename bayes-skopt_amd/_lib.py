@@ -123,6 +123,7 @@ SIGNATURES = {
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "bgp_knowledge_gradient": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_int, _dp, _dp]),
+    "bgp_joint_entropy": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
@@ -800,6 +801,33 @@ class Context:
         _check(self._lib.bgp_knowledge_gradient(self._h, B, _p(H), _p(noise), m, _p(Xc), M, _p(Xr) if M else null, float(y_std),
                                                 int(n_samples), _p(kg) if want_rows else null, _p(avg)), "bgp_knowledge_gradient")
         return kg, avg
+
+    # ---- joint entropy search acquisition (bgp_jes.hip)
+    def joint_entropy(self, H_kernel, noise, Xcand, Xopt, fopt, tau, n_samples, want_rows=True):
+        """``bgp_joint_entropy``: for the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2), white level at -inf) the moment-matched
+        drop of the entropy of an observation (variance ``var(x) + noise[b]``) at each row of ``Xcand`` (m, d) once the optimum is
+        known, averaged over posterior b's OWN optimum samples ``Xopt`` (B, R, d) / ``fopt`` (B, R), 1 <= R <= 255; ``tau`` >= 0 is
+        the jitter on the noiseless optimum observation.  Returns ``(gain (B, m) | None, avg (m,))`` in nats; ``avg`` adds the rows
+        in order, each divided by ``n_samples``.  Needs d <= 32 and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        noise = _c(np.asarray(noise, dtype=np.float64).reshape(B))
+        Xc = _c(np.atleast_2d(Xcand))
+        if Xc.shape[1] != self.d:
+            raise ValueError(f"candidates must have {self.d} columns, got {Xc.shape[1]}")
+        fo = _c(np.asarray(fopt, dtype=np.float64).reshape(B, -1))
+        R = fo.shape[1]
+        Xo = np.asarray(Xopt, dtype=np.float64)
+        if Xo.size != B * R * self.d:
+            raise ValueError(f"optimum points must be ({B}, {R}, {self.d}), got {Xo.shape}")
+        Xo = _c(Xo.reshape(B, R, self.d))
+        m = Xc.shape[0]
+        gain = np.empty((B, m)) if want_rows else None
+        avg = np.empty(m)
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_joint_entropy(self._h, B, _p(H), _p(noise), m, _p(Xc), R, _p(Xo), _p(fo), float(tau), int(n_samples),
+                                           _p(gain) if want_rows else null, _p(avg)), "bgp_joint_entropy")
+        return gain, avg
 
     # ---- cross-validation from the resident inverses (bgp_cv.hip; DESIGN.md section 20)
     def cross_validate(self, B, folds):

@@ -13,7 +13,10 @@ Mirrors ``bask/acquisition.py``: the same class hierarchy (``UncertaintyAcquisit
   (``bgp_pvrs``; SURVEY.md 3.5) -- same numbers to rounding;
 * the closed forms on (mu, std) (EI, TopTwoEI, LCB, mean, MES) are elementwise numpy on the host;
 * ``KnowledgeGradient`` is not in the reference: the expected decrease of the minimum of the posterior mean after one more noisy
-  observation, one device call for all candidates and hyper-posterior rows (``bgp_knowledge_gradient``).
+  observation, one device call for all candidates and hyper-posterior rows (``bgp_knowledge_gradient``, DESIGN.md section 23);
+* ``JointEntropySearch`` is not in the reference either: the expected drop of the entropy of an observation once the optimum's
+  location AND value are known, on optimum samples found continuously on the device (``PosteriorPaths.minimize``), one device call
+  for all candidates and hyper-posterior rows (``bgp_joint_entropy``).
 """
 import sys
 from abc import ABC, abstractmethod
@@ -36,6 +39,8 @@ __all__ = [
     "PVRS",
     "KnowledgeGradient",
     "knowledge_gradient_values",
+    "JointEntropySearch",
+    "joint_entropy_values",
 ]
 
 
@@ -467,4 +472,188 @@ class KnowledgeGradient(FullGPAcquisition):
             H = gp._post.build_rows(gp, rows)
         noise = gp._fantasy_base_alpha() + np.exp(H[:, -1])
         vals = gp._ctx.knowledge_gradient(noise_off(H), noise, X, A, y_std, len(H), want_rows=False)[1]
+        return (vals, "device") if return_path else vals
+
+
+# ---- joint entropy search --------------------------------------------------------------------------------
+JES_DMAX, JES_RMAX = 32, 255  # limits of the device call (bgp_jes.hip)
+JES_F_SWITCH, JES_F_DEPTH = 4.0, 40  # F: the definition below the switch point, the continued fraction (cut at this numerator) from it on
+JES_NOISE_FLOOR = 1e-12
+_jes_told, _jes_floor_told = [], []
+
+
+def _jes_tell_once(why):
+    """One line on stderr, once per process: a joint entropy search computed on the host from ``predict(return_cov=True)``."""
+    if not _jes_told:
+        _jes_told.append(True)
+        print("[bayes_skopt_amd] joint_entropy: on the host from predict(return_cov=True) (%s)" % why, file=sys.stderr, flush=True)
+
+
+def _jes_F_direct(z):
+    """``1 - lam (lam - z)``, ``lam = sqrt(2 / pi) / erfcx(z / sqrt 2)``: loses ``eps z^4`` for large positive z."""
+    from scipy.special import erfcx
+
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        lam = np.sqrt(2.0 / np.pi) / erfcx(z * np.sqrt(0.5))
+        return 1.0 - lam * (lam - z)
+
+
+def _jes_F_cf(z, depth=JES_F_DEPTH):
+    """``T (U - T)`` with ``T = 1 / (z + U)``, ``U = 2 / (z + 3 / (z + ... depth / z))`` (Laplace's continued fraction of the Mills
+    ratio; z > 0), U bottom-up as a ratio scaled by 1 / z: ``N_k = k D_{k+1} / z``, ``D_k = D_{k+1} + N_{k+1} / z``."""
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        rz = 1.0 / z
+        N, D = np.zeros_like(z), np.ones_like(z)
+        for k in range(depth, 1, -1):
+            N, D = (k * rz) * D, D + rz * N
+        U = N / D
+        T = 1.0 / (z + U)
+        return T * (U - T)
+
+
+def _jes_F(z):
+    """The variance factor of a normal truncated below at z, ``1 - lam (lam - z)`` with ``lam = phi(z) / Phi(-z)``: the definition
+    for z < 4, the continued fraction from 4 on (a function of z alone; bgp_jes.hip takes the same two forms)."""
+    z = np.asarray(z, dtype=np.float64)
+    big = z >= JES_F_SWITCH
+    return np.where(big, _jes_F_cf(np.where(big, z, JES_F_SWITCH)), _jes_F_direct(np.where(big, 0.0, z)))
+
+
+def joint_entropy_values(mu, var, mu_opt, var_opt, cov, f_opt, noise, tau):
+    """The joint-entropy-search gain (nats, >= 0) of candidates with latent moments ``mu``, ``var`` (..., m) given R samples of the
+    optimum with latent moments ``mu_opt``, ``var_opt`` and values ``f_opt`` (..., R) and cross-covariances ``cov`` (..., m, R):
+    each sample conditions on ``f(a_r) = f_r`` (jitter ``tau``; nothing where ``var_opt + tau <= 0``), truncates ``f(x) >= f_r``
+    (``v_t = clip(v_s F(z), 0, v_s)``, 0 where ``v_s <= 0``) and contributes ``1/2 [log(v + noise) - log(v_t + noise)]`` clipped at
+    0; the mean over the samples.  Everything in normalised-y units; ``noise`` > 0 is the variance of an observation."""
+    mu, var = np.asarray(mu, dtype=np.float64)[..., None], np.asarray(var, dtype=np.float64)[..., None]
+    mo, vo, fo = (np.asarray(a, dtype=np.float64)[..., None, :] for a in (mu_opt, var_opt, f_opt))
+    c = np.asarray(cov, dtype=np.float64)
+    nu = np.asarray(noise, dtype=np.float64)[..., None, None]
+    w = vo + tau
+    on = w > 0.0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ws = np.where(on, w, 1.0)
+        mr = mu + np.where(on, c * ((fo - mo) / ws), 0.0)
+        vs = np.maximum(var - np.where(on, c * c / ws, 0.0), 0.0)
+        pos = vs > 0.0
+        z = (fo - mr) / np.sqrt(np.where(pos, vs, 1.0))
+        vt = np.where(pos, np.clip(vs * _jes_F(z), 0.0, vs), 0.0)
+        g = np.maximum(0.5 * (np.log(var + nu) - np.log(vt + nu)), 0.0)
+    return g.mean(axis=-1)
+
+
+def _jes_noise(gp, whites):
+    """The variance of an observation per row, ``_fantasy_base_alpha() + white``, floored at 1e-12 (said once if the floor bites)."""
+    noise = gp._fantasy_base_alpha() + np.asarray(whites, dtype=np.float64)
+    if np.any(noise < JES_NOISE_FLOOR) and not _jes_floor_told:
+        _jes_floor_told.append(True)
+        print("[bayes_skopt_amd] joint_entropy: observation noise below %g, floored there" % JES_NOISE_FLOOR, file=sys.stderr, flush=True)
+    return np.maximum(noise, JES_NOISE_FLOOR)
+
+
+def _jes_host(gp, rows, X, A, f, tau, n_samples, why):
+    """The host path: per row the latent joint moments of [A_b; chunk] from ``predict(return_cov=True)`` and
+    ``joint_entropy_values``, row by row as ``_kg_host``.  ``A`` (B, R, d), ``f`` (B, R) in normalised-y units; ``rows=None``: the
+    median GP.  Returns (m,) in nats, averaged as ``evaluate_acquisitions`` averages."""
+    from ._posterior import noise_off
+
+    _jes_tell_once(why)
+    post = gp._post
+    m, R = X.shape[0], A.shape[1]
+    step = max(1, KG_HOST_ROWS - R)
+
+    def row_values(theta_row, noise, Ab, fb):
+        out = np.zeros(m)
+        for lo in range(0, m, step):
+            Q = np.vstack([Ab, X[lo : lo + step]])
+            if theta_row is None and post.canonical:
+                post.make_resident(gp)
+                mean, var, cov = gp._ctx.predict(noise_off(gp._canonical(gp._kernel_theta_for_predict())), Q, return_cov=True)
+            else:
+                mean, var, cov = post.rows_predict(gp, theta_row, Q, noise_zero=True, return_cov=True)
+            mean, var, cov = mean[0], var[0], cov[0]
+            out[lo : lo + step] = joint_entropy_values(mean[R:], var[R:], mean[:R], var[:R], cov[:R, R:].T, fb, noise, tau)
+        return out
+
+    if rows is None:
+        return row_values(None, _jes_noise(gp, [_kg_white_level(gp, gp._post_theta)])[0], A[0], f[0])
+    total = np.zeros(m)
+    n_theta = len(gp.kernel_.theta)
+    saved = (gp._post_theta, gp.alpha_)
+    try:
+        if gp.warp_inputs:
+            with gp._row_warps() as install:
+                vals = [row_values(install(r), _jes_noise(gp, [_kg_white_level(gp, r[:n_theta])])[0], A[b], f[b])
+                        for b, r in enumerate(rows)]
+        else:
+            vals = [row_values(r[None, :], _jes_noise(gp, [_kg_white_level(gp, r)])[0], A[b], f[b]) for b, r in enumerate(rows)]
+    finally:
+        gp._post_theta, gp.alpha_ = saved
+    for v in vals:
+        if np.all(np.isfinite(v)):
+            total += v / n_samples
+    return total
+
+
+class JointEntropySearch(FullGPAcquisition):
+    """Joint entropy search for minimisation under noise (Hvarfner, Hutter & Nardi 2022; Tu, Gandy, Kantas & Shafei 2022): the
+    expected drop of the entropy of an observation at x once the optimum's location and value ``(x*, f*)`` are known, moment
+    matched -- each optimum sample conditions the GP on ``f(x*) = f*`` (jitter ``tau``, normalised-y units squared) and truncates
+    ``f(x) >= f*`` (``joint_entropy_values``).  Values in nats, >= 0.
+
+    ``n_gp_samples = 0``: the median GP with ``n_optima`` optimum samples; ``n_gp_samples = B > 0``: B chain rows drawn without
+    replacement from ``random_state`` (first), each with ``n_optima`` samples of ITS optimum.  The samples are pathwise draws of
+    exactly those rows (``n_features`` Fourier features each), minimised over the unit box on the device from the ``n_starts``
+    lowest of ``n_candidates`` uniform points (``PosteriorPaths.minimize``); ``optimum_samples=(X_opt, f_opt)`` gives them instead:
+    ``X_opt`` (R, d) in the transformed space and ``f_opt`` (R,) in y units, or (B, R, d) / (B, R).  ONE batched posterior build
+    for the rows and ONE device call (``bgp_joint_entropy``); the observation carries the noise a ``tell``
+    with noise 0 would give it (the scalar alpha + the row's white level, floored at 1e-12).  Generic kernel trees,
+    ``warp_inputs=True``, more than 32 dimensions or more than 255 optimum samples: the host path (``joint_entropy_values`` on
+    ``predict(return_cov=True)``), said once on stderr -- and ``ValueError`` with ``sample_paths``' own reason where the draws
+    cannot run and no ``optimum_samples`` were given.  ``return_path``: also "device" | "host"."""
+
+    path = "auto"  # "host": always the host path (tests compare the two)
+
+    def __call__(self, X, gp, *args, n_optima=64, n_gp_samples=0, optimum_samples=None, n_features=1024, n_candidates=2000,
+                 n_starts=4, tau=1e-6, random_state=None, return_path=False, **kwargs):
+        from ._posterior import noise_off
+
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        m, d = X.shape
+        rng = check_random_state(random_state)
+        rows = None
+        if n_gp_samples > 0:
+            rows = gp.chain_[rng.choice(len(gp.chain_), replace=False, size=int(n_gp_samples))]
+        B = 1 if rows is None else len(rows)
+        y_mean, y_std = float(np.ravel(gp.y_train_mean_)[0]), float(np.ravel(gp.y_train_std_)[0])
+        if optimum_samples is None:
+            thetas = np.asarray(gp._post_theta, dtype=np.float64)[None, :] if rows is None else rows
+            with gp._sample_paths_rows(thetas, int(n_optima), n_features, rng) as paths:
+                found = paths.minimize(bounds=(0.0, 1.0), n_candidates=n_candidates, n_starts=n_starts, random_state=rng)
+            A, f = found["x"].reshape(B, -1, d), found["fun"].reshape(B, -1)
+        else:
+            A, f = (np.asarray(a, dtype=np.float64) for a in optimum_samples)
+            if A.ndim == 2:
+                A, f = np.broadcast_to(A[None], (B,) + A.shape), np.broadcast_to(f.reshape(1, -1), (B, f.size))
+            if A.ndim != 3 or A.shape[0] != B or A.shape[2] != d or f.shape != A.shape[:2] or A.shape[1] < 1:
+                raise ValueError("optimum_samples must be ((R, d), (R,)) or ((%d, R, d), (%d, R)) with R >= 1 and d = %d, got %r, %r"
+                                 % (B, B, d, A.shape, f.shape))
+        A, f = np.ascontiguousarray(A), (np.ascontiguousarray(f) - y_mean) / y_std
+        if not np.all(np.isfinite(f)):
+            raise ValueError("the optimum values are not all finite")
+        tau = float(tau)
+        why = ("forced" if self.path == "host" else "generic kernel tree" if not gp._post.canonical else "input warping"
+               if gp.warp_inputs else "more than 32 dimensions" if d > JES_DMAX else "more than 255 optimum samples"
+               if A.shape[1] > JES_RMAX else None)
+        if why is not None:
+            vals = _jes_host(gp, rows, X, A, f, tau, max(int(n_gp_samples), 1), why)
+            return (vals, "host") if return_path else vals
+        if rows is None:
+            gp._post.make_resident(gp)
+            H = gp._canonical(gp._post_theta)
+        else:
+            H = gp._post.build_rows(gp, rows)
+        H = np.atleast_2d(H)
+        noise = _jes_noise(gp, np.exp(H[:, -1]))
+        vals = gp._ctx.joint_entropy(noise_off(H), noise, X, A, f, tau, len(H), want_rows=False)[1]
         return (vals, "device") if return_path else vals

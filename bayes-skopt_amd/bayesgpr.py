@@ -1167,6 +1167,25 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             thetas = np.tile(np.asarray(self._post_theta, dtype=np.float64)[None, :n_theta], (n_paths, 1))
         else:
             thetas = self.chain_[rng.choice(len(self.chain_), size=n_paths, replace=True)][:, :n_theta]
+        return self._paths_of_thetas(thetas, F, rng)
+
+    def _sample_paths_rows(self, thetas, n_per_row, n_features, rng):
+        """``n_per_row`` pathwise draws for EACH row of ``thetas`` (B, n_theta), as ``sample_paths`` draws them: path
+        ``b * n_per_row + j`` is draw j of row b.  The generator ``rng`` is consumed per path as ``sample_paths`` documents (no row
+        indices are drawn here).  ``ValueError`` with ``sample_paths``' own reason where the pathwise draws cannot run."""
+        why = None if getattr(self, "_X_train_", None) is None else self._pathwise_obstacle()
+        if why is not None:
+            raise ValueError("sample_paths does not support %s" % why)
+        n_per_row, F = int(n_per_row), int(n_features)
+        if n_per_row < 1 or not 1 <= F <= 65536:
+            raise ValueError("sample_paths needs n_paths >= 1 and 1 <= n_features <= 65536")
+        n_theta = len(self.kernel_.theta)
+        thetas = np.repeat(np.atleast_2d(np.asarray(thetas, dtype=np.float64))[:, :n_theta], n_per_row, axis=0)
+        return self._paths_of_thetas(thetas, F, rng)
+
+    def _paths_of_thetas(self, thetas, F, rng):
+        """One pathwise draw per row of ``thetas`` (the common tail of ``sample_paths`` and ``_sample_paths_rows``)."""
+        n_paths = len(thetas)
         H = self._canonical(thetas)
         n, d = self._X_train_.shape
         omega, phase, w, eps = draw_path_variates(rng, n_paths, F, d, n, self._plan.stationary)

@@ -391,7 +391,7 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
@@ -433,7 +433,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
   return BGP_OK;
 }
 
-// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip,
+// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip, bgp_jes.hip,
 // bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success

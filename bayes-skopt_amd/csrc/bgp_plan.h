@@ -27,7 +27,7 @@ enum BgpSwitch {
   BGP_SW_STREAMS, BGP_SW_PERSIST, BGP_SW_PANEL_FUSED, BGP_SW_PANELS,
   BGP_SW_WAIT, BGP_SW_DEBUG_TIMES, BGP_SW_PS_COOLDOWN, BGP_SW_PS_TIMEOUT_MS, BGP_SW_PS_TIMEOUT_TICKS, BGP_SW_PS_PAIR, BGP_SW_PS_GEN,
   BGP_SW_PS_TRACE, BGP_SW_COMM_TIMEOUT_S,
-  BGP_SW_SYRK_GEN, BGP_SW_GCOV_CHUNK, BGP_SW_KG_CHUNK,
+  BGP_SW_SYRK_GEN, BGP_SW_GCOV_CHUNK, BGP_SW_KG_CHUNK, BGP_SW_JES_CHUNK,
   BGP_SW_COUNT
 };
 enum BgpSwitchRead { BGP_READ_CONTEXT, BGP_READ_PROCESS, BGP_READ_CALL };
@@ -54,6 +54,7 @@ static const BgpSwitchRow bgp_switches[BGP_SW_COUNT] = {
     {"BGP_SYRK_GEN", BGP_READ_CALL, "1", "0: every Gram block by the Gram kernel, none generated inside the trailing update"},
     {"BGP_GCOV_CHUNK", BGP_READ_CALL, "by n and d", "query points per chunk of bgp_grad_cov, rounded up to 256 (tests: a small chunk against the default)"},
     {"BGP_KG_CHUNK", BGP_READ_CALL, "by n", "candidates per chunk of bgp_knowledge_gradient, rounded up to 128 (tests: a small chunk against the default)"},
+    {"BGP_JES_CHUNK", BGP_READ_CALL, "by n", "candidates per chunk of bgp_joint_entropy, rounded up to 128 (tests: a small chunk against the default)"},
 };
 // read elsewhere: by the Python layer and bench.py, never by libbgp.so
 static const char* const bgp_switches_elsewhere[] = {"BGP_COMM_DIR", "BGP_COMM_PORT", "BGP_COMM_TCP", "BGP_COMM_JOB",

@@ -24,6 +24,7 @@ __all__ = ["Optimizer"]
 ACQUISITION_FUNC = {
     "ei": acquisition.ExpectedImprovement(),
     "kg": acquisition.KnowledgeGradient(),
+    "jes": acquisition.JointEntropySearch(),
     "lcb": acquisition.LCB(),
     "mean": acquisition.Expectation(),
     "mes": acquisition.MaxValueSearch(),

@@ -109,7 +109,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -434,6 +434,36 @@ int bgp_knowledge_gradient(bgp_ctx* ctx, int B, const double* h_kernel, const do
                            const double* Xref, double y_std, int n_samples, double* kg, double* avg);
 
 /*
+ * Joint entropy search acquisition (csrc/bgp_jes.hip) of the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as
+ * in bgp_acq_batch: the white level at -inf, the latent function) at the m candidates Xcand (m*d, row-major).  Posterior b has its
+ * OWN R samples of the optimum: locations Xopt (B*R*d, posterior-major) and values fopt (B*R).  noise (B): the variance of an
+ * observation per posterior, as bgp_knowledge_gradient takes it (constructor alpha + the row's white level), > 0; tau >= 0: a
+ * jitter on the noiseless optimum observation.  In normalised-y units, for minimisation, with latent moments mu, v of x and
+ * mu_r, v_r of a_r, c_r = cov_b(a_r, x) = k_b(a_r, x) - k_b(a_r, X) K_b^-1 k_b(X, x) and w_r = v_r + tau:
+ *   m_r = mu + c_r (f_r - mu_r) / w_r        v_s = max(v - c_r^2 / w_r, 0)         conditioning on f(a_r) = f_r
+ *   z_r = (f_r - m_r) / sqrt(v_s)            v_t = clip(v_s F(z_r), 0, v_s)        f(x) >= f_r: lower truncation
+ *   F(z) = 1 - lam (lam - z),  lam = phi(z) / Phi(-z)                              variance factor of a lower-truncated normal
+ *   g_r = max(1/2 [log(v + noise_b) - log(v_t + noise_b)], 0)                      moment-matched entropy drop, nats
+ *   gain  B*m   gain_b(x_i) = (1 / R) sum_r g_r           avg  m   sum over b, ascending, of gain[b][i] / n_samples
+ * w_r <= 0: the sample conditions nothing (m_r = mu, v_s = v); v_s <= 0: v_t = 0.  A posterior whose values are not all finite
+ * contributes nothing to avg (the rule of bgp_acq_batch).  Either output may be NULL, not both.  No y_std enters: nats.
+ * F is a function of z alone: for z < 4 the definition with lam = sqrt(2 / pi) / erfcx(z / sqrt 2), from 4 on the Laplace continued
+ * fraction lam = z + T, T = 1 / (z + U), U = 2 / (z + 3 / (z + ... 40 / z)), F = T (U - T), which has no cancellation.
+ * Order of the sums: the two quotients 1 / w_r and (f_r - mu_r) / w_r are formed once per sample and multiplied by c_r^2 and c_r;
+ * lane l of a 64-lane wave adds the terms r = l, l + 64, l + 128, l + 192 (< R) in that order, the lanes are added by the xor
+ * butterfly 32, 16, 8, 4, 2, 1, then one division by R.  The product k_b(x, X) (K_b^-1 k_b(X, A_b)) runs on the fp64 MFMA ring.
+ * A candidate's gain is the same bits whatever m and B are, whatever else shares the call, whichever outputs are asked for and
+ * however the call is chunked.
+ * Needs d <= 32, 1 <= R <= 255, 1 <= m <= 2^24, 1 <= B <= 65535, 1 <= n_samples, every noise[b] > 0 and finite, tau >= 0 and finite,
+ * every fopt finite and no context-level warp: BGP_ERR_INVALID before anything is launched; B resident posteriors that are not
+ * per-row warped: BGP_ERR_STATE.  A refused call leaves the resident posteriors as they were; a successful one does not change them
+ * either.
+ *   Replaces: nothing in the reference -- its only information-theoretic acquisition (mes) looks at the optimum's value alone.
+ */
+int bgp_joint_entropy(bgp_ctx* ctx, int B, const double* h_kernel, const double* noise, int m, const double* Xcand, int R,
+                      const double* Xopt, const double* fopt, double tau, int n_samples, double* gain, double* avg);
+
+/*
  * Cross-validation from the resident inverses (csrc/bgp_cv.hip): for each of the first B resident posteriors
  * and each fold F (fold f holds the training indices fold_idx[fold_ptr[f] .. fold_ptr[f + 1])), the predictive of the held-out
  * OBSERVATIONS y_F given all the other ones, without a refit.  With A = K^-1 (K with the alpha diagonal and the white level) and
@@ -520,7 +550,7 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   at the head of their ticket list; default by shape), BGP_SYRK_GEN (0 / 1: on the launch schedule, every Gram block by the
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
- *   256; default by n and d; read at every call), BGP_KG_CHUNK (candidates per chunk of bgp_knowledge_gradient, rounded up to 128;
+ *   256; default by n and d; read at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
  *   default by n; read at every call).
  * Runtime switch set by the PYTHON package, not read by this library: bayes-skopt_amd/_lib.py exports HIP_FORCE_DEV_KERNARG=1 (kernel
  *   arguments in device memory: -6 % per call on the launch schedule at n = 1024 x 32) at import unless the user has set it --
