@@ -6,7 +6,14 @@
 // the K-build through a per-walker X stride.
 #include "bgp_common.h"
 
-// Continued fraction of the incomplete beta function (modified Lentz), relative accuracy ~1e-15.
+// Continued fraction of the incomplete beta function (modified Lentz), at most 1000 iterations; NaN when they do not suffice.
+// Accuracy of bgp_betainc (tests/_warpref.py: the same arithmetic in host fp64 against 50 digits): ABSOLUTE, a few eps times
+// 1 + the sum of the magnitudes of the five terms of the prefactor's exponent -- 2e-15 for parameters in [e^-1, e^1], 3e-14 in
+// [e^-4, e^4], 2e-13 in [e^-6, e^6].  The RELATIVE error is ~1e-13 only near the prior's centre (|w| <= 2): where the complement
+// branch returns a small value as 1 - (nearly 1) it reaches 1e-10 at |w| = 6.
+// Domain: log-space parameters |w| <= 15 (a, b in [3.1e-7, 3.3e6]).  There the fraction converges at every x (most
+// iterations: 778 at a = b = e^15, x = 0.5); the cap is first reached between |w| = 15.7 and 15.8.  Outside, the result is
+// NaN on purpose -- never an unconverged number handed on as if it were one.
 static __device__ double bgp_betacf(double a, double b, double x) {
   const double FPMIN = 1e-300, EPS = 1e-16;
   const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
@@ -31,12 +38,15 @@ static __device__ double bgp_betacf(double a, double b, double x) {
     d = 1.0 / d;
     const double del = d * c;
     h *= del;
-    if (fabs(del - 1.0) < EPS) break;
+    if (fabs(del - 1.0) < EPS) return h;
   }
-  return h;
+  return NAN;  // (not converged: the Gram matrix built from it fails its factorisation, lml = -inf with a non-zero status)
 }
 
 static __device__ double bgp_betainc(double a, double b, double x) {
+  // exp(w) that overflowed or underflowed (or a NaN parameter): no Beta distribution.  NaN at EVERY x, the end points included --
+  // else a = 0 gave 1 above the switch point and b = 0 gave 0 below it, and a column of such values is a valid design matrix
+  if (!(a > 0.0 && a < INFINITY && b > 0.0 && b < INFINITY)) return NAN;
   if (!(x > 0.0)) return 0.0;  // cdf(x <= 0) = 0
   if (x >= 1.0) return 1.0;
   const double bt = exp(lgamma(a + b) - lgamma(a) - lgamma(b) + a * log(x) + b * log1p(-x));

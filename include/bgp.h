@@ -103,6 +103,17 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   query points (bask/bayesgpr.py:630-632); NULL clears it; bgp_ctx_update_data clears it.
  * bgp_beta_cdf: warp m points (m*d row-major) on the device -- BayesGPR.warp() (bask/bayesgpr.py:249-264).
  *
+ * Domain and accuracy of the Beta CDF (all three entry points and the resident sampler's warped walkers run one kernel):
+ *   log-space parameters |w| <= 15, i.e. a, b in [3.1e-7, 3.3e6].  There the continued fraction converges within its 1000
+ *   iterations at every x.  The error is ABSOLUTE (a warped coordinate lives in [0, 1] and enters the kernel through
+ *   differences): 8 eps (1 + |lgamma(a+b)| + |lgamma(a)| + |lgamma(b)| + |a log x| + |b log1p(-x)|), which is 2e-15 for
+ *   |w| <= 1, 3e-14 for |w| <= 4 and 2e-13 for |w| <= 6 (tests/_warpref.py); the relative error of a small result above the
+ *   switch point (a+1)/(a+b+2) reaches 1e-10 at |w| = 6.  x <= 0 gives exactly 0, x >= 1 exactly 1.
+ *   Outside the domain nothing wrong is handed on as a number: a parameter whose exp is 0, inf or NaN gives NaN at every x,
+ *   and so does a continued fraction that has not converged (first between |w| = 15.7 and 15.8).  bgp_beta_cdf returns those
+ *   NaNs; a Gram matrix built from them fails its factorisation, so bgp_lml_batch_warped answers lml = -inf with a non-zero
+ *   status for that row (the other rows keep their bits) and the resident sampler rejects the proposal.
+ *
  * Per-row-warped posteriors (bgp_posterior_batch_warped, below): posterior b is built from the un-warped training inputs
  *   through ITS OWN warp and keeps them resident; a context-level warp is replaced for that call, not composed.  While such
  *   posteriors are resident only bgp_predict_batch_warped reads them (and bgp_cross_validate, which needs neither the inputs nor

@@ -12,6 +12,9 @@ does for tests/_cvref.py.
 * Each slip of ``_mcmcref.SLIPS`` changes the chain of a case in group A and of a case in group B or C.  ``fixed_counted``
   is the exception, for a reason and not for a margin: no case of group A has a fixed canonical entry, so there the slip
   changes no bit (asserted); it has to change BOTH cases of group B.
+* Group W (warped walkers): the fp64 replay there is ``gp_oracle.lml_warped`` (scipy's Beta CDF) against mpmath + long double,
+  within a tenth of ``tol("lml", kappa of the warped matrix, n, warp sensitivity)``; the same three conditions; each slip of
+  ``_mcmcref.WARP_SLIPS`` changes the chain of a warped case.
 
 Lines printed with ``pytest -s`` start with ``MCMCREF``."""
 import time
@@ -39,7 +42,7 @@ def test_cases_reach_every_branch_they_were_written_for():
     assert {c["d"] for c in A} == {1, 2, 3} and {c["vec_alpha"] for c in A} == {True, False}
     for c in R.CASES:
         inp = R.inputs(c["id"])
-        assert R.expected_form(inp["n"], inp["p"], inp["d"] + 2, inp["W"]) == c["runs"], c["id"]
+        assert R.expected_form(inp["n"], inp["p"], inp["d"] + 2, inp["W"], inp["nwarp"]) == c["runs"], c["id"]
         assert inp["plan"][0].shape == (2 * c["steps"], c["W"] // 2)
     shapes = {c["id"][:2]: (R.inputs(c["id"])["p"], R.inputs(c["id"])["d"] + 2, c["W"]) for c in R.CASES}
     assert shapes["E0"][:2] == (64, 64) and shapes["E1"][:2] == (65, 65) and shapes["E2"][:2] == (2, 65)
@@ -56,6 +59,27 @@ def test_cases_reach_every_branch_they_were_written_for():
     assert R.inputs("D0_n17_d1_W2")["W"] == 2
     assert [R.ALL[g]["runs"] for g in R.GROW] == ["fused", "fused", "step_lds"]
     assert R.ALL[R.SEGMENT_CASE]["group"] == "A" and R.ALL[R.SEGMENT_CASE]["steps"] == 4
+    # group W: warped walkers, never fused; the layout [kernel entries, alphas of all columns, betas of all columns]
+    Wc = {c["id"][:2]: (c, R.inputs(c["id"])) for c in R.CASES if c["group"] == "W"}
+    assert sorted(Wc) == ["W%d" % k for k in range(8)]
+    for c, inp in Wc.values():
+        d, ng = inp["d"], inp["ng"]
+        assert inp["nwarp"] == 2 * d and inp["p"] == ng + 2 * d and c["runs"] != "fused" and (inp["h_src"] < ng).all()
+        assert inp["roles"][ng:] == ["wa"] * d + ["wb"] * d and inp["coords0"].shape == (c["W"], inp["p"])
+        assert c["W"] == 2 * inp["p"] + 2 or c["id"][:2] in ("W6", "W7")
+    assert R.expected_form(17, 5, 3, 12, 0) == "fused" and Wc["W0"][0]["runs"] == "step_lds" and Wc["W0"][1]["p"] == 5
+    assert [Wc[k][1]["n"] for k in ("W0", "W1", "W2")] == [17, 65, 129] and np.ndim(Wc["W1"][1]["alpha"]) == 1
+    w3 = Wc["W3"][1]
+    assert (w3["ng"], w3["d"] + 2, w3["p"]) == (2, 5, 8)  # the warp offset is not the canonical vector's length
+    w4 = Wc["W4"][1]
+    assert list(w4["prior_kind"]) == [1, 2, 2, 3, 3, 3, 2] and list(w4["h_src"]) == [0, 1, 2, -1]
+    assert [tuple(v[:2]) for v in w4["prior_par"][3:6]] == [(0.2, 0.3), (0.2, 0.3), (-0.1, 0.5)]
+    # (far from the identity warp, and 0.2 wide in the warp entries: a mover's warp is not its proposal's)
+    assert abs(w4["coords0"][:, 3:5].mean() - 0.3) < 0.1 and abs(w4["coords0"][:, 5:].mean() + 0.2) < 0.1
+    assert w4["coords0"][:, 3:].std(axis=0).min() > 0.1 and w4["coords0"][:, :3].std(axis=0).max() < 0.02
+    assert Wc["W5"][1]["n"] <= 128 and Wc["W5"][0]["edges"]
+    assert doubles(212, 72, 48) == 20472 and doubles(212, 72, 50) == 21325
+    assert [Wc[k][1]["p"] for k in ("W6", "W7")] == [212, 212] and [Wc[k][0]["runs"] for k in ("W6", "W7")] == ["step_lds", "step_hbm"]
 
 
 def test_long_double_prior_formulas_agree_with_the_host_callables():
@@ -86,7 +110,8 @@ def test_fp64_replay_walks_the_long_double_chain_and_the_inputs_hold_their_condi
         assert np.array_equal(ref[key], got[key]), key
     fin = np.isfinite(ref["lp"])
     assert np.array_equal(fin, np.isfinite(got["lp"])) and np.array_equal(np.isneginf(ref["lps"]), np.isneginf(got["lps"]))
-    tol = np.array([P.tol("lml", k, inp["n"]) for k in ref["kappa"][fin]])
+    tol = R.proposal_tolerance(cid)[fin]  # (P.tol("lml", kappa, n, sens) of every proposal; sens = 0 without a warp)
+    assert np.all(np.isfinite(tol)) and (c["warp"] or np.array_equal(tol, [P.tol("lml", k, inp["n"]) for k in ref["kappa"][fin]]))
     reach = float((np.abs(got["lp"][fin] - ref["lp"][fin]) / ref["scale"][fin] / tol).max())
     assert reach <= 1.0 / MARGIN, reach
     # condition 1: every finite margin clears 1000 x the tolerance of the two log-probabilities it compares
@@ -96,9 +121,9 @@ def test_fp64_replay_walks_the_long_double_chain_and_the_inputs_hold_their_condi
     over = float((ref["margin"][f] / bound[f]).min()) if f.any() else np.inf
     assert over >= 1.0, over
     # condition 3: nothing is left out -- a test is either finite (and has a margin) or one of group G's, compared by its outcome
-    assert f.all() or c["group"] == "G"
+    assert f.all() or c["edges"]
     acc, rej = int(ref["accepted"].sum()), int((~ref["accepted"]).sum())
-    moved = bool(c["steps"] > 1 and np.any(chain[1:] != chain[:-1]))
+    moved = bool(np.any(chain[1:] != chain[:-1]) if c["steps"] > 1 else np.any(chain[0] != inp["coords0"]))  # (one step: from the start)
     print("MCMCREF %s runs %s: accepted %d rejected %d non-finite tests %d; smallest margin / bound %.3g; fp64 replay %.4f tol, "
           "kappa <= %.3g; %.2f s" % (cid, c["runs"], acc, rej, int((~f).sum()), over, reach, float(np.nanmax(ref["kappa"])),
                                       time.time() - t0))
@@ -108,9 +133,22 @@ def test_fp64_replay_walks_the_long_double_chain_and_the_inputs_hold_their_condi
     assert nacc.sum() == acc and np.array_equal(lps[-1], logp) and np.array_equal(chain[-1], coords)
 
 
-@pytest.mark.parametrize("cid", [c["id"] for c in R.CASES if c["group"] == "G"])
+@pytest.mark.parametrize("cid", [c["id"] for c in R.CASES if c["edges"]])
 def test_the_edges_of_group_g_are_what_they_were_built_to_be(cid):
+    """(and those of the warped case W5: there the two proposals with lp = -inf have every prior term finite and every kernel
+    entry where its partner has it -- a warp ALPHA entry at +800, a warp BETA entry at -800 decide)"""
     inp, ref = R.inputs(cid), R.replay_full(cid)
+    if inp["nwarp"]:
+        mv, pr, zz = inp["plan"][:3]
+        ng, d = inp["ng"], inp["d"]
+        for key, col, target in (("nan_reject", ng, 800.0), ("inf_reject", ng + d + 1, -800.0)):
+            h, i = inp["edges"][key]
+            s, c = inp["coords0"][mv[h, i]], inp["coords0"][pr[h, i]]
+            q = c - (c - s) * zz[h, i]
+            assert h == 0 and abs(q[col] - target) < 1e-9 and np.array_equal(np.delete(q, col), np.delete(c, col))
+            terms = R.prior_terms_ld(inp["prior_kind"], inp["prior_par"], q)
+            assert np.all(np.isfinite(terms.astype(np.float64))) and not R._warp_ok(q[ng:]) and R._warp_ok(c[ng:])
+            assert abs(q[col]) > 745.0  # exp is 0 or inf in fp64
     e = inp["edges"]
     a, b = e["minus_inf_walkers"]
     assert np.isneginf(inp["logp0"][[a, b]]).all() and np.isfinite(np.delete(inp["logp0"], [a, b])).all()
@@ -141,6 +179,29 @@ def test_every_slip_changes_a_chain():
         else:
             assert bites["A"], slip
             assert bites["B"] or bites["C"], slip
+
+
+def test_every_warp_slip_changes_a_warped_chain():
+    """The mistakes the warped path could make without any other test noticing (``_mcmcref.WARP_SLIPS``): the scatter handing
+    betas where alphas belong; warp parameters read from the mover's current row; a zero stride (every proposal of a half-step
+    sees proposal 0's warped matrix); the warp entries taken from ``hp`` onward instead of from ``ng`` (neutral where the two are
+    equal -- asserted -- and biting on W3, where ng = 2 and hp = 5); the prior summed over the kernel entries only; the LML on
+    the unwarped inputs.  Each changes the chain of at least one of W0 .. W5, and every one of them changes W4: different priors
+    on alphas and betas, a start far from the identity and 0.2 wide in the warp entries, ng = 3 against hp = 4.  The other
+    ensembles are 1e-2 wide, so there a mover's warp is close to its proposal's and ``warp_of_mover`` flips an accept test only
+    on W5, where a mover holds a finite warp entry and its proposal has +-800.  A chain changes only where an accept test
+    flips; on the device every slip also moves the stored log-probabilities, which are held to the tolerance."""
+    ids = [c["id"] for c in R.CASES if c["group"] == "W" and c["id"][:2] not in ("W6", "W7")]
+    for slip in R.WARP_SLIPS:
+        bites = [cid for cid in ids if not np.array_equal(R.replay64(cid, slip)["chain"], R.replay64(cid)["chain"])]
+        print("MCMCREF slip %-19s changes the chain of %d / %d warped cases: %s" % (slip, len(bites), len(ids), " ".join(b[:2] for b in bites)))
+        assert bites, slip
+        assert any(b.startswith("W4") for b in bites), slip
+        if slip == "warp_offset_hp":
+            assert any(b.startswith("W3") for b in bites)
+            for cid in ids:  # where ng == hp the slip reads the right entries
+                inp = R.inputs(cid)
+                assert (cid in bites) or inp["ng"] == inp["d"] + 2, cid
 
 
 def test_run_time():

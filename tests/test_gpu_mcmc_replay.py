@@ -1,7 +1,9 @@
 """The device-resident ensemble sampler against an independent replay of its plan (tests/_mcmcref.py): the fused n <= 128
 half-step (``mcmc_small_kernel``) on a ragged block, every kernel family, a vector alpha, fixed canonical entries, every prior
 kind, -inf log-probabilities and the smallest ensemble; both sides of ``p, hp <= 64``; both sides of the step kernel's 20 480
-doubles; a plan handed over in segments; a context that grows through n = 128.
+doubles; a plan handed over in segments; a context that grows through n = 128; walkers that carry their own input warp
+(group W: a ragged block, two block columns, ng != hp, different priors on alphas and betas, warp entries at +-800, both sides
+of the 20 480 doubles).
 
 The reference shares nothing with the device library: positions are replayed in fp64 with the device's operation order and have
 to be EQUAL; log-probabilities come from ``oracle.hp_oracle`` in long double and have to be within ``_precision.tol("lml")`` on
@@ -44,7 +46,8 @@ def _run(lib, cid, ctx=None, coords0=None):
     own = ctx is None
     ctx = _context(lib, inp) if own else ctx
     try:
-        out = ctx.mcmc_run(inp["coords0"] if coords0 is None else coords0, inp["logp0"], inp["plan"], *_tables(inp))
+        out = ctx.mcmc_run(inp["coords0"] if coords0 is None else coords0, inp["logp0"], inp["plan"], *_tables(inp),
+                           nwarp=inp["nwarp"])
         return out, ctx.mcmc_form
     finally:
         if own:
@@ -74,9 +77,29 @@ def _compare(cid, out, form, tag=""):
 
 @pytest.mark.parametrize("cid", [c["id"] for c in R.CASES if c["group"] != "grow"])
 def test_device_run_equals_the_replay_of_its_plan(lib, cid):
+    """Group W, the warped walkers: the split ng = p - nwarp of ``mcmc_step_kernel``, the pair-wise sum of the warp priors, the
+    scatter of a proposal's last 2 d entries into the per-proposal Beta-CDF design matrices and their row stride, against the
+    replay's mpmath warp and long-double LML; the tolerance carries the Beta-CDF budget (``sens``) at kappa of the WARPED Gram
+    matrix.  A warped ensemble is never fused.
+    (W5 at n = 60 sends two proposals whose warp parameter is exp(800) = inf or exp(-800) = 0: ``bgp_betainc`` answers NaN for
+    every point, the Gram kernel builds a matrix of NaN, and on the launch schedule a matrix of one block column is ONE
+    ``potrf_kernel<0, 0, 0>`` launch with one workgroup per matrix: ``pf_block<0, ..., 0>`` with PRE = 0, ``wrow`` = nullptr and
+    no chain arguments factorises it like any other -- its loops run over block indices, its one early exit is the
+    workgroup-uniform failure word read behind a barrier, it waits for nothing but its own barriers -- and leaves a non-zero
+    status and a non-finite log-likelihood, which the step kernel turns into -inf.  nblk = 1 never takes the launch-free
+    path: ``bgp_persist_fits`` asks for two block columns.)
+    Measured on the device (err / tol of the stored log-probabilities; every case EQUAL in positions and on its form):
+    PRECISION W0_n17_d1_warp                     matern52  product lp     err/tol 2.596e-03  ran step_lds; accepted 26 of 36
+    PRECISION W1_n65_d2_rbf_sum_vec_warp         rbf       sum     lp     err/tol 3.551e-03  ran step_lds; accepted 36 of 54
+    PRECISION W2_n129_d2_m32_warp                matern32  product lp     err/tol 2.798e-03  ran step_lds; accepted 41 of 54
+    PRECISION W3_n60_d3_iso_fixc_warp            matern52  product lp     err/tol 1.576e-03  ran step_lds; accepted 31 of 54
+    PRECISION W4_n60_d2_fixnoise_m12_sum_warp_priors matern12 sum     lp     err/tol 1.229e-03  ran step_lds; accepted 24 of 48
+    PRECISION W5_n60_d2_edges_warp               matern52  product lp     err/tol 1.505e-03  ran step_lds; accepted 37 of 54
+    PRECISION W6_n3_d70_W48_lds_warp             matern52  product lp     err/tol 9.309e-04  ran step_lds; accepted 34 of 48
+    PRECISION W7_n3_d70_W50_hbm_warp             matern52  product lp     err/tol 6.841e-04  ran step_hbm; accepted 28 of 50"""
     out, form = _run(lib, cid)
     _compare(cid, out, form)
-    if R.ALL[cid]["group"] == "G":  # the edges by their outcome
+    if R.ALL[cid]["edges"]:  # the edges by their outcome
         e, inp = R.inputs(cid)["edges"], R.inputs(cid)
         a, b = e["minus_inf_walkers"]
         chain, lps = out[0], out[1]

@@ -287,6 +287,7 @@ def _loopback_run(world, n, d, W, steps, persist, warp=False, seed=3):
     (4, 260, 2, 12, 5, 0, False),       # 6 proposals over four ranks: 1 / 2 / 1 / 2 rows
     (8, 200, 2, 12, 4, 0, False),       # more ranks than some shares have rows: 0 / 1 / 1 / 1 / 0 / 1 / 1 / 1
     (2, 200, 2, 24, 6, 0, True),        # warped walkers, sharded
+    (3, 200, 2, 10, 4, 0, True),        # warped walkers, 5 proposals over three ranks: 1 / 2 / 2 rows
 ])
 def test_sharded_resident_run_over_a_loop_back_group_equals_the_single_context_run(world, n, d, W, steps, persist, warp):
     """The row-sharding logic of the multi-GPU resident sampler with world > 1 semantics on ONE GPU: `world` contexts (one host

@@ -172,3 +172,179 @@ def test_warped_device_chain_equals_oracle_chain(O):
     ref_chain, ref_lp, _, _, _ = O.stretch_move_sampler(log_prob, start, steps, np.random.RandomState(seed))
     np.testing.assert_allclose(dev_chain, ref_chain, rtol=1e-7, atol=1e-9)
     np.testing.assert_allclose(gp._sampler.get_log_prob(), ref_lp, rtol=1e-7)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the Beta CDF at its edges (tests/_warpref.py; tests/test_cpu_warp_reference.py qualifies grid, reference and tolerance)
+# ------------------------------------------------------------------------------------------------------------------------------
+_GRID = {}
+
+
+def _device_grid(lib):
+    """``beta_cdf`` on the edge grid and on its mirror image (1 - x with the parameters swapped), four parameter pairs per call
+    on ONE context of 8 points in d = 4; computed once for the tests below."""
+    if not _GRID:
+        import _warpref as WR
+
+        X, _T, _A, _B = WR.grid()
+        d = 4
+        ctx = lib.Context(np.full((8, d), 0.5), np.zeros(8), 1e-10, max_batch=2)
+        got, mirror = np.empty_like(X), np.empty_like(X)
+        try:
+            for j0 in range(0, len(WR.PAIRS), d):
+                js = [min(j, len(WR.PAIRS) - 1) for j in range(j0, j0 + d)]  # (the last call repeats the last pair)
+                wa, wb = [WR.PAIRS[j][0] for j in js], [WR.PAIRS[j][1] for j in js]
+                got[js] = ctx.beta_cdf(X[js].T, np.array(wa + wb)).T
+                mirror[js] = ctx.beta_cdf(1.0 - X[js].T, np.array(wb + wa)).T
+        finally:
+            ctx.close()
+        _GRID.update(got=got, mirror=mirror)
+    return _GRID["got"], _GRID["mirror"]
+
+
+def _warpref():
+    hp = pytest.importorskip("oracle.hp_oracle")
+    if not hp.available():
+        pytest.skip("np.longdouble has no 64-bit mantissa here: no extended-precision reference")
+    pytest.importorskip("mpmath")
+    import _warpref as WR
+
+    return WR
+
+
+def test_beta_cdf_on_the_edge_grid_meets_the_absolute_tolerance(lib):
+    """``beta_cdf`` against mpmath at 50 digits on the 121 x 20 grid of tests/_warpref.py, parameters up to e^+-6 and x from the
+    smallest normal double to 1 - 2^-53, at the absolute tolerance ``_warpref.tol`` (K = 8; the host restatement of the same
+    arithmetic holds a quarter of it); exactly 0 at x = 0 and exactly 1 at x = 1 for every (a, b).
+    Measured on the device: worst err / tol 0.203, at w = (-0.3, -1), x = 0.55998 (the switch point; absolute error 1.0e-15);
+    worst absolute error 2.2e-13; the device's values are those of the host restatement bit for bit on 1326 of the 2420
+    points (host: worst err / tol 0.243).  The switch-point test below: largest decrease 0.087 of its 2 tol; the symmetry
+    test: 0.059 of its 2 tol over 1154 points."""
+    WR = _warpref()
+    X, T, _A, _B = WR.grid()
+    got, _mirror = _device_grid(lib)
+    ref = WR.reference()
+    err = np.abs(got.astype(np.longdouble) - ref).astype(np.float64)
+    inner = T > 0.0
+    ratio = np.where(inner, err / np.where(inner, T, 1.0), 0.0)
+    j, i = np.unravel_index(np.argmax(ratio), ratio.shape)
+    host = np.abs(WR.restated()[0].astype(np.longdouble) - ref).astype(np.float64)
+    print("PRECISION beta_cdf edge grid: worst err / tol %.3f at w = (%g, %g), x = %.17g (abs err %.3e); worst abs err %.3e; host "
+          "restatement worst err / tol %.3f; device == host restatement on %d of %d points"
+          % (ratio[j, i], WR.PAIRS[j][0], WR.PAIRS[j][1], X[j, i], err[j, i], err.max(), float((host[inner] / T[inner]).max()),
+             int((got == WR.restated()[0]).sum()), got.size))
+    assert np.all(got[:, 0] == 0.0) and np.all(got[:, 1] == 1.0)
+    assert np.all(np.isfinite(got)) and np.all((got >= 0.0) & (got <= 1.0))
+    assert np.all(err <= T), "worst err / tol %.3f" % ratio[j, i]
+
+
+def test_beta_cdf_is_monotone_across_the_switch_point(lib):
+    """The two continued fractions meet at x = (a + 1) / (a + b + 2): for every (a, b) of the grid the device values at the
+    switch point and its two fp64 neighbours are non-decreasing within 2 tol."""
+    WR = _warpref()
+    _X, T, _A, _B = WR.grid()
+    got, _mirror = _device_grid(lib)
+    s, t = got[:, WR.SWITCH], T[:, WR.SWITCH]
+    step = np.diff(s, axis=1)
+    lim = 2.0 * np.maximum(t[:, :-1], t[:, 1:])
+    print("PRECISION beta_cdf switch point: largest decrease / (2 tol) %.3f" % float((-step / lim).max()))
+    assert np.all(step >= -lim)
+
+
+def test_beta_cdf_symmetry(lib):
+    """I_x(a, b) + I_{1-x}(b, a) = 1 within 2 tol at every grid point whose 1 - x is exact in fp64."""
+    from fractions import Fraction
+
+    WR = _warpref()
+    X, T, A, B = WR.grid()
+    got, mirror = _device_grid(lib)
+    worst, count = 0.0, 0
+    for j in range(X.shape[0]):
+        for i in range(X.shape[1]):
+            x = float(X[j, i])
+            if 0.0 < x < 1.0 and Fraction(1) - Fraction(x) == Fraction(1.0 - x):
+                lim = 2.0 * max(T[j, i], WR.tol(B[j], A[j], 1.0 - x))
+                worst, count = max(worst, abs(got[j, i] + mirror[j, i] - 1.0) / lim), count + 1
+    print("PRECISION beta_cdf symmetry: worst |I_x(a, b) + I_{1-x}(b, a) - 1| / (2 tol) %.3f over %d points" % (worst, count))
+    assert count >= 121 * 6 and worst <= 1.0
+
+
+def test_the_three_warp_entry_points_give_the_same_bits(lib):
+    """``beta_cdf``, the context-level warp and the per-walker warp run ONE kernel behind three launches (one matrix without a
+    stride; B matrices behind a row stride, in chunks of ``max_batch``).  n d = 900 is no multiple of the 256 threads of a
+    block, B = 9 > max_batch = 4 (chunks of 4 / 4 / 1).  No accessor reads a warped design matrix back, so the log-likelihood
+    carries the bits: a context built on ``beta_cdf(X, w)`` without a warp, ``set_warp(w)`` on the context of X, and
+    ``lml_warped`` rows that share w, row by row."""
+    n, d, B = 300, 3, 9
+    X, y = synth(n, d, 31)
+    rng = np.random.RandomState(32)
+    H = np.array([0.0, -1.0, -1.1, -0.9, -3.5]) + 0.1 * rng.randn(B, d + 2)
+    H[4] = H[8] = H[0]  # the first row of every chunk: the same problem behind three offsets
+    w = np.array([0.4, -0.3, 0.2, -0.5, 0.1, 0.6])
+    ctx = lib.Context(X, y, 1e-10, max_batch=4)
+    try:
+        rows, st = ctx.lml_warped(H, np.tile(w, (B, 1)), return_status=True)
+        Xw = ctx.beta_cdf(X, w)
+        ctx.set_warp(w)
+        ctxwarp = np.array([ctx.lml(H[b:b + 1])[0] for b in range(B)])
+        ctx.set_warp(None)
+    finally:
+        ctx.close()
+    ctx2 = lib.Context(Xw, y, 1e-10, max_batch=4)
+    try:
+        plain = np.array([ctx2.lml(H[b:b + 1])[0] for b in range(B)])
+    finally:
+        ctx2.close()
+    assert np.all(st == 0) and np.all(np.isfinite(rows)) and rows[0] == rows[4] == rows[8]
+    assert np.array_equal(ctxwarp, plain), "set_warp and beta_cdf: max |d| %.3e" % np.abs(ctxwarp - plain).max()
+    assert np.array_equal(rows, ctxwarp), "lml_warped and set_warp: max |d| %.3e" % np.abs(rows - ctxwarp).max()
+
+
+def test_warp_parameters_outside_the_domain_give_minus_inf_not_nan(lib):
+    """Outside |w| <= 15 (include/bgp.h at ``bgp_beta_cdf``) a per-walker warped LML is a finite number or -inf with a non-zero
+    status, never NaN; where ``exp(w)`` is 0 or inf it is -inf with a non-zero status -- the Beta CDF is NaN there by
+    construction, whatever x is; and the other rows of the batch keep the bits they have alone.  n = 60: one block column, so
+    a matrix of NaN is factorised by one workgroup that waits for nothing but its own barriers (the argument is written out
+    at ``test_device_run_equals_the_replay_of_its_plan`` of tests/test_gpu_mcmc_replay.py)."""
+    n, d = 60, 2
+    X, y = synth(n, d, 41)
+    X = 0.05 + 0.9 * (X - X.min(axis=0)) / (X.max(axis=0) - X.min(axis=0))  # strictly inside (0, 1)
+    assert X.min() > 0.0 and X.max() < 1.0
+    rng = np.random.RandomState(42)
+    far = [20.0, -20.0, 700.0, -700.0, 800.0, -800.0]
+    W = 0.3 * rng.randn(3 * len(far), 2 * d)
+    bad = {}
+    for k, v in enumerate(far):  # rows 3 k: an ALPHA entry of column 0; rows 3 k + 1: a BETA entry of column 1; rows 3 k + 2: inside
+        W[3 * k, 0], W[3 * k + 1, d + 1] = v, v
+        bad[3 * k], bad[3 * k + 1] = v, v
+    H = np.array([0.0, -1.0, -1.1, -3.5]) + 0.1 * rng.randn(len(W), d + 2)
+    good = [b for b in range(len(W)) if b not in bad]
+    ctx = lib.Context(X, y, 1e-10, max_batch=5)  # (18 rows in chunks of 5 / 5 / 5 / 3)
+    try:
+        got, st = ctx.lml_warped(H, W, return_status=True)
+        alone = np.array([ctx.lml_warped(H[b:b + 1], W[b:b + 1])[0] for b in good])
+        cdf = ctx.beta_cdf(X, np.array([800.0, 0.1, -0.2, -800.0]))
+        half = [ctx.beta_cdf(np.full((1, d), 0.5), np.array([v, 0.0, v, 0.0]))[0] for v in (15.0, 20.0)]
+    finally:
+        ctx.close()
+    for b, v in bad.items():
+        print("PRECISION warp parameter %6g in row %2d: lml %s status %d" % (v, b, got[b], st[b]))
+    assert not np.any(np.isnan(got))
+    for b, v in bad.items():
+        assert np.isfinite(got[b]) or (got[b] == -np.inf and st[b] != 0), (b, v, got[b], st[b])
+        if abs(v) > 745.0:  # exp(v) is 0 or inf in fp64
+            assert got[b] == -np.inf and st[b] != 0, (b, v, got[b], st[b])
+    assert np.all(np.isfinite(got[good])) and np.all(st[good] == 0)
+    assert np.array_equal(got[good], alone)
+    assert np.all(np.isnan(cdf))  # exp(800) = inf on column 0, exp(-800) = 0 on column 1: NaN at every x
+    # the slowest point of the continued fraction, a = b and x = 0.5, where the answer is 0.5 by symmetry: at the edge of the
+    # domain (778 iterations in host fp64) within the tolerance; at w = (20, 20) the cap is reached -- NaN, not the 0.4826 that
+    # the unconverged fraction gives.  (Column 1 is Beta(1, 1): the identity.)  Measured on the device: 0.49999999958113872 at
+    # e^15, 4.2e-10 from 0.5 against a tolerance of 3.4e-7; NaN at e^20; w = +-20 in ONE entry converges (status 0), w = 700 gives
+    # -inf with status 2 like +-800.
+    import _warpref as WR
+
+    a15 = float(np.exp(15.0))
+    print("PRECISION beta_cdf at a = b = e^15, x = 0.5: %.17g (tol %.3e); at a = b = e^20: %s" % (half[0][0], WR.tol(a15, a15, 0.5), half[1][0]))
+    assert abs(half[0][0] - 0.5) <= WR.tol(a15, a15, 0.5) and np.isnan(half[1][0])
+    assert abs(half[0][1] - 0.5) <= WR.tol(1.0, 1.0, 0.5) and abs(half[1][1] - 0.5) <= WR.tol(1.0, 1.0, 0.5)
