@@ -309,11 +309,12 @@ KG_HOST_ROWS = 2048         # rows of [reference points; candidates] per predict
 _kg_told = []
 
 
-def _kg_tell_once(why):
-    """One line on stderr, once per process: a knowledge gradient computed on the host from ``predict(return_cov=True)``."""
-    if not _kg_told:
-        _kg_told.append(True)
-        print("[bayes_skopt_amd] knowledge_gradient: on the host from predict(return_cov=True) (%s)" % why, file=sys.stderr, flush=True)
+def _tell_once(name, why):
+    """One line on stderr, once per process and acquisition: computed on the host from ``predict(return_cov=True)``."""
+    told = globals()[{"knowledge_gradient": "_kg_told", "joint_entropy": "_jes_told"}[name]]
+    if not told:
+        told.append(True)
+        print("[bayes_skopt_amd] %s: on the host from predict(return_cov=True) (%s)" % (name, why), file=sys.stderr, flush=True)
 
 
 def knowledge_gradient_values(p, q):
@@ -374,58 +375,71 @@ def _kg_white_level(gp, theta):
     return float(k.get_params()[name].noise_level) if present else 0.0
 
 
-def _kg_host(gp, rows, X, A, n_samples, why):
-    """The host path: per row the latent joint moments of [A; chunk] from ``predict(return_cov=True)`` (the device's predictive
-    products, the kernel on the host where it is a generic tree), the lines, ``knowledge_gradient_values``.  ``rows=None``: the
-    median GP.  Under ``warp_inputs`` a chain row is installed with its own warp, one row after the other.  Returns (m,) in y
-    units, averaged as ``evaluate_acquisitions`` averages (a row that is not all finite contributes nothing)."""
+def _host_rows(gp, rows, X, points, noise_of, value, n_samples):
+    """The row loop of the host paths: per row b (``rows=None``: the median GP) the latent joint moments of [points[b]; chunk] from
+    ``predict(return_cov=True)`` (the device's predictive products, the kernel on the host where it is a generic tree), handed to
+    ``value(out, b, noise, mean_p, var_p, mean_c, var_c, cov)`` -- ``out`` the chunk's slice of the row's values, ``cov`` (chunk,
+    points), ``noise = noise_of(white level of the row)``.  Under ``warp_inputs`` a chain row is installed with its own warp, one
+    row after the other.  Returns (m,), averaged as ``evaluate_acquisitions`` averages (a row that is not all finite contributes
+    nothing)."""
     from ._posterior import noise_off
 
-    _kg_tell_once(why)
     post = gp._post
-    y_std = float(np.ravel(gp.y_train_std_)[0])
-    m, M = X.shape[0], A.shape[0]
-    step = max(1, KG_HOST_ROWS - M)
+    m = X.shape[0]
 
-    def row_values(theta_row, noise):
+    def row_values(theta_row, theta, b):
+        noise = noise_of(_kg_white_level(gp, theta))
+        M = points[b].shape[0]
+        step = max(1, KG_HOST_ROWS - M)
         out = np.zeros(m)
         for lo in range(0, m, step):
-            Q = np.vstack([A, X[lo : lo + step]])
+            Q = np.vstack([points[b], X[lo : lo + step]])
             if theta_row is None and post.canonical:
                 post.make_resident(gp)
                 mean, var, cov = gp._ctx.predict(noise_off(gp._canonical(gp._kernel_theta_for_predict())), Q, return_cov=True)
             else:
                 mean, var, cov = post.rows_predict(gp, theta_row, Q, noise_zero=True, return_cov=True)
             mean, var, cov = mean[0], var[0], cov[0]
-            v = var[M:]
-            s = v + noise
-            ok = s > 0.0
-            if not ok.any():
-                continue
-            rs = 1.0 / np.sqrt(s[ok])
-            pl = np.concatenate([np.broadcast_to(mean[:M], (int(ok.sum()), M)), mean[M:][ok][:, None]], axis=1)
-            ql = np.concatenate([cov[:M, M:].T[ok], v[ok][:, None]], axis=1) * rs[:, None]
-            out[lo + np.flatnonzero(ok)] = np.maximum(knowledge_gradient_values(pl, ql), 0.0) * y_std
+            value(out[lo : lo + step], b, noise, mean[:M], var[:M], mean[M:], var[M:], cov[:M, M:].T)
         return out
 
-    base = gp._fantasy_base_alpha()
     if rows is None:
-        return row_values(None, base + _kg_white_level(gp, gp._post_theta))
+        return row_values(None, gp._post_theta, 0)
     total = np.zeros(m)
     n_theta = len(gp.kernel_.theta)
     saved = (gp._post_theta, gp.alpha_)
     try:
         if gp.warp_inputs:
             with gp._row_warps() as install:
-                vals = [row_values(install(r), base + _kg_white_level(gp, r[:n_theta])) for r in rows]
+                vals = [row_values(install(r), r[:n_theta], b) for b, r in enumerate(rows)]
         else:
-            vals = [row_values(r[None, :], base + _kg_white_level(gp, r)) for r in rows]
+            vals = [row_values(r[None, :], r, b) for b, r in enumerate(rows)]
     finally:
         gp._post_theta, gp.alpha_ = saved
     for v in vals:
         if np.all(np.isfinite(v)):
             total += v / n_samples
     return total
+
+
+def _kg_host(gp, rows, X, A, n_samples, why):
+    """The host path: the lines of every candidate from the joint moments of [A; chunk] (``_host_rows``; the observation's noise
+    is not floored), ``knowledge_gradient_values``; written only where ``s > 0``.  Returns (m,) in y units."""
+    _tell_once("knowledge_gradient", why)
+    y_std = float(np.ravel(gp.y_train_std_)[0])
+    base = gp._fantasy_base_alpha()
+
+    def value(out, b, noise, mean_p, var_p, mean_c, v, cov):
+        ok = v + noise > 0.0
+        if not ok.any():
+            return
+        rs = 1.0 / np.sqrt((v + noise)[ok])
+        pl = np.concatenate([np.broadcast_to(mean_p, (int(ok.sum()), len(mean_p))), mean_c[ok][:, None]], axis=1)
+        ql = np.concatenate([cov[ok], v[ok][:, None]], axis=1) * rs[:, None]
+        out[ok] = np.maximum(knowledge_gradient_values(pl, ql), 0.0) * y_std
+
+    return _host_rows(gp, rows, X, np.broadcast_to(A, (1 if rows is None else len(rows),) + A.shape), lambda white: base + white, value,
+                      n_samples)
 
 
 class KnowledgeGradient(FullGPAcquisition):
@@ -480,13 +494,6 @@ JES_DMAX, JES_RMAX = 32, 255  # limits of the device call (bgp_jes.hip)
 JES_F_SWITCH, JES_F_DEPTH = 4.0, 40  # F: the definition below the switch point, the continued fraction (cut at this numerator) from it on
 JES_NOISE_FLOOR = 1e-12
 _jes_told, _jes_floor_told = [], []
-
-
-def _jes_tell_once(why):
-    """One line on stderr, once per process: a joint entropy search computed on the host from ``predict(return_cov=True)``."""
-    if not _jes_told:
-        _jes_told.append(True)
-        print("[bayes_skopt_amd] joint_entropy: on the host from predict(return_cov=True) (%s)" % why, file=sys.stderr, flush=True)
 
 
 def _jes_F_direct(z):
@@ -552,47 +559,14 @@ def _jes_noise(gp, whites):
 
 
 def _jes_host(gp, rows, X, A, f, tau, n_samples, why):
-    """The host path: per row the latent joint moments of [A_b; chunk] from ``predict(return_cov=True)`` and
-    ``joint_entropy_values``, row by row as ``_kg_host``.  ``A`` (B, R, d), ``f`` (B, R) in normalised-y units; ``rows=None``: the
-    median GP.  Returns (m,) in nats, averaged as ``evaluate_acquisitions`` averages."""
-    from ._posterior import noise_off
+    """The host path: ``joint_entropy_values`` on the joint moments of [A_b; chunk] (``_host_rows``; the observation's noise floored
+    by ``_jes_noise``).  ``A`` (B, R, d), ``f`` (B, R) in normalised-y units.  Returns (m,) in nats."""
+    _tell_once("joint_entropy", why)
 
-    _jes_tell_once(why)
-    post = gp._post
-    m, R = X.shape[0], A.shape[1]
-    step = max(1, KG_HOST_ROWS - R)
+    def value(out, b, noise, mean_p, var_p, mean_c, var_c, cov):
+        out[:] = joint_entropy_values(mean_c, var_c, mean_p, var_p, cov, f[b], noise, tau)
 
-    def row_values(theta_row, noise, Ab, fb):
-        out = np.zeros(m)
-        for lo in range(0, m, step):
-            Q = np.vstack([Ab, X[lo : lo + step]])
-            if theta_row is None and post.canonical:
-                post.make_resident(gp)
-                mean, var, cov = gp._ctx.predict(noise_off(gp._canonical(gp._kernel_theta_for_predict())), Q, return_cov=True)
-            else:
-                mean, var, cov = post.rows_predict(gp, theta_row, Q, noise_zero=True, return_cov=True)
-            mean, var, cov = mean[0], var[0], cov[0]
-            out[lo : lo + step] = joint_entropy_values(mean[R:], var[R:], mean[:R], var[:R], cov[:R, R:].T, fb, noise, tau)
-        return out
-
-    if rows is None:
-        return row_values(None, _jes_noise(gp, [_kg_white_level(gp, gp._post_theta)])[0], A[0], f[0])
-    total = np.zeros(m)
-    n_theta = len(gp.kernel_.theta)
-    saved = (gp._post_theta, gp.alpha_)
-    try:
-        if gp.warp_inputs:
-            with gp._row_warps() as install:
-                vals = [row_values(install(r), _jes_noise(gp, [_kg_white_level(gp, r[:n_theta])])[0], A[b], f[b])
-                        for b, r in enumerate(rows)]
-        else:
-            vals = [row_values(r[None, :], _jes_noise(gp, [_kg_white_level(gp, r)])[0], A[b], f[b]) for b, r in enumerate(rows)]
-    finally:
-        gp._post_theta, gp.alpha_ = saved
-    for v in vals:
-        if np.all(np.isfinite(v)):
-            total += v / n_samples
-    return total
+    return _host_rows(gp, rows, X, A, lambda white: _jes_noise(gp, [white])[0], value, n_samples)
 
 
 class JointEntropySearch(FullGPAcquisition):

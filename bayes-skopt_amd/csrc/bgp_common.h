@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -391,7 +392,7 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
@@ -433,7 +434,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
   return BGP_OK;
 }
 
-// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_kg.hip, bgp_jes.hip,
+// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
 // bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
@@ -528,3 +529,87 @@ struct S4Gen {           // what the trailing update's Gram generator reads (S4G
   int n, d, dpad, npad;
 };
 int bgp_lml_gen_args(const bgp_ctx* ctx, int off, S4Gen* out);
+// bgp_syrk4.hip, NT products on the LDS-DMA ring for nb items (item b's B operand is Bm + (pidxB ? pidxB[b] : b) * sB; M, N multiples
+// of 64): mode 0: C = A B^T; mode 1: C -= A B^T on the lower tiles of a square C; mode 2: C -= A B^T on all tiles
+void bgp_launch_gemm4(hipStream_t st, int mode, const double* A, const double* Bm, int ldx, int M, int N, int K, double* C,
+                      int ldc, int nb, size_t sA, size_t sB, size_t sC, const int* pidxB);
+// bgp_syrk4.hip: column-tile partials of a_i^T S_b a_i for the rows of A_b (M x n, zero padded, multiples of 128; S symmetric) into
+// part = nb * (n / bgp_rowquad_tile()) * M doubles; rowdot_reduce_kernel adds them
+void bgp_launch_rowquad(hipStream_t st, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
+                        const int* pidx, int M, int n, int nb, double* part);
+int bgp_rowquad_tile();
+// bgp_post.hip: out[b][i] = sum_t part[(b tn + t) M + i], t ascending (out packed with stride M); grid (ceil(M / 256), items)
+__global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, int M, double* __restrict__ out);
+// bgp_post.hip: var[b][i] = max(0, kernel_.diag of H[b] incl. the white level - q[b][i]), i < m; grid (ceil(m / 256), items)
+__global__ void finish_var_kernel(const double* __restrict__ q, size_t sq, const double* __restrict__ H, int d, int form,
+                                  int m, double* __restrict__ var, size_t so);
+// bgp_post.hip: C[i][i] += v, i < m; grid ceil(m / 256)
+__global__ void add_diag_kernel(double* __restrict__ C, int ld, int m, double v);
+// bgp_post.hip, the closed forms and the average of bgp_acq_batch.  mumin[b] = np.min of draw b's means (NaN if any is); grid (draws)
+__global__ void __launch_bounds__(256) acq_mumin_kernel(const double* __restrict__ mean, size_t smean, int m,
+                                                         double y_mean, double y_std, double* __restrict__ mumin);
+// T[(k B + b) sm + i] = acquisition k of draw b at candidate i, bad[k B + b] |= "not finite"; grid (ceil(m / 256), draws)
+__global__ void __launch_bounds__(256) acq_values_kernel(const double* __restrict__ mean, const double* __restrict__ var,
+                                                          size_t sm, int m, int B, double y_mean, double y_std, int n_acq,
+                                                          const int* __restrict__ kinds,
+                                                          const double* __restrict__ params,
+                                                          const double* __restrict__ mumin, double* __restrict__ T,
+                                                          int* __restrict__ bad);
+// acc[k sm + i] = sum over b ascending of T[(k B + b) sm + i] / n_samples, a draw with bad[k B + b] left out; grid (ceil(m / 256), n_acq)
+__global__ void __launch_bounds__(256) acq_sum_kernel(const double* __restrict__ T, const int* __restrict__ bad, size_t sm,
+                                                       int m, int B, int n_samples, double* __restrict__ acc);
+// bgp_fantasy.hip: argmax over the candidates not chosen yet (np.argmax's order: ties to the lower index); one workgroup of 1024
+__global__ void __launch_bounds__(1024) fant_argmax_kernel(const double* __restrict__ acc, const int* __restrict__ chosen, int m,
+                                                           int* __restrict__ next);
+
+static inline int pad_to(int v, int q) { return (v + q - 1) / q * q; }
+
+// bgp_post.hip, the latent moments of `rows` query rows for nb items as bgp_predict_batch computes them -- five launches: the cross
+// build K_* = k_b(Xq_b, Xt_b) with the column-tile partials of K_* alpha_b, rowdot_reduce_kernel (mean), bgp_launch_rowquad on
+// K_* and K_b^-1, rowdot_reduce_kernel, the kernel diagonal minus that in place (variance).  Item b reads dH + b (d + 2), dXq + b qstride, dXt + b xstride
+// (stride 0: shared), alpha + b npad, Kinv + b npad^2 and writes dKs + b sKs (leading dimension ldk), dmpart (nb * (npad / 128) *
+// pad128(rows)), dmean / dvar + b pad128(rows).  dvar == nullptr: the first two launches only.  The row-dot partials go to
+// c->drowpart, grown here when it is too small (a caller that loops sizes it before its loop).
+int bgp_launch_moments(bgp_ctx* c, int nb, const double* dH, int rows, const double* dXq, size_t qstride, const double* dXt,
+                       size_t xstride, const double* alpha, const double* Kinv, double* dKs, int ldk, size_t sKs, double* dmpart,
+                       double* dmean, double* dvar);
+
+// ---- moments of candidates conditional on point sets: the pipeline behind bgp_knowledge_gradient and bgp_joint_entropy
+// (bgp_cond.hip) ----
+struct BgpCondPlan {
+  int Mp, M64;  // points as stored (rows of R, columns of C: pad128, at least 128) and as multiplied (pad64)
+  int mtot;     // pad128 of the candidates: the row stride of the value matrix
+  int mc;       // candidates per chunk
+  int tq;       // column tiles of the row-dot partials
+  int Bc;       // posteriors per chunk: K_*, C, R and P of a chunk within 2^29 doubles together
+  size_t sKs, sC, sR, sAx;  // item strides of K_*, C, R / P and of the point sets (0: one shared set)
+};
+struct BgpCondReq {
+  int B, m, M;                               // posteriors, candidates, points per set (0: none, stage 1 is skipped)
+  const double *h_kernel, *noise, *Xcand;    // host: B x (d + 2), B, m x d
+  const double* Xpts;                        // host: the point sets (M x d each)
+  bool per_posterior;                        // one set per posterior (B sets) instead of one shared set
+  const double* fpts;                        // host, B x M values that go with the points, or nullptr (not carved then)
+  bool want_var;                             // the latent variance at the points (not carved otherwise)
+  BgpSwitch chunk_switch;                    // the caller's candidate-chunk switch (tests)
+  int n_samples;                             // divisor of the average
+  double *rows, *avg;                        // host outputs: B x m values, m averaged values (either may be nullptr)
+};
+struct BgpCondChunk {                // posteriors b0 .. b0 + nb, candidates m0 .. m0 + mm; every pointer is that of item b0
+  int b0, nb, m0, mm;
+  const double *muA, *vA;            // [b][j] latent mean / variance at the points (stride Mp; vA only with want_var)
+  const double* fpts;                // [b][j] (stride M; only when given)
+  const double* Cv;                  // [b][i][j] = cov_b(point j, candidate i) (row stride Mp, item stride sC; not written when M == 0)
+  int Mp;
+  size_t sC;
+  const double *mean, *var;          // [b][i] latent moments of the chunk (stride sm)
+  size_t sm;
+  const double* noise;               // [b]
+  double* out;                       // [b][i] values of the chunk (stride so)
+  size_t so;
+  int* bad;                          // [b] "a value is not finite" (zero on entry)
+};
+BgpCondPlan bgp_cond_plan(const bgp_ctx* c, const BgpCondReq& q);
+// Uploads, stage 1 per chunk of posteriors, stage 2 per chunk of candidates followed by `score` (ONE launch of the caller's scoring
+// kernel on the context's stream), then the average, the downloads and the stream sync.
+int bgp_cond_run(bgp_ctx* c, const BgpCondReq& q, const std::function<void(const BgpCondChunk&)>& score);

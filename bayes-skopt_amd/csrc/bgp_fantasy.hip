@@ -17,16 +17,6 @@
 #include "bgp_common.h"
 #include "bgp_device.h"
 
-// bgp_post.hip: the closed forms + average of bgp_acq_batch
-__global__ void acq_mumin_kernel(const double* __restrict__ mean, size_t smean, int m, double y_mean, double y_std,
-                                 double* __restrict__ mumin);
-__global__ void acq_values_kernel(const double* __restrict__ mean, const double* __restrict__ var, size_t sm, int m, int B,
-                                  double y_mean, double y_std, int n_acq, const int* __restrict__ kinds,
-                                  const double* __restrict__ params, const double* __restrict__ mumin, double* __restrict__ T,
-                                  int* __restrict__ bad);
-__global__ void acq_sum_kernel(const double* __restrict__ T, const int* __restrict__ bad, size_t sm, int m, int B,
-                               int n_samples, double* __restrict__ acc);
-
 #define FT_TP 64       // training points per LDS tile of the generated GEMV
 #define FT_DMAX 32     // input dimensions the generated GEMV stages (larger d: the caller's fallback path)
 

@@ -34,9 +34,6 @@
 #define GC_MDMAX (1 << 24)  // m d per call
 #define GC_UMAX 3           // (pair, slice) units per thread of the contraction: (GC_DMAX (GC_DMAX + 1) / 2 + GC_DMAX) / 256, rounded up
 
-void bgp_launch_gemm4(hipStream_t st, int mode, const double* A, const double* Bm, int ldx, int M, int N, int K, double* C,
-                      int ldc, int nb, size_t sA, size_t sB, size_t sC, const int* pidxB);
-
 // R[b][(s d + k) npad + j] for the points s of this chunk; grid (npad / 64, points / GC_PT, posteriors)
 template <int STAT, int FORM>
 __global__ void __launch_bounds__(256) gcov_build_kernel(const double* __restrict__ X, int n, int npad, int d,

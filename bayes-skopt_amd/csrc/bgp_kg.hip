@@ -5,19 +5,13 @@
 //   p_j = mu_b(a_j)   q_j = cov_b(a_j, x) / sqrt(s)   (j < M)        p_M = mu_b(x)   q_M = var_b(x) / sqrt(s)
 //   cov_b(a, x) = k_b(a, x) - k_b(a, X) K_b^-1 k_b(X, x)             (latent: no white term)
 //   KG_b(x) = min_j p_j - E[min_j (p_j + q_j Z)] >= 0, exactly 0 where s <= 0
-// Stages, plain launches on the context's stream:
-//   1  reference rows, once per chunk of posteriors: R = k_b(A, X) and mu_b(A) = R alpha_b by the cross build (kbuild_cross_kernel,
-//      rows zero padded to 128), P = R K_b^-1 on the LDS-DMA ring (bgp_launch_gemm4).
-//   2  per chunk of candidates: K_* = k_b(chunk, X), mean and variance as bgp_predict_batch computes them (the same launches, the same
-//      bits); k_b(chunk, A) by the cross build into C, then C -= K_* P^T on the ring (mode 2 of gemm4_kernel): the hot product,
-//      2 n m pad64(M) flops per posterior.  C[x][j] = cov_b(a_j, x).
+// Stages 1, 2 and 4 -- mu_b(A), the candidates' moments, C[x][j] = cov_b(a_j, x), the average over the posteriors -- are the
+// conditional-moments pipeline of bgp_cond.hip with ONE point set shared by the posteriors and no point variances.  Stage
 //   3  kg_envelope_kernel: one wave per (posterior, candidate).  The lower envelope by pairwise interval clipping, sort-free: line j
 //      is the minimum on [lo_j, hi_j] = the intersection over i of {z : (q_j - q_i) z <= p_i - p_j}; a bound is kept as a fraction
 //      (numerator, positive denominator; denominator 0 = infinite) and two bounds are compared by cross-multiplication, so the M^2 loop
 //      holds no division.  A line that owns an interval contributes (p_j - p*) (Phi(hi) - Phi(lo)) + q_j (phi(lo) - phi(hi)), p* = min p.
 //      Divisions per candidate: 1 (1 / sqrt(s)) + 2 (M + 1) (the two bounds of every line).
-//   4  the average over the posteriors: bgp_acq_batch's kernel (acq_sum_kernel: ascending posterior, value / n_samples, a posterior
-//      with a non-finite value contributes nothing).
 // No workgroup waits for another; no floating-point atomics (one integer flag per posterior: "a value is not finite"); every loop is
 // bounded by an argument.  A candidate's value depends on the posterior, the ordered reference list and that candidate alone: a lane
 // adds its lines in ascending j = lane + 64 t, the 64 lanes are added by a fixed butterfly.
@@ -28,18 +22,6 @@
 #define KG_MMAX 255   // reference points
 #define KG_LMAX 256   // lines of a candidate (KG_MMAX + 1)
 #define KG_LPL 4      // lines per lane (KG_LMAX / 64)
-
-// bgp_post.hip: the pieces of bgp_predict_batch and the average of bgp_acq_batch
-__global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, int M, double* __restrict__ out);
-__global__ void finish_var_kernel(const double* __restrict__ q, size_t sq, const double* __restrict__ H, int d, int form, int m,
-                                  double* __restrict__ var, size_t so);
-__global__ void acq_sum_kernel(const double* __restrict__ T, const int* __restrict__ bad, size_t sm, int m, int B, int n_samples,
-                               double* __restrict__ acc);
-void bgp_launch_gemm4(hipStream_t st, int mode, const double* A, const double* Bm, int ldx, int M, int N, int K, double* C,
-                      int ldc, int nb, size_t sA, size_t sB, size_t sC, const int* pidxB);
-void bgp_launch_rowquad(hipStream_t st, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
-                        const int* pidx, int M, int n, int nb, double* part);
-int bgp_rowquad_tile();
 
 static __device__ __forceinline__ double kg_wave_min(double v) {
 #pragma unroll
@@ -142,101 +124,16 @@ __global__ void __launch_bounds__(256) kg_envelope_kernel(const double* __restri
   }
 }
 
-static inline int kg_pad(int v, int q) { return (v + q - 1) / q * q; }
-
-// Candidates per chunk: a multiple of 128 that depends on n alone, so that a posterior's K_* stays within 2^24 doubles.  BGP_KG_CHUNK
-// (tests): another size, rounded up to 128.
-static size_t kg_cand_chunk(int npad) {
-  size_t mc = (((size_t)1 << 24) / (size_t)npad) / 128 * 128;
-  if (const char* e = bgp_switch(BGP_SW_KG_CHUNK)) {
-    const long v = atol(e);
-    if (v > 0) mc = ((size_t)v + 127) / 128 * 128;
-  }
-  return std::min<size_t>(std::max<size_t>(mc, 128), (size_t)1 << 18);
-}
-
+// Everything but the scoring launch is the conditional-moments pipeline (bgp_cond.hip): one shared point set, no point variances.
 static int kg_run(bgp_ctx* c, int B, const double* h_kernel, const double* noise, int m, const double* Xcand, int M,
                   const double* Xref, double y_std, int n_samples, double* kg, double* avg) {
-  const int n = c->n, d = c->d, npad = c->npad;
-  const size_t p = d + 2;
-  const int Mp = std::max(kg_pad(M, 128), 128), M64 = kg_pad(M, 64);  // rows of R / columns of C as stored, and as multiplied
-  const int mtot = kg_pad(m, 128);
-  const int mc = (int)std::min<size_t>(kg_cand_chunk(npad), (size_t)mtot);
-  const int tq = npad / bgp_rowquad_tile();
-  const size_t sKs = (size_t)mc * npad, sC = (size_t)mc * Mp, sR = (size_t)Mp * npad;
-  // posteriors per chunk: K_*, C, R and P of a chunk within 2^29 doubles together
-  const int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)1 << 29) / (sKs + sC + 2 * sR)));
-  double *dXc, *dA, *dH, *dnoise, *dR, *dP, *dmuA, *dpartA, *dKs, *dmpart, *dmean, *dvar, *dCv, *dKG, *davg;
-  int* dbad;
-  BgpScratch live(c);
-  BGP_TRY(live.carve([&](BgpCarve& s) {
-    dXc = s.take<double>((size_t)m * d);
-    dA = s.take<double>((size_t)std::max(M, 1) * d);
-    dH = s.take<double>((size_t)B * p);
-    dnoise = s.take<double>(B);
-    dR = s.take<double>((size_t)Bc * sR);
-    dP = s.take<double>((size_t)Bc * sR);
-    dmuA = s.take<double>((size_t)Bc * Mp);
-    dpartA = s.take<double>((size_t)Bc * (npad / 128) * Mp);
-    dKs = s.take<double>((size_t)Bc * sKs);
-    dmpart = s.take<double>((size_t)Bc * (npad / 128) * mc);
-    dmean = s.take<double>((size_t)Bc * mc);
-    dvar = s.take<double>((size_t)Bc * mc);
-    dCv = s.take<double>((size_t)Bc * sC);
-    dKG = s.take<double>((size_t)B * mtot);
-    davg = s.take<double>(mtot);
-    dbad = s.take<int>(B);
-  }));
-  BGP_TRY(c->drowpart.ensure((size_t)Bc * tq * mc));
-  hipStream_t st = c->stream;
-  BGP_HIP(bgp_memcpy_async(dXc, Xcand, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, st));
-  if (M > 0) BGP_HIP(bgp_memcpy_async(dA, Xref, (size_t)M * d * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(bgp_memcpy_async(dnoise, noise, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-  BGP_HIP(hipMemsetAsync(dbad, 0, (size_t)B * sizeof(int), st));
-  for (int b0 = 0; b0 < B; b0 += Bc) {
-    const int nb = std::min(Bc, B - b0);
-    const double* dHb = dH + (size_t)b0 * p;
-    const double* Kinv = c->dKinv + (size_t)b0 * npad * npad;
-    const double* al = c->dalpha_sol + (size_t)b0 * npad;
-    if (M > 0) {
-      // R = k_b(A, X) with the column-tile partials of R alpha_b, then P = R K_b^-1 (K^-1 symmetric: an NT product)
-      BGP_TRY(bgp_launch_kcross_matvec(c, nb, dHb, M, dA, n, c->dXeff, dR, npad, sR, al, (size_t)npad, dpartA));
-      hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((Mp + 255) / 256, nb), dim3(256), 0, st, dpartA, npad / 128, Mp, dmuA);
-      bgp_launch_gemm4(st, 0, dR, Kinv, npad, M64, npad, npad, dP, npad, nb, sR, (size_t)npad * npad, sR, nullptr);
-      BGP_HIP(hipGetLastError());
-    }
-    for (int m0 = 0; m0 < m; m0 += mc) {
-      const int mm = std::min(mc, m - m0), mmp = kg_pad(mm, 128);
-      const double* dXq = dXc + (size_t)m0 * d;
-      // mean and variance of the chunk: the launches of bgp_predict_batch (strides of this chunk: mmp)
-      BGP_TRY(bgp_launch_kcross_matvec(c, nb, dHb, mm, dXq, n, c->dXeff, dKs, npad, sKs, al, (size_t)npad, dmpart));
-      hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((mmp + 255) / 256, nb), dim3(256), 0, st, dmpart, npad / 128, mmp, dmean);
-      bgp_launch_rowquad(st, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mmp, npad, nb, c->drowpart);
-      hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((mmp + 255) / 256, nb), dim3(256), 0, st, c->drowpart, tq, mmp, dvar);
-      hipLaunchKernelGGL(finish_var_kernel, dim3((mm + 255) / 256, nb), dim3(256), 0, st, dvar, (size_t)mmp, dHb, d, c->ks.form, mm,
-                         dvar, (size_t)mmp);
-      BGP_HIP(hipGetLastError());
-      if (M > 0) {
-        // C = k_b(chunk, A) - K_* P^T: the hot product, on the columns 0 .. pad64(M) only
-        BGP_TRY(bgp_launch_kcross_batch(c, nb, dHb, mm, dXq, M, dA, dCv, Mp, sC));
-        bgp_launch_gemm4(st, 2, dKs, dP, npad, kg_pad(mm, 64), M64, npad, dCv, Mp, nb, sKs, sR, sC, nullptr);
-      }
-      hipLaunchKernelGGL(kg_envelope_kernel, dim3((mm + 3) / 4, nb), dim3(256), 0, st, dmuA, (size_t)Mp, dCv, sC, Mp, dmean, dvar,
-                         (size_t)mmp, dnoise + b0, M, mm, y_std, dKG + (size_t)b0 * mtot + m0, (size_t)mtot, dbad + b0);
-      BGP_HIP(hipGetLastError());
-    }
-  }
-  if (avg) {
-    hipLaunchKernelGGL(acq_sum_kernel, dim3((m + 255) / 256, 1), dim3(256), 0, st, dKG, dbad, (size_t)mtot, m, B, n_samples, davg);
-    BGP_HIP(hipGetLastError());
-    BGP_HIP(bgp_memcpy_async(avg, davg, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  if (kg)
-    BGP_HIP(bgp_memcpy2d_async(kg, (size_t)m * sizeof(double), dKG, (size_t)mtot * sizeof(double), (size_t)m * sizeof(double), B,
-                               hipMemcpyDeviceToHost, st));
-  BGP_HIP(bgp_stream_sync(st));
-  return BGP_OK;
+  BgpCondReq q{};
+  q.B = B, q.m = m, q.M = M, q.h_kernel = h_kernel, q.noise = noise, q.Xcand = Xcand, q.Xpts = Xref;
+  q.chunk_switch = BGP_SW_KG_CHUNK, q.n_samples = n_samples, q.rows = kg, q.avg = avg;
+  return bgp_cond_run(c, q, [&](const BgpCondChunk& k) {
+    hipLaunchKernelGGL(kg_envelope_kernel, dim3((k.mm + 3) / 4, k.nb), dim3(256), 0, c->stream, k.muA, (size_t)k.Mp, k.Cv, k.sC, k.Mp,
+                       k.mean, k.var, k.sm, k.noise, M, k.mm, y_std, k.out, k.so, k.bad);
+  });
 }
 
 extern "C" int bgp_knowledge_gradient(bgp_ctx* c, int B, const double* h_kernel, const double* noise, int m, const double* Xcand,

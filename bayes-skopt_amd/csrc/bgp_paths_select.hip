@@ -15,9 +15,6 @@
 #include "bgp_device.h"
 #include "bgp_paths_int.h"
 
-// bgp_fantasy.hip: argmax over the candidates not chosen yet, one workgroup
-__global__ void fant_argmax_kernel(const double* __restrict__ acc, const int* __restrict__ chosen, int m, int* __restrict__ next);
-
 #define SEL_NT 64    // candidates per workgroup of the values kernel (one wave: m = 10 000 is 157 workgroups, not 40)
 #define SEL_TC 256   // incumbents per LDS tile of the values kernel
 

@@ -107,15 +107,6 @@ __global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, in
   out[(size_t)b * M + i] = s;  // (batched row dots are packed with stride M)
 }
 
-__global__ void add_diag_kernel(double* __restrict__ C, int ld, int m, double v);
-
-void bgp_launch_rowquad(hipStream_t st, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
-                        const int* pidx, int M, int n, int nb, double* part);
-// NT products on the LDS-DMA ring (bgp_syrk4.hip): mode 0: C = A B^T; mode 1: C -= A B^T on the lower tiles of a square C
-void bgp_launch_gemm4(hipStream_t st, int mode, const double* A, const double* Bm, int ldx, int M, int N, int K, double* C,
-                      int ldc, int nb, size_t sA, size_t sB, size_t sC, const int* pidxB);
-int bgp_rowquad_tile();
-
 // out[b][i] = a_i^T S_b a_i for the rows of A_b (M x n, zero padded; S symmetric): half-product on the LDS-DMA ring
 // (rowquad4_kernel, bgp_syrk4.hip) + ordered reduction of the column-tile partials.  out is packed with stride M.
 static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
@@ -131,7 +122,25 @@ static int launch_rowquad(bgp_ctx* c, const double* A, int lda, size_t sA, const
   return BGP_OK;
 }
 
-static inline int pad128(int v) { return ((v + 127) / 128) * 128; }
+static inline int pad128(int v) { return pad_to(v, 128); }
+
+// The latent moments of `rows` query rows for nb items (contract: bgp_common.h).  mean = K_* alpha comes out of the cross build's
+// registers as column-tile partials, added in tile order; q_i = k_i^T K^-1 k_i (= rowsum((K_* K^-1) o K_*), evaluated on the lower
+// block triangle of K^-1) becomes the variance in place.
+int bgp_launch_moments(bgp_ctx* c, int nb, const double* dH, int rows, const double* dXq, size_t qstride, const double* dXt,
+                       size_t xstride, const double* alpha, const double* Kinv, double* dKs, int ldk, size_t sKs, double* dmpart,
+                       double* dmean, double* dvar) {
+  const int npad = c->npad, rp = pad128(rows);
+  BGP_TRY(bgp_launch_kcross_matvec_x(c, nb, dH, rows, dXq, qstride, c->n, dXt, xstride, dKs, ldk, sKs, alpha, (size_t)npad, dmpart));
+  hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((rp + 255) / 256, nb), dim3(256), 0, c->stream, dmpart, npad / 128, rp, dmean);
+  if (dvar) {
+    BGP_TRY(launch_rowquad(c, dKs, ldk, sKs, Kinv, npad, (size_t)npad * npad, nullptr, rp, npad, nb, dvar));
+    hipLaunchKernelGGL(finish_var_kernel, dim3((rows + 255) / 256, nb), dim3(256), 0, c->stream, dvar, (size_t)rp, dH, c->d,
+                       c->ks.form, rows, dvar, (size_t)rp);
+  }
+  BGP_HIP(hipGetLastError());
+  return BGP_OK;
+}
 
 // (bgp_guard and post_call, the ONE guard and the ONE exit path of the entry points of this file: bgp_common.h)
 
@@ -408,18 +417,11 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     const double* Kinv = c->dKinv + (size_t)off * npad * npad;  // items off .. off+nb-1 are posteriors off .. off+nb-1
     const double* al = c->dalpha_sol + (size_t)off * npad;
     double *dq = dqB + (size_t)off * mpad, *dout = doutB + (size_t)off * mpad;
-    // K_* and, from the same registers, the column-tile partials of the mean K_* alpha (added in tile order below)
-    BGP_TRY(bgp_launch_kcross_matvec_x(c, nb, dHc, m, dXq + (size_t)off * qs, qs, n, dXt + (size_t)off * xs, xs, dKs, npad, sKs, al,
-                                       (size_t)npad, dmpart));
-    hipLaunchKernelGGL(rowdot_reduce_kernel, dim3((mpad + 255) / 256, nb), dim3(256), 0, c->stream, dmpart, npad / 128, mpad,
-                       dout);
+    BGP_TRY(bgp_launch_moments(c, nb, dHc, m, dXq + (size_t)off * qs, qs, dXt + (size_t)off * xs, xs, al, Kinv, dKs, npad, sKs, dmpart,
+                               dout, dq));
     if (mean) BGP_HIP(rows_down(c, mean + (size_t)off * m, dout, m, mpad, nb));
-    // q_i = k_i^T K^-1 k_i  (= rowsum((K_* K^-1) o K_*), evaluated on the lower block triangle of K^-1)
-    BGP_TRY(launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq));
+    // (the covariance reads K_* and K^-1 and writes dP / dCov, never dq: behind the moments it leaves their bits alone)
     if (cov) BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, PostKss{dHc, dXq}, 2, dCov, cov + (size_t)off * m * m));  // (never rowwarp)
-    hipLaunchKernelGGL(finish_var_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, (size_t)mpad, dHc, d,
-                       c->ks.form, m, dq, (size_t)mpad);  // in place
-    BGP_HIP(hipGetLastError());
     if (var) BGP_HIP(rows_down(c, var + (size_t)off * m, dq, m, mpad, nb));
     // (the next chunk reuses the scratch slices: stream order keeps its launches behind these copies)
   }
