@@ -681,7 +681,7 @@ class Context:
         """``bgp_minimize_starts``: minimise ``y_mean + y_std mean(x) + kappa y_std sqrt(var(x))`` of resident posterior ``b``
         (``H_kernel``: its d + 2 kernel parameters, or the block of all resident posteriors) over the box [lo, hi] from every row
         of ``X0``, in one launch.  Returns a dict: x (S, d), mean, var (S,; normalised units, the bits of ``predict_grad`` at x),
-        iters, evals, status (S,; 0 converged to ``gtol``, 1 ``max_iter`` reached, 2 no decrease found)."""
+        iters, evals, status (S,; 0 converged to ``gtol``, 1 ``max_iter`` reached, 2 no decrease found or a non-finite objective / gradient)."""
         H = self._H(H_kernel)
         h = _c(H[int(b)] if H.shape[0] > 1 else H[0])
         X0 = _c(np.atleast_2d(X0))
@@ -885,7 +885,7 @@ class Context:
         """``bgp_paths_minimize``: minimise every open path over the box [lo, hi] from its own starts ``X0`` (P, S, d), one
         workgroup per (start, path) in one launch.  Returns a dict: x (P, S, d; inside the box exactly), fun (P, S; normalised
         units) and grad (P, S, d | None): the search's evaluator at x; iters, evals, status (P, S; 0 converged to ``gtol``, 1
-        ``max_iter`` reached, 2 no decrease found).  ``max_iter=0`` evaluates the clipped starts."""
+        ``max_iter`` reached, 2 no decrease found or a non-finite objective / gradient).  ``max_iter=0`` evaluates the clipped starts."""
         X0 = _c(X0)
         P = self._paths_P
         if X0.ndim != 3 or X0.shape[2] != self.d or (P and X0.shape[0] != P):

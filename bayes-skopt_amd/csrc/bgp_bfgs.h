@@ -24,7 +24,8 @@ struct PgBfgs {                   // LDS of one search
 
 // Minimises from B.x (inside [B.lo, B.hi]; wx holds the same point) until the inf-norm of the projected gradient is <= gtol.  On
 // return B.x is the end point, it / nev the iterations and evaluations spent, and the status is returned -- 0: converged, 1: max_iter
-// reached, 2: no decrease found.  The last evaluation need not have been at B.x (a failed line search): the caller closes with one.
+// reached, 2: no decrease found, or the objective / its gradient is not finite.  The last evaluation need not have been at B.x (a
+// failed line search): the caller closes with one.
 template <class Eval, class Objective, class Gradient>
 static __device__ __forceinline__ int pg_bfgs(PgBfgs& B, double* wx, int d, double gtol, int max_iter, Eval&& eval,
                                               Objective&& objective, Gradient&& gradient, int& it, int& nev) {
@@ -46,8 +47,15 @@ static __device__ __forceinline__ int pg_bfgs(PgBfgs& B, double* wx, int d, doub
     if (tid < d) act[tid] = (x[tid] <= lo[tid] && g[tid] > 0.0) || (x[tid] >= hi[tid] && g[tid] < 0.0);
     __syncthreads();
     double pgn = 0.0;
-    for (int t = 0; t < d; t++)
+    bool finite = isfinite(f);
+    for (int t = 0; t < d; t++) {
+      finite = finite && isfinite(g[t]);
       if (!act[t]) pgn = fmax(pgn, fabs(g[t]));
+    }
+    if (!finite) {  // (fmax drops a NaN: without this a non-finite iterate would pass for converged)
+      st = 2;
+      break;
+    }
     if (pgn <= gtol) {
       st = 0;
       break;

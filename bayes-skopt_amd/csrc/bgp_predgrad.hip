@@ -194,7 +194,7 @@ static __device__ __forceinline__ double pg_gradient(const PgWork& W, int t, dou
 }
 
 // One workgroup per start: the projected BFGS of bgp_bfgs.h on pg_eval.  status 0: |projected gradient|_inf <= gtol; 1: max_iter
-// reached; 2: no decrease found.
+// reached; 2: no decrease found, or a non-finite objective / gradient (a NaN start).
 template <int STAT, int FORM>
 __global__ void __launch_bounds__(PG_NT) pg_min_kernel(const double* __restrict__ X, int n, int d, int npad,
                                                        const double* __restrict__ alpha, const double* __restrict__ Kinv,

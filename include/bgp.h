@@ -276,7 +276,8 @@ int bgp_fantasy_stats(bgp_ctx* ctx, long long* out);
  *   most 30 trial points); where y_std sqrt(var) <= 1e-8 the std term contributes no gradient.  Per start: X_out (inside the box
  *   exactly), mean_out / var_out (normalised units: the bits bgp_predict_grad_batch returns at X_out), iters, evals (evaluations of f,
  *   the closing one at X_out included) and status -- 0: the inf-norm of the projected gradient of f (y units) is <= gtol, 1: max_iter
- *   reached, 2: the line search found no decrease.  A start's result does not depend on the other starts.
+ *   reached, 2: the line search found no decrease, or f / its gradient is not finite at an iterate (a NaN start: X_out is the start).
+ *   A start's result does not depend on the other starts.
  *   Replaces: the scipy L-BFGS-B loop of skopt.utils.expected_minimum (bask/optimizer.py:497-503).
  * Both need d <= 32 and no context-level warp (BGP_ERR_INVALID otherwise), and resident posteriors (BGP_ERR_STATE).
  */
@@ -314,10 +315,10 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
  *   Armijo backtracking (at most max_iter iterations of at most 30 trial points).  Per (path, start), item p*S + s: X_out (inside
  *   the box exactly), f_out and g_out (P*S*d, may be NULL): the search's own evaluator at X_out; iters; evals (evaluations of the
  *   path, a closing one at X_out included where the last trial point was not X_out); status -- 0: the inf-norm of the projected
- *   gradient is <= gtol, 1: max_iter reached, 2: the line search found no decrease.  max_iter = 0 is a pure evaluation of the clipped
- *   starts (iters 0, evals 1).  A (path, start) result does not depend on what shares the call.  S >= 1, max_iter >= 0, gtol >= 0
- *   (BGP_ERR_INVALID); BGP_ERR_STATE without a state.  Does not read the resident posteriors.  The staged outputs are chunked over S
- *   under the 2^24-double budget of bgp_paths_eval.
+ *   gradient is <= gtol, 1: max_iter reached, 2: the line search found no decrease (or a non-finite iterate).  max_iter = 0 is a
+ *   pure evaluation of the clipped starts (iters 0, evals 1).  A (path, start) result does not depend on what shares the call.
+ *   S >= 1, max_iter >= 0, gtol >= 0 (BGP_ERR_INVALID); BGP_ERR_STATE without a state.  Does not read the resident posteriors.
+ *   The staged outputs are chunked over S under the 2^24-double budget of bgp_paths_eval.
  *   Replaces: the argmin over 500 random rows of a joint draw in Optimizer.optimum_intervals (bask/optimizer.py:622-689).
  */
 int bgp_paths_begin(bgp_ctx* ctx, int P, const int* pidx, const double* h_kernel, const double* s2, int F,
