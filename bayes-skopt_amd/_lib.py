@@ -102,6 +102,13 @@ SIGNATURES = {
     "bgp_predict_batch_warped": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "bgp_acq_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, C.c_int, _dp]),
     "bgp_acq_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, _dp]),
+    "bgp_predict_mixture": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                      _ip]),
+    "bgp_predict_mixture_warped": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp,
+                                             _dp, _ip]),
+    "bgp_mixture_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                     _ip]),
+    "bgp_mixture_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_pvrs": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "bgp_pvrs_prepare": (C.c_int, [_vp, _dp, C.c_int, _ip]),
     "bgp_fantasy_begin": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, C.c_int,
@@ -605,6 +612,66 @@ class Context:
         _check(self._lib.bgp_acq_values(self._h, mu.shape[0], mu.shape[1], _p(mu), _p(std), len(kinds), _p(kinds),
                                         _p(params), int(n_samples), _p(out)), "bgp_acq_values")
         return out
+
+    def _mixture(self, m, B, probs, at, weights, want, call):
+        """Arguments and outputs shared by ``predict_mixture`` and ``mixture_values``; ``call(tail)`` issues the C call with the
+        common argument tail.  ``want``: which of "moments", "quantiles", "at" to compute (None: whatever the arguments allow)."""
+        probs = _c(np.asarray(probs if probs is not None else [], dtype=np.float64).ravel())
+        Q = len(probs)
+        if want is None:
+            want = ("moments",) + (("quantiles",) if Q else ()) + (("at",) if at is not None else ())
+        nul = C.cast(None, _dp)
+        t = None
+        if at is not None:
+            t = _c(np.broadcast_to(np.asarray(at, dtype=np.float64), (m,)))
+        w = None
+        if weights is not None:
+            w = _c(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (B,):
+                raise ValueError("weights: one per row expected (%d), got %d" % (B, len(w)))
+        mom = np.empty((3, m)) if "moments" in want else None
+        qu = np.empty((Q, m)) if "quantiles" in want else None
+        att = np.empty((3, m)) if "at" in want else None
+        nu = np.zeros(1, dtype=np.int32)
+        opt = lambda a: _p(a) if a is not None else nul  # noqa: E731
+        call((Q, _p(probs) if Q else nul, opt(t), opt(mom), opt(qu), opt(att), _p(nu)), opt(w))
+        out = {"n_used": int(nu[0]), "probs": probs}
+        if mom is not None:
+            out.update(mean=mom[0], within=mom[1], between=mom[2])
+        if qu is not None:
+            out["quantiles"] = qu
+        if att is not None:
+            out.update(cdf=att[0], sf=att[1], logpdf=att[2])
+        return out
+
+    def predict_mixture(self, H_kernel, Xq, y_mean, y_std, probs, at=None, weights=None, warped=False, want=None):
+        """The hyper-posterior mixture ``sum_b w_b N(mu_b, sd_b^2)`` of the first B resident posteriors at Xq, on the device behind
+        the batched predict (bgp_predict_mixture; ``warped``: bgp_predict_mixture_warped on per-row-warped posteriors).  A dict in y
+        units: ``mean``, ``within``, ``between`` (m,), ``quantiles`` (Q, m) at ``probs``, with ``at`` (a value per point) ``cdf``,
+        ``sf``, ``logpdf``, and ``n_used``, the rows that counted (positive weight, finite moments)."""
+        H = self._H(H_kernel)
+        Xq = _c(np.atleast_2d(Xq))
+        B, m = H.shape[0], Xq.shape[0]
+        name = "bgp_predict_mixture_warped" if warped else "bgp_predict_mixture"
+        fn = getattr(self._lib, name)
+        return self._mixture(m, B, probs, at, weights, want, lambda tail, w: _check(
+            fn(self._h, B, _p(H), w, m, _p(Xq), float(y_mean), float(y_std), *tail), name))
+
+    def mixture_values(self, mean, var, y_mean, y_std, probs, at=None, weights=None, want=None):
+        """The same pass on given normalised (B, m) means / variances (bgp_mixture_values): no resident posterior is read."""
+        mean, var = _c(np.atleast_2d(mean)), _c(np.atleast_2d(var))
+        if mean.shape != var.shape:
+            raise ValueError("mean and var differ in shape")
+        B, m = mean.shape
+        return self._mixture(m, B, probs, at, weights, want, lambda tail, w: _check(
+            self._lib.bgp_mixture_values(self._h, B, m, _p(mean), _p(var), w, float(y_mean), float(y_std), *tail),
+            "bgp_mixture_values"))
+
+    def mixture_stats(self):
+        """(largest solver iteration count, largest number of bracket moves) of the last mixture call."""
+        out = (C.c_longlong * 2)()
+        _check(self._lib.bgp_mixture_stats(self._h, out), "bgp_mixture_stats")
+        return int(out[0]), int(out[1])
 
     def pvrs_prepare(self, h_kernel, has_alpha_vec):
         H = self._H(h_kernel)

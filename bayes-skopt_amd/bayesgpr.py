@@ -914,6 +914,64 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             mean, var = self._post.hyper_predict(self, rows, X, noise_zero)
         return self.y_train_std_ * mean + self.y_train_mean_, np.sqrt(var * self.y_train_std_**2)
 
+    def predict_marginal(self, X, thetas=None, n_samples=64, weights=None, quantiles=(0.05, 0.5, 0.95), at=None, noise=False,
+                         random_state=None, return_path=False):
+        """The fully Bayesian prediction at the rows of ``X`` (m, d; transformed space): the hyper-posterior mixture
+        ``sum_b w_b N(mu_b(x), sigma_b(x)^2)`` over chain rows, i.e. the posterior predictive with the kernel hyper-parameters
+        integrated out -- ``predict`` uses the ONE GP at the chain's geometric median.  Rows: ``thetas`` (B, p; under
+        ``warp_inputs`` they carry their warps, as ``chain_`` holds them), or ``n_samples`` rows of ``chain_`` drawn without
+        replacement from ``random_state`` as ``evaluate_acquisitions`` draws them (fewer if the chain is shorter).  ``weights``
+        (B,): importance weights, default equal; a row with weight 0 or a non-finite moment anywhere is left out and the rest
+        renormalised.  ``noise=False``: the latent function, as the acquisitions see it; ``noise=True`` keeps every row's own
+        white level: the predictive of an observation.
+
+        Returns a dict in y units: ``mean``; ``std`` with its two parts ``std_within`` ("the GPs are unsure") and ``std_between``
+        ("the hyper-parameters are unsure": ``std^2 = std_within^2 + std_between^2``); ``quantiles`` (Q, m) of the MIXTURE at
+        ``probs`` (not ``mean + z std``: the two differ as soon as the rows disagree); with ``at`` (a value per point or one for
+        all) ``cdf`` = P(f(x) <= at), ``sf`` = P(f(x) > at) (each accurate in its own tail) and ``logpdf``, the log predictive
+        density of ``at``; ``n_used`` and the ``rows``.  Canonical kernels with at most ``max_batch`` rows: ONE batched build and ONE
+        device call (``bgp_predict_mixture``; under ``warp_inputs`` the per-row-warped build and
+        ``bgp_predict_mixture_warped``) -- the B x m moments never leave the device.  Generic kernel trees, and more rows than
+        ``max_batch``: the rows' moments chunk by chunk through the existing predict paths, then the same pass on them
+        (``bgp_mixture_values``), said once on stderr.  ``return_path``: also "device" | "chunks"."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if self.warp_inputs:
+            validate_zeroone(X)
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        if thetas is None:
+            chain = np.asarray(self.chain_)
+            rng = check_random_state(random_state)
+            rows = chain[rng.choice(len(chain), replace=False, size=min(int(n_samples), len(chain)))]
+        else:
+            rows = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        probs = np.asarray(quantiles if quantiles is not None else [], dtype=np.float64).ravel()
+        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        post, ctx = self._post, self._ctx
+        if post.canonical and len(rows) <= ctx.max_batch and self._warp_rows_path == "auto":
+            if self.warp_inputs:
+                n_theta = len(self.kernel_.theta)
+                H = self._canonical(rows[:, :n_theta])
+                status = ctx.posterior(H, want_alpha=False, warps=np.ascontiguousarray(rows[:, n_theta:]))["status"]
+                raise_if_not_pd(status, self.kernel_)
+            else:
+                H = post.build_rows(self, rows)
+            out = ctx.predict_mixture(H if noise else noise_off(H), X, y_mean, y_std, probs, at=at, weights=weights,
+                                      warped=bool(self.warp_inputs))
+            path = "device"
+        else:
+            _marginal_tell_once("generic kernel tree" if not post.canonical else "more rows than the context's max_batch")
+            step = max(1, int(ctx.max_batch))
+            parts = [self._predict_hyper_samples(rows[b0:b0 + step], X, noise_zero=not noise) for b0 in range(0, len(rows), step)]
+            mu, sd = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+            out = ctx.mixture_values(mu, sd * sd, 0.0, 1.0, probs, at=at, weights=weights)  # (already in y units)
+            path = "chunks"
+        within, between = out.pop("within"), out.pop("between")
+        out.update(std=np.sqrt(within + between), std_within=np.sqrt(within), std_between=np.sqrt(between), rows=rows)
+        if "quantiles" not in out:
+            out["quantiles"] = np.empty((0, X.shape[0]))
+        return (out, path) if return_path else out
+
     def _acq_hyper_samples(self, thetas, X, kinds, params, n_samples, noise_zero=True):
         """Closed-form acquisition values averaged over a batch of hyper-posterior draws, entirely on the device:
         batched posterior build, batched predict and the acquisition / averaging pass of
@@ -1431,6 +1489,17 @@ def _pathwise_tell_once(why):
         _pathwise_told.append(True)
         print("[bayes_skopt_amd] mvn='pathwise': not available for %s; drawing as mvn='auto' does" % why, file=sys.stderr,
               flush=True)
+
+
+_marginal_told = []
+
+
+def _marginal_tell_once(why):
+    """One line on stderr, once per process: a hyper-posterior mixture whose rows' moments came back to the host in chunks."""
+    if not _marginal_told:
+        _marginal_told.append(True)
+        print("[bayes_skopt_amd] predict_marginal: the rows' moments chunk by chunk through predict, then the mixture pass on them "
+              "(%s)" % why, file=sys.stderr, flush=True)
 
 
 _fantasy_told = []

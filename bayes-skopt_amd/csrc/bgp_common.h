@@ -225,6 +225,7 @@ struct bgp_ctx {
   long long fant_stats[2] = {0, 0};             // fantasy begins / steps run on this context (bgp_fantasy_stats)
   struct bgp_paths_state* paths = nullptr;      // pathwise posterior draws (bgp_paths_begin .. bgp_paths_end; bgp_paths.hip)
   long long paths_stats[2] = {0, 0};            // paths begins / evals run on this context (bgp_paths_stats)
+  int mix_last[4] = {0, 0, 0, 0};               // last mixture pass: rows used, largest solver step / bracket-move counts (bgp_mixture_stats)
   struct bgp_mcmc_state* mcmc = nullptr;  // an open device-resident sampler run (bgp_mcmc_begin .. bgp_mcmc_end; bgp_mcmc.hip)
   int ps_forbid = 0;            // the device-resident sampler redoes a run after a time-out: launches only, on every rank
   int ps_resident = 0;          // the device-resident sampler is enqueuing: no per-call copy of the error word (its kernels read it)
@@ -392,13 +393,13 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
 // other entry point's guard too (bgp_api.hip, bgp_gram.hip, bgp_mcmc.hip, bgp_comm.hip).
 //   BGP_POST_PLAIN    the resident posteriors are not per-row warped: they go with the shared c->dXeff
-//   BGP_POST_ROWWARP  they are (bgp_predict_batch_warped)
+//   BGP_POST_ROWWARP  they are (bgp_predict_batch_warped, bgp_predict_mixture_warped)
 //   count > 0: at least `count` are resident (index b: b + 1);  idx: every idx[0 .. nidx) names a resident one.
 // Nothing is launched and nothing changes on a refusal.
 enum BgpPostKind { BGP_POST_ANY, BGP_POST_PLAIN, BGP_POST_ROWWARP };
@@ -435,7 +436,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
 }
 
 // ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
-// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
+// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
 // path is the body's own.
@@ -573,6 +574,29 @@ static inline int pad_to(int v, int q) { return (v + q - 1) / q * q; }
 int bgp_launch_moments(bgp_ctx* c, int nb, const double* dH, int rows, const double* dXq, size_t qstride, const double* dXt,
                        size_t xstride, const double* alpha, const double* Kinv, double* dKs, int ldk, size_t sKs, double* dmpart,
                        double* dmean, double* dvar);
+
+// ---- the hyper-posterior mixture pass (bgp_mix.hip): behind the batched predict (predict_run, bgp_post.hip)
+// for bgp_predict_mixture / bgp_predict_mixture_warped, on uploaded moments for bgp_mixture_values ----
+struct BgpMixPlan {                  // the host side of one pass (arguments of the entry points, include/bgp.h)
+  const double* weights;             // B, or nullptr: every row counts 1
+  double y_mean, y_std;
+  int Q;
+  const double *probs, *t;           // Q probabilities; m values for at_t (nullptr without it)
+  double *moments, *quant, *at_t;    // 3 x m, Q x m, 3 x m; each may be nullptr
+  int* n_used;
+};
+struct BgpMixScratch {               // device regions of bgp_mix_run
+  double *dmu = nullptr, *dsd = nullptr, *dw = nullptr, *dwn = nullptr, *dprobs = nullptr, *dt = nullptr, *dmom = nullptr,
+         *dat = nullptr, *dquant = nullptr;
+  int *dbad = nullptr, *dused = nullptr, *dstat = nullptr;
+  void take(BgpCarve& s, int B, int mpad, int Q);
+};
+int bgp_mix_check(const char* who, int B, const BgpMixPlan& mp);  // the argument rules: BGP_ERR_INVALID, nothing launched
+// the pass on B device rows of stride mpad, enqueued on the context's stream with its downloads; the caller synchronises
+int bgp_mix_run(bgp_ctx* c, int B, int m, int mpad, const double* dmean, const double* dvar, const BgpMixPlan& mp,
+                const BgpMixScratch& ms);
+// bgp_post.hip: predict_run on the first B resident posteriors with the pass behind the moments (nothing else is downloaded)
+int bgp_predict_run_mix(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, const BgpMixPlan& mp, bool rowwarp);
 
 // ---- moments of candidates conditional on point sets: the pipeline behind bgp_knowledge_gradient and bgp_joint_entropy
 // (bgp_cond.hip) ----

@@ -379,7 +379,7 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
 // rowwarp: the resident posteriors are per-row warped -- item b reads its own training inputs (c->dXwP) and its own warped copy of
 // the queries (one upload of the m rows, ONE warp launch over the B parameter sets in c->dwarpP); no cov there.
 static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
-                       double* cov, const AcqPlan* ap, bool rowwarp = false) {
+                       double* cov, const AcqPlan* ap, bool rowwarp = false, const BgpMixPlan* mp = nullptr) {
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
   const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
   const size_t qs = rowwarp ? (size_t)m * d : 0, xs = rowwarp ? (size_t)n * d : 0;  // per-item strides of queries / training inputs
@@ -388,6 +388,7 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   const int n_acq = ap ? ap->n_acq : 0;
   double *dXq, *dXq0 = nullptr, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr;
   AcqScratch as;
+  BgpMixScratch ms;
   BgpScratch live(c);
   BGP_TRY(live.carve([&](BgpCarve& s) {
     dXq = s.take<double>(rowwarp ? (size_t)B * qs : (size_t)m * d);  // (every item's warped queries: all B, as dqB / doutB)
@@ -402,6 +403,7 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
       dCov = s.take<double>((size_t)chunk * sCv);
     }
     if (n_acq) as.take(s, n_acq, B, mpad);
+    if (mp) ms.take(s, B, mpad, mp->Q);
   }));
   if (rowwarp) {
     BGP_HIP(bgp_memcpy_async(dXq0, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -426,8 +428,13 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     // (the next chunk reuses the scratch slices: stream order keeps its launches behind these copies)
   }
   if (n_acq) BGP_TRY(acq_run(c, B, m, mpad, doutB, dqB, *ap, as));
+  if (mp) BGP_TRY(bgp_mix_run(c, B, m, mpad, doutB, dqB, *mp, ms));  // the hyper-posterior mixture of the B rows (bgp_mix.hip)
   BGP_HIP(bgp_stream_sync(c->stream));
   return BGP_OK;
+}
+
+int bgp_predict_run_mix(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, const BgpMixPlan& mp, bool rowwarp) {
+  return predict_run(c, B, h_kernel, m, Xq, nullptr, nullptr, nullptr, nullptr, rowwarp, &mp);
 }
 
 extern "C" int bgp_predict_batch(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean,

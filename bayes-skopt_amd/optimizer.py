@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, sensitivity_indices
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices
 
 __all__ = ["Optimizer"]
 
@@ -325,6 +325,12 @@ class Optimizer:
         without a refit (``utils.cross_validate`` on the current result, same keyword arguments; the optimizer's own random state
         is not consumed)."""
         return cross_validate(self._result(), **kw)
+
+    def predict_marginal(self, X, **kw):
+        """What the surrogate predicts at points ``X`` of the original space once the kernel hyper-parameters are integrated out:
+        mean, within / between spread, mixture quantiles, P(f <= at) and the log predictive density (``utils.predict_marginal`` on
+        the current result, same keyword arguments; the optimizer's own random state is not consumed)."""
+        return predict_marginal(self._result(), X, **kw)
 
     def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed, minimizer="scipy"):
         """Function draws (device ``sample_y``) at [expected optimum, n_space_samples random points]:

@@ -389,6 +389,17 @@ def cross_validate(res, n_folds=None, n_samples=0, folds=None, weights="is", ran
     return reg.cross_validate(folds=folds, n_folds=n_folds, thetas=thetas, weights=weights, random_state=rng)
 
 
+def predict_marginal(res, X, **kw):
+    """The fully Bayesian prediction of the surrogate ``res.models[-1]`` at points ``X`` of the ORIGINAL space: mean, the spread split
+    into its within-GP and between-hyper-parameter parts, quantiles of the hyper-posterior mixture and, with ``at``, P(f <= at),
+    P(f > at) and the log predictive density (``BayesGPR.predict_marginal`` on ``res.space.transform(X)``, same keyword arguments;
+    ``bgp_predict_mixture``)."""
+    X = list(X)
+    if X and not np.iterable(X[0]):
+        X = [X]
+    return res.models[-1].predict_marginal(res.space.transform(X), **kw)
+
+
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):
     """Highest density interval(s) of a 1-d sample (the quantity ``bask/optimizer.py:684`` takes from
     ``arviz.hdi``; arviz is not part of this image, so its two estimators are restated):

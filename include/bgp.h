@@ -116,11 +116,11 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *
  * Per-row-warped posteriors (bgp_posterior_batch_warped, below): posterior b is built from the un-warped training inputs
  *   through ITS OWN warp and keeps them resident; a context-level warp is replaced for that call, not composed.  While such
- *   posteriors are resident only bgp_predict_batch_warped reads them (and bgp_cross_validate, which needs neither the inputs nor
+ *   posteriors are resident only bgp_predict_batch_warped and bgp_predict_mixture_warped read them (and bgp_cross_validate, which needs neither the inputs nor
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -215,6 +215,49 @@ int bgp_acq_batch(bgp_ctx* ctx, int B, const double* h_kernel, int m, const doub
                   int n_acq, const int* kinds, const double* params, int n_samples, double* out);
 int bgp_acq_values(bgp_ctx* ctx, int B, int m, const double* mu, const double* std_, int n_acq, const int* kinds,
                    const double* params, int n_samples, double* out);
+
+/*
+ * The hyper-posterior mixture: the posterior predictive at a point with the kernel hyper-parameters integrated out,
+ *   sum_b w^_b N(mu_b(x), sd_b(x)^2)  over B posteriors (chain rows),
+ * evaluated on the device behind the batched predict (the B*m means and variances never cross PCIe).
+ *   bgp_predict_mixture         the first B resident posteriors, as bgp_acq_batch; h_kernel as in bgp_predict_batch (the white
+ *                               level is h_kernel's last entry: -inf for the latent function).  Its moments are made of the bits
+ *                               bgp_predict_batch returns.
+ *   bgp_predict_mixture_warped  the same on per-row-warped resident posteriors (bgp_posterior_batch_warped).
+ *   bgp_mixture_values          the same pass on caller-supplied normalised mean / var (B*m each): generic kernel trees, more rows
+ *                               than max_batch.  Needs no resident posterior.
+ * With mu_bi = y_std * mean_bi + y_mean and sd_bi = sqrt(var_bi * (y_std * y_std)):
+ *   weights (B, or NULL: w_b = 1).  Row b is USED iff w_b > 0 and all of its m means and variances are finite; W = sum of w_b over
+ *   the used rows in ascending b, w^_b = w_b / W, *n_used = their count.  n_used == 0: every output is NaN, the call returns BGP_OK.
+ *   moments (3*m, may be NULL): mean_i = sum w^_b mu_bi;  within_i = sum w^_b sd_bi^2;  between_i = sum w^_b (mu_bi - mean_i)^2 in a
+ *     second pass against the finished mean (>= 0, exactly 0 for B = 1).  The predictive variance is within + between.
+ *   at_t (3*m, may be NULL; needs t, one value per point, y units), z_bi = (t_i - mu_bi) / sd_bi:
+ *     cdf_i = sum w^_b Phi(z_bi), sf_i = sum w^_b Phi(-z_bi), each tail summed on its own from erfc of a non-negative argument (a
+ *     1e-300 tail keeps its relative accuracy);  logpdf_i = log sum w^_b exp(-z^2 / 2) / (sd_bi sqrt(2 pi)) as a max-shifted sum.
+ *     A component with sd = 0 is a step at mu_bi (Phi = 1 where t >= mu, else 0) and adds nothing to the density; logpdf is -inf
+ *     when no used component has sd > 0.
+ *   quant (Q*m, may be NULL; Q <= BGP_MIX_QMAX probabilities probs inside (0, 1)): q_pi = inf {t : F_i(t) >= p}.  F = p is solved
+ *     for p <= 0.5 and S = 1 - p above.  Bracket: [min_b, max_b] of mu_bi + z_p sd_bi over the used rows, z_p from the device's own
+ *     inverse normal; an end whose evaluated sign is wrong moves outwards.  The bracket shrinks by safeguarded Newton steps (slope:
+ *     the mixture density; bisection when a step leaves the bracket or the bracket has not halved in two steps) until its ends are
+ *     adjacent doubles, and the UPPER end is returned: the result is deterministic and a quantile carried by an atom (sd = 0) is
+ *     exactly that mu.  Iteration cap 200: the upper end of the bracket reached by then is returned.
+ * Every sum runs over the used rows in ascending b, one thread per point: when no row is dropped a point's results are the same
+ * bits alone and in a crowd.  A negative or non-finite weight, Q > BGP_MIX_QMAX or a probs entry outside (0, 1): BGP_ERR_INVALID.
+ * bgp_mixture_stats: out[0] = the largest solver iteration count of the context's last mixture call, out[1] = the largest number
+ * of bracket moves.
+ */
+#define BGP_MIX_QMAX 16
+int bgp_predict_mixture(bgp_ctx* ctx, int B, const double* h_kernel, const double* weights, int m, const double* Xq, double y_mean,
+                        double y_std, int Q, const double* probs, const double* t, double* moments, double* quant, double* at_t,
+                        int* n_used);
+int bgp_predict_mixture_warped(bgp_ctx* ctx, int B, const double* h_kernel, const double* weights, int m, const double* Xq,
+                               double y_mean, double y_std, int Q, const double* probs, const double* t, double* moments,
+                               double* quant, double* at_t, int* n_used);
+int bgp_mixture_values(bgp_ctx* ctx, int B, int m, const double* mean, const double* var, const double* weights, double y_mean,
+                       double y_std, int Q, const double* probs, const double* t, double* moments, double* quant, double* at_t,
+                       int* n_used);
+int bgp_mixture_stats(bgp_ctx* ctx, long long* out);
 
 /*
  * PVRS inner loop with the resident posterior built by bgp_pvrs_prepare (K without the candidate
