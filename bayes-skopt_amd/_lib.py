@@ -121,6 +121,7 @@ SIGNATURES = {
     "bgp_paths_eval": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "bgp_paths_end": (C.c_int, [_vp]),
     "bgp_paths_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bgp_chunk_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "bgp_paths_minimize": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_paths_select": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _ip, C.c_int, _ip, _dp, _dp]),
     "bgp_predict_grad_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
@@ -1004,6 +1005,12 @@ class Context:
         out = (C.c_longlong * 2)()
         _check(self._lib.bgp_paths_stats(self._h, out), "bgp_paths_stats")
         return {"begins": int(out[0]), "evals": int(out[1])}
+
+    def chunk_stats(self):
+        """Chunks of the last budget-chunked posterior call: posteriors, and query rows / candidates / starts."""
+        out = (C.c_longlong * 2)()
+        _check(self._lib.bgp_chunk_stats(self._h, out), "bgp_chunk_stats")
+        return {"items": int(out[0]), "rows": int(out[1])}
 
     def sample_y(self, b, h_kernel, Xq, z, jitter=0.0):
         H = self._H(h_kernel)

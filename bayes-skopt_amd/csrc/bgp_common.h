@@ -226,6 +226,7 @@ struct bgp_ctx {
   struct bgp_paths_state* paths = nullptr;      // pathwise posterior draws (bgp_paths_begin .. bgp_paths_end; bgp_paths.hip)
   long long paths_stats[2] = {0, 0};            // paths begins / evals run on this context (bgp_paths_stats)
   int mix_last[4] = {0, 0, 0, 0};               // last mixture pass: rows used, largest solver step / bracket-move counts (bgp_mixture_stats)
+  long long chunk_last[2] = {0, 0};             // last chunked posterior call: item chunks, row / candidate chunks (bgp_chunk_stats)
   struct bgp_mcmc_state* mcmc = nullptr;  // an open device-resident sampler run (bgp_mcmc_begin .. bgp_mcmc_end; bgp_mcmc.hip)
   int ps_forbid = 0;            // the device-resident sampler redoes a run after a time-out: launches only, on every rank
   int ps_resident = 0;          // the device-resident sampler is enqueuing: no per-call copy of the error word (its kernels read it)

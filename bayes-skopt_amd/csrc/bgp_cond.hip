@@ -37,6 +37,7 @@ BgpCondPlan bgp_cond_plan(const bgp_ctx* c, const BgpCondReq& q) {
   p.sKs = (size_t)p.mc * npad, p.sC = (size_t)p.mc * p.Mp, p.sR = (size_t)p.Mp * npad;
   p.sAx = q.per_posterior ? (size_t)q.M * c->d : 0;
   p.Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)q.B, ((size_t)1 << 29) / (p.sKs + p.sC + 2 * p.sR)));
+  p.Bc = (int)bgp_switch_cap(BGP_SW_ITEM_CHUNK, (size_t)p.Bc);  // (tests: forced posterior chunks against the default)
   return p;
 }
 
@@ -79,7 +80,9 @@ int bgp_cond_run(bgp_ctx* c, const BgpCondReq& q, const std::function<void(const
   BGP_HIP(bgp_memcpy_async(dH, q.h_kernel, (size_t)B * hp * sizeof(double), hipMemcpyHostToDevice, st));
   BGP_HIP(bgp_memcpy_async(dnoise, q.noise, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
   BGP_HIP(hipMemsetAsync(dbad, 0, (size_t)B * sizeof(int), st));
+  c->chunk_last[0] = c->chunk_last[1] = 0;
   for (int b0 = 0; b0 < B; b0 += Bc) {
+    c->chunk_last[0]++;
     const int nb = std::min(Bc, B - b0);
     const double* dHb = dH + (size_t)b0 * hp;
     const double* dAb = dA + (size_t)b0 * p.sAx;
@@ -92,6 +95,7 @@ int bgp_cond_run(bgp_ctx* c, const BgpCondReq& q, const std::function<void(const
     }
     for (int m0 = 0; m0 < m; m0 += mc) {
       const int mm = std::min(mc, m - m0), mmp = pad_to(mm, 128);  // (the strides of this chunk's moments: mmp)
+      if (b0 == 0) c->chunk_last[1]++;
       const double* dXq = dXc + (size_t)m0 * d;
       BGP_TRY(bgp_launch_moments(c, nb, dHb, mm, dXq, 0, c->dXeff, 0, al, Kinv, dKs, npad, p.sKs, dmpart, dmean, dvar));
       if (M > 0) {

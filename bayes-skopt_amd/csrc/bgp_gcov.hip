@@ -230,7 +230,8 @@ static int gcov_run(bgp_ctx* c, int B, const double* h_kernel, int m, const doub
   const size_t mc = std::min(gcov_point_chunk(npad, d), ((size_t)m + GC_RC - 1) / GC_RC * GC_RC);
   const size_t rows = (mc * d + 127) / 128 * 128, sR = rows * npad;  // a posterior's R (and P) of one point chunk
   // posteriors per chunk: R and P of a chunk within 2^29 doubles together
-  const int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)1 << 28) / sR));
+  // (BGP_ITEM_CHUNK, tests: forced posterior chunks against the default)
+  const int Bc = (int)bgp_switch_cap(BGP_SW_ITEM_CHUNK, std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)1 << 28) / sR)));
   const int nchmax = (int)(mc / GC_RC);
   double *dXq, *dH, *dR, *dP = nullptr, *dG, *dS = nullptr, *dpart = nullptr, *dacc = nullptr;
   BgpScratch live(c);
@@ -251,12 +252,15 @@ static int gcov_run(bgp_ctx* c, int B, const double* h_kernel, int m, const doub
   const int product = c->ks.form == BGP_FORM_PRODUCT;
   const auto blocks = [](size_t items) { return (unsigned)((items + 255) / 256); };
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, st));
+  c->chunk_last[0] = c->chunk_last[1] = 0;
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int nb = std::min(Bc, B - b0);
     const double* dHb = dH + (size_t)b0 * p;
+    c->chunk_last[0]++;
     if (csum) BGP_HIP(hipMemsetAsync(dacc, 0, (size_t)nb * E * sizeof(double), st));
     for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
       const int mm = (int)std::min(mc, (size_t)m - m0);
+      if (b0 == 0) c->chunk_last[1]++;
       const int md = mm * d, mdpad = (md + 127) / 128 * 128;
       BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)md * sizeof(double), hipMemcpyHostToDevice, st));
       KB_DISPATCH(c->ks.stationary, c->ks.form,

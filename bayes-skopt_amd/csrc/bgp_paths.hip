@@ -453,6 +453,7 @@ static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, doub
   const int P = s->P, d = s->d;
   // chunks of query rows: staged outputs of P mc (1 + d) doubles under the budget of the prediction gradients (2^24 doubles)
   size_t mc = std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)P * (1 + (size_t)d)));
+  mc = bgp_switch_cap(BGP_SW_ROW_CHUNK, mc);  // (tests: forced row chunks against the default; the rounding below still applies)
   if (mc >= 256) mc &= ~(size_t)255;
   mc = std::min(mc, (size_t)m);
   double *dXq, *dO, *dG = nullptr;
@@ -464,8 +465,10 @@ static int paths_eval_run(bgp_ctx* c, int m, const double* Xq, double* out, doub
   });
   if (rc) return rc;
   hipStream_t q = c->stream;
+  c->chunk_last[0] = 1, c->chunk_last[1] = 0;
   for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
     const int mm = (int)std::min(mc, (size_t)m - m0);
+    c->chunk_last[1]++;
     BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, q));
     BGP_TRY(bgp_paths_launch_eval(c, s, dXq, mm, dO, mc, dG));
     const size_t w1 = (size_t)mm * sizeof(double), wd = w1 * d;
@@ -498,7 +501,7 @@ static int paths_min_run(bgp_ctx* c, int S, const double* X0, const double* lo, 
   const int P = s->P, d = s->d, n = s->n;
   // chunks of starts: staged starts, end points, values, gradients and counters of P sc items under the budget of bgp_paths_eval
   size_t sc = std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)P * (3 + 3 * (size_t)d)));
-  sc = std::min(sc, (size_t)S);
+  sc = std::min(bgp_switch_cap(BGP_SW_ROW_CHUNK, sc), (size_t)S);  // (tests: forced chunks of starts against the default)
   const size_t Ps = (size_t)P * sc;
   double *dX0, *dXo, *dlo, *dhi, *df, *dg = nullptr;
   int *dit, *dev, *dst;
@@ -518,7 +521,9 @@ static int paths_min_run(bgp_ctx* c, int S, const double* X0, const double* lo, 
   hipStream_t q = c->stream;
   BGP_HIP(bgp_memcpy_async(dlo, lo, (size_t)d * sizeof(double), hipMemcpyHostToDevice, q));
   BGP_HIP(bgp_memcpy_async(dhi, hi, (size_t)d * sizeof(double), hipMemcpyHostToDevice, q));
+  c->chunk_last[0] = 1, c->chunk_last[1] = 0;
   for (size_t s0 = 0; s0 < (size_t)S; s0 += sc) {
+    c->chunk_last[1]++;
     const int ss = (int)std::min(sc, (size_t)S - s0);  // (the chunk's items are packed: item = path * ss + start)
     const size_t w1 = (size_t)ss * sizeof(double), wd = w1 * d, wi = (size_t)ss * sizeof(int);
     BGP_HIP(bgp_memcpy2d_async(dX0, wd, X0 + s0 * d, (size_t)S * d * sizeof(double), wd, P, hipMemcpyHostToDevice, q));
@@ -562,6 +567,16 @@ extern "C" int bgp_paths_end(bgp_ctx* c) {
     return BGP_ERR_INVALID;
   }
   paths_free(c);
+  return BGP_OK;
+}
+
+extern "C" int bgp_chunk_stats(bgp_ctx* c, long long* out) {
+  if (!c || !out) {
+    bgp_set_error("bgp_chunk_stats: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  out[0] = c->chunk_last[0];
+  out[1] = c->chunk_last[1];
   return BGP_OK;
 }
 

@@ -27,7 +27,7 @@ enum BgpSwitch {
   BGP_SW_STREAMS, BGP_SW_PERSIST, BGP_SW_PANEL_FUSED, BGP_SW_PANELS,
   BGP_SW_WAIT, BGP_SW_DEBUG_TIMES, BGP_SW_PS_COOLDOWN, BGP_SW_PS_TIMEOUT_MS, BGP_SW_PS_TIMEOUT_TICKS, BGP_SW_PS_PAIR, BGP_SW_PS_GEN,
   BGP_SW_PS_TRACE, BGP_SW_COMM_TIMEOUT_S,
-  BGP_SW_SYRK_GEN, BGP_SW_GCOV_CHUNK, BGP_SW_KG_CHUNK, BGP_SW_JES_CHUNK,
+  BGP_SW_SYRK_GEN, BGP_SW_GCOV_CHUNK, BGP_SW_KG_CHUNK, BGP_SW_JES_CHUNK, BGP_SW_ITEM_CHUNK, BGP_SW_ROW_CHUNK,
   BGP_SW_COUNT
 };
 enum BgpSwitchRead { BGP_READ_CONTEXT, BGP_READ_PROCESS, BGP_READ_CALL };
@@ -55,6 +55,8 @@ static const BgpSwitchRow bgp_switches[BGP_SW_COUNT] = {
     {"BGP_GCOV_CHUNK", BGP_READ_CALL, "by n and d", "query points per chunk of bgp_grad_cov, rounded up to 256 (tests: a small chunk against the default)"},
     {"BGP_KG_CHUNK", BGP_READ_CALL, "by n", "candidates per chunk of bgp_knowledge_gradient, rounded up to 128 (tests: a small chunk against the default)"},
     {"BGP_JES_CHUNK", BGP_READ_CALL, "by n", "candidates per chunk of bgp_joint_entropy, rounded up to 128 (tests: a small chunk against the default)"},
+    {"BGP_ITEM_CHUNK", BGP_READ_CALL, "by the scratch budget", "upper bound on the posteriors per chunk of the batched posterior calls (tests: forced chunks against the default)"},
+    {"BGP_ROW_CHUNK", BGP_READ_CALL, "by the scratch budget", "upper bound on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize (tests)"},
 };
 // read elsewhere: by the Python layer and bench.py, never by libbgp.so
 static const char* const bgp_switches_elsewhere[] = {"BGP_COMM_DIR", "BGP_COMM_PORT", "BGP_COMM_TCP", "BGP_COMM_JOB",
@@ -65,6 +67,13 @@ static inline const char* bgp_switch(BgpSwitch s) { return getenv(bgp_switches[s
 static inline int bgp_switch_tristate(BgpSwitch s) {
   const char* e = bgp_switch(s);
   return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+// BGP_ITEM_CHUNK / BGP_ROW_CHUNK: an UPPER bound on a chunk that a scratch budget has sized -- min(chunk, N), so the switch shrinks
+// a chunk and never enlarges it; unset, zero, negative or not a number: the budget alone decides
+static inline size_t bgp_switch_cap(BgpSwitch s, size_t chunk) {
+  const char* e = bgp_switch(s);
+  const long long v = e ? atoll(e) : 0;
+  return (v > 0 && (unsigned long long)v < chunk) ? (size_t)v : chunk;
 }
 static inline bool bgp_switch_known(const char* name, size_t len) {
   for (const BgpSwitchRow& r : bgp_switches)

@@ -155,9 +155,11 @@ static hipError_t rows_down(bgp_ctx* c, double* host, const double* dev, int w, 
 }
 
 // Items per chunk of a batched call: what `budget` doubles of scratch hold at `per_item` each; round8: whole rounds of the
-// item -> XCD pinning (rowquad4_kernel) when the batch takes more than one chunk.
+// item -> XCD pinning (rowquad4_kernel) when the batch takes more than one chunk.  BGP_ITEM_CHUNK (tests: forced chunks against the
+// default) bounds the budget's answer from above, in front of the rounding.
 static int post_chunk(int B, size_t per_item, size_t budget, bool round8) {
   int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, budget / per_item));
+  chunk = (int)bgp_switch_cap(BGP_SW_ITEM_CHUNK, (size_t)chunk);
   if (round8 && chunk >= 8 && chunk < B) chunk &= ~7;
   return chunk;
 }
@@ -413,8 +415,10 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   }
   const double* dXt = rowwarp ? (const double*)c->dXwP : (const double*)c->dXeff;
   BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  c->chunk_last[0] = 0, c->chunk_last[1] = 1;
   for (int off = 0; off < B; off += chunk) {
     const int nb = std::min(chunk, B - off);
+    c->chunk_last[0]++;
     const double* dHc = dH + (size_t)off * p;
     const double* Kinv = c->dKinv + (size_t)off * npad * npad;  // items off .. off+nb-1 are posteriors off .. off+nb-1
     const double* al = c->dalpha_sol + (size_t)off * npad;
@@ -497,8 +501,10 @@ extern "C" int bgp_predict_batch_gram(bgp_ctx* c, int B, int m, const double* Ks
         dCov = s.take<double>((size_t)chunk * sCv);
       }
     }));
+    c->chunk_last[0] = 0, c->chunk_last[1] = 1;
     for (int off = 0; off < B; off += chunk) {
       const int nb = std::min(chunk, B - off);
+      c->chunk_last[0]++;
       const double* Kinv = c->dKinv + (size_t)off * npad * npad;
       const double* al = c->dalpha_sol + (size_t)off * npad;
       // K_* with its zero padding (rows m .. mpad, columns n .. npad)
@@ -1215,8 +1221,10 @@ extern "C" int bgp_sample_y_batch(bgp_ctx* c, int B, const int* pidx, const doub
     BGP_TRY(post_stage_queries(c, dXq, Xq, m));
     BGP_HIP(bgp_memcpy_async(dH, h_kernel, (size_t)B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
     BGP_HIP(bgp_memcpy_async(dpidx, pidx, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    c->chunk_last[0] = 0, c->chunk_last[1] = 1;
     for (int off = 0; off < B; off += chunk) {
       const int nb = std::min(chunk, B - off);
+      c->chunk_last[0]++;
       const double* dHc = dH + (size_t)off * p;
       const int* dpc = dpidx + off;
       BGP_HIP(hipMemsetAsync(dZ, 0, (size_t)nb * mpad * sizeof(double), c->stream));

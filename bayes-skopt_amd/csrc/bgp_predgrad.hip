@@ -266,6 +266,7 @@ extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel,
     size_t mc = std::min<size_t>((size_t)m, 65535);
     mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 24) / ((size_t)B * (2 + 2 * (size_t)d))));
     if (!lds) mc = std::min(mc, std::max<size_t>(1, ((size_t)1 << 26) / ((size_t)B * 2 * npad)));
+    mc = bgp_switch_cap(BGP_SW_ROW_CHUNK, mc);  // (tests: forced row chunks against the default)
     const size_t Bm = (size_t)B * mc;
     double *dXq, *dH, *dm, *dv, *ddm, *ddv, *rows = nullptr;
     BgpScratch live(c);
@@ -281,8 +282,10 @@ extern "C" int bgp_predict_grad_batch(bgp_ctx* c, int B, const double* h_kernel,
     if (rc) return rc;
     const size_t shmem = lds ? 2 * (size_t)n * sizeof(double) : 0;
     BGP_HIP(bgp_memcpy_async(dH, h_kernel, B * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->chunk_last[0] = 1, c->chunk_last[1] = 0;
     for (size_t m0 = 0; m0 < (size_t)m; m0 += mc) {
       const int mm = (int)std::min(mc, (size_t)m - m0);
+      c->chunk_last[1]++;
       BGP_HIP(bgp_memcpy_async(dXq, Xq + m0 * d, (size_t)mm * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
       KB_DISPATCH(c->ks.stationary, c->ks.form,
                   hipLaunchKernelGGL((pg_rows_kernel<S, F>), dim3(mm, B), dim3(PG_NT), shmem, c->stream, c->dXeff, n, d, npad,

@@ -351,6 +351,11 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
  *   value at (path, row) does not depend on which rows or paths share the call.  BGP_ERR_STATE without a state.
  * bgp_paths_end drops the state; bgp_ctx_update_data and bgp_ctx_destroy drop it too.
  * bgp_paths_stats: out[0] = begins, out[1] = evals run on this context.
+ * bgp_chunk_stats: how the context's last call to an entry point that cuts its work by a scratch budget ran -- bgp_predict_batch /
+ *   _warped / _gram, bgp_acq_batch, bgp_predict_mixture, bgp_sample_y_batch, bgp_knowledge_gradient, bgp_joint_entropy, bgp_grad_cov,
+ *   bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize: out[0] = chunks of posteriors, out[1] = chunks of query rows,
+ *   candidates or starts (per chunk of posteriors); a loop the entry point does not have counts as one chunk.  Host counters only.
+ *   BGP_ITEM_CHUNK / BGP_ROW_CHUNK (below) force several chunks at small shapes (tests/test_gpu_chunk_loops.py).
  * bgp_paths_minimize: minimise every open path over the box [lo, hi] (d doubles each) from its OWN S starts,
  *   X0 P*S*d path-major, clipped into the box.  The objective is the path itself (normalised-y units).  ONE launch per chunk of
  *   starts, one workgroup per (start, path): a whole-workgroup evaluator of one path at one point (the identities above, every
@@ -369,6 +374,7 @@ int bgp_paths_begin(bgp_ctx* ctx, int P, const int* pidx, const double* h_kernel
 int bgp_paths_eval(bgp_ctx* ctx, int m, const double* Xq, double* out, double* dout);
 int bgp_paths_end(bgp_ctx* ctx);
 int bgp_paths_stats(bgp_ctx* ctx, long long* out2);
+int bgp_chunk_stats(bgp_ctx* ctx, long long* out2);
 int bgp_paths_minimize(bgp_ctx* ctx, int S, const double* X0, const double* lo, const double* hi, double gtol, int max_iter,
                        double* X_out, double* f_out, double* g_out, int* iters, int* evals, int* status);
 
@@ -606,7 +612,9 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
  *   256; default by n and d; read at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
- *   default by n; read at every call).
+ *   default by n; read at every call), BGP_ITEM_CHUNK / BGP_ROW_CHUNK (upper bounds on the posteriors per chunk of the batched posterior
+ *   calls and on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval and bgp_paths_minimize; default: the
+ *   scratch budgets alone; read at every call; a bound can shrink a chunk, never enlarge it: see bgp_chunk_stats).
  * Runtime switch set by the PYTHON package, not read by this library: bayes-skopt_amd/_lib.py exports HIP_FORCE_DEV_KERNARG=1 (kernel
  *   arguments in device memory: -6 % per call on the launch schedule at n = 1024 x 32) at import unless the user has set it --
  *   a process-wide setting that every other HIP user of the process inherits, effective only if the GPU has not been initialised

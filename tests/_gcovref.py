@@ -54,6 +54,9 @@ def _cases():
     out = [_case("gc%d_n%d_d%d_m%d_%s_%s" % (j, n, d, m, st, fm), n, d, st, fm, m, 2300 + j)
            for j, (n, d, st, fm, m) in enumerate(rows)]
     out.append(_case("gc_B3_n65_d3", 65, 3, "matern52", "product", 40, 2330, B=3, Buse=2))
+    # three posteriors, all used, over three point chunks of the forced 256: the forced posterior chunks of
+    # tests/test_gpu_chunk_loops.py run with both loop indices of gcov_run non-zero
+    out.append(_case("gc_B3_n64_d2_m600", 64, 2, "matern52", "product", 600, 2350, B=3, Buse=3))
     # query 0 IS training point 0, query 1 is 1e-8 from it in every coordinate, query 2 lies far outside the data
     out.append(_case("gc_special_n129_d3", 129, 3, "matern32", "product", 6, 2340, special=True))
     return out

@@ -84,6 +84,9 @@ def _cases():
            for j, (n, d, st, fm, R, m) in enumerate(rows)]
     # three resident posteriors, two used, each with its OWN optimum set
     out.append(_case("jes_B3_n65_d3", 65, 3, "matern52", "product", 10, 40, 2730, B=3, Buse=2))
+    # three posteriors, all used, over three candidate chunks of the forced 128: the forced posterior chunks of
+    # tests/test_gpu_chunk_loops.py run with both loop indices of bgp_cond_run non-zero
+    out.append(_case("jes_B3_n64_d2_R3_m300", 64, 2, "matern52", "product", 3, 300, 2760, B=3, Buse=3))
     # candidate 0 IS optimum point 0, candidate 1 IS training point 0, candidate 2 is 1e-8 from it, candidate 3 lies far outside the
     # data; optimum points 1 and 2 coincide; sample 5 has f_r = mu_r + 1e3 sqrt(v_r): z ~ 1e3
     out.append(_case("jes_special_n129_d3", 129, 3, "matern32", "product", 6, 8, 2740, special="points"))

@@ -63,6 +63,9 @@ def _cases():
     out = [_case("kg%d_n%d_d%d_M%d_m%d_%s_%s" % (j, n, d, M, m, st, fm), n, d, st, fm, M, m, 2500 + j)
            for j, (n, d, st, fm, M, m) in enumerate(rows)]
     out.append(_case("kg_B3_n65_d3", 65, 3, "matern52", "product", 10, 40, 2530, B=3, Buse=2))
+    # three posteriors, all used, over three candidate chunks of the forced 128: the forced posterior chunks of
+    # tests/test_gpu_chunk_loops.py run with both loop indices of bgp_cond_run non-zero
+    out.append(_case("kg_B3_n64_d2_M3_m300", 64, 2, "matern52", "product", 3, 300, 2560, B=3, Buse=3))
     # candidate 0 IS reference point 0, candidate 1 IS training point 0, candidate 2 is 1e-8 from it, candidate 3 lies far outside
     # the data; reference points 1 and 2 coincide
     out.append(_case("kg_special_n129_d3", 129, 3, "matern32", "product", 6, 8, 2540, special="points"))

@@ -296,6 +296,9 @@ def _predb_cases():
         (256, 2, 256, 1, ("matern32", "product"), True, True, 4),
         # both sides > 512
         (640, 5, 385, 3, ("matern52", "product"), True, True, 3),
+        # 17 items: two whole rounds of the item -> XCD pinning and one item more (the forced chunks of
+        # tests/test_gpu_chunk_loops.py: 8 + 8 + 1)
+        (64, 2, 33, 17, ("matern52", "product"), False, False, 5),
     ]
     out = []
     for j, (n, d, m, B, (st, fm), vec, cov, ns) in enumerate(rows):

@@ -251,10 +251,14 @@ def test_unknown_switch_is_reported():
     code = ("import sys, numpy as np; sys.path.insert(0, %r); import bayes_skopt_amd; from bayes_skopt_amd import _lib;"
             "c=_lib.Context(np.random.RandomState(0).rand(40,2), np.zeros(40), 1e-6, max_batch=2); print('ok')"
             ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, BGP_SYRK4="1", BGP_PANELS="2"), capture_output=True,
-                       text=True)
+    r = subprocess.run([sys.executable, "-c", code],
+                       env=dict(os.environ, BGP_SYRK4="1", BGP_PANELS="2", BGP_ITEM_CHUNK="2", BGP_ROW_CHUNK="32", BGP_ROWS_CHUNK="32"),
+                       capture_output=True, text=True)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-1500:]
     assert "BGP_SYRK4 is not one this library reads" in r.stderr and "BGP_PANELS" not in r.stderr
+    # the chunk bounds of the posterior entry points (tests/test_gpu_chunk_loops.py) are known; a misspelt one is not
+    assert "BGP_ITEM_CHUNK" not in r.stderr and "BGP_ROW_CHUNK" not in r.stderr
+    assert "BGP_ROWS_CHUNK is not one this library reads" in r.stderr
 
 
 def test_allocation_failure_is_an_error_and_the_library_stays_usable(lib, O):
