@@ -44,27 +44,26 @@ def _pd_tell_once(why):
         print("[bayes_skopt_amd] partial_dependence: through predict on synthesised rows (%s)" % why, file=sys.stderr, flush=True)
 
 
-PD_ROWS = 8192  # synthesised rows per predict of the fallback
+PD_ROWS = 8192  # synthesised rows per predict of the fallbacks
+
+
+def means_by_predict(gp, thetas, X):
+    """The (B, m) latent means at ``X`` of both ``*_by_predict`` fallbacks, normalised-target units.  ``thetas=None``: the resident
+    posterior with ``kernel_`` as it is (B = 1); otherwise one item per chain row -- under ``warp_inputs`` one row at a time with the
+    row's own warp (``BayesGPR._warped_rows_moments``), because every draw there has its own training inputs."""
+    if thetas is None:
+        return gp._post.predict(gp, X, False)[0]
+    if gp.warp_inputs:
+        return gp._warped_rows_moments(np.atleast_2d(thetas), X, True)[0]
+    return gp._post.hyper_predict(gp, np.atleast_2d(thetas), X, True)[0]
 
 
 def partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why):
     """The fallback of ``partial_dependence``: per panel, the sample rows with the panel's columns overwritten cell by cell, at most
-    ``PD_ROWS`` rows per ``predict``, the mean, the average over the samples.  ``thetas=None``: the resident posterior with
-    ``kernel_`` as it is; otherwise one item per chain row -- under ``warp_inputs`` one row at a time with the row's own warp
-    (``BayesGPR._row_warps``), because every draw there has its own training inputs."""
+    ``PD_ROWS`` rows per ``predict`` (``means_by_predict``), the mean, the average over the samples."""
     _pd_tell_once(why)
     Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
     S = Xs.shape[0]
-    rows = None if thetas is None else np.atleast_2d(thetas)
-
-    def means(X):
-        if rows is None:
-            return gp._post.predict(gp, X, False)[0]
-        if gp.warp_inputs:
-            with gp._row_warps() as install:
-                return np.stack([gp._post.rows_predict(gp, install(r), X, True)[0][0] for r in rows])
-        return gp._post.hyper_predict(gp, rows, X, True)[0]
-
     out = []
     for k1, k2 in panels:
         axes = [(k1, np.asarray(grids[k1], dtype=np.float64))] + ([(k2, np.asarray(grids[k2], dtype=np.float64))] if k2 >= 0 else [])
@@ -78,7 +77,7 @@ def partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why):
             for i, c in enumerate(cells):
                 for (k, g), gi in zip(axes, np.unravel_index(c, shape)):
                     X[i, :, k] = g[gi]
-            m = np.asarray(means(X.reshape(-1, Xs.shape[1])))
+            m = means_by_predict(gp, thetas, X.reshape(-1, Xs.shape[1]))
             if vals is None:
                 vals = np.empty((m.shape[0], ncell))
             vals[:, c0:c0 + len(cells)] = m.reshape(m.shape[0], len(cells), S).mean(axis=2)
@@ -136,28 +135,13 @@ def sobol_estimator(fA, fB, fT):
 
 def sensitivity_by_predict(gp, thetas, A, Bm, masks, why):
     """The fallback of ``sensitivity``: the means of A, Bm and every term's synthetic rows through ``predict``, at most ``PD_ROWS``
-    rows per call, then ``sobol_estimator`` in numpy.  ``thetas=None``: the resident posterior with ``kernel_`` as it is; otherwise
-    one item per chain row -- under ``warp_inputs`` one row at a time with the row's own warp (``BayesGPR._row_warps``).  Returns
-    (f0 (B,), V (B,), closed (B, T), total (B, T)) in normalised-target units."""
+    rows per call (``means_by_predict``), then ``sobol_estimator`` in numpy.  Returns (f0 (B,), V (B,), closed (B, T), total (B, T))
+    in normalised-target units."""
     _sens_tell_once(why)
     A, Bm = np.atleast_2d(np.asarray(A, dtype=np.float64)), np.atleast_2d(np.asarray(Bm, dtype=np.float64))
     N = A.shape[0]
-    rows = None if thetas is None else np.atleast_2d(thetas)
-
-    def means(X):
-        if rows is None:
-            return np.atleast_2d(gp._post.predict(gp, X, False)[0])
-        if gp.warp_inputs:
-            saved = (gp._post_theta, gp.alpha_)  # (installing a warp forgets the median GP's posterior: as BayesGPR.cross_validate)
-            try:
-                with gp._row_warps() as install:
-                    return np.stack([gp._post.rows_predict(gp, install(r), X, True)[0][0] for r in rows])
-            finally:
-                gp._post_theta, gp.alpha_ = saved
-        return np.asarray(gp._post.hyper_predict(gp, rows, X, True)[0])
-
     X = np.concatenate([A, Bm] + [sobol_rows(A, Bm, m) for m in masks])
-    F = np.concatenate([means(X[r0:r0 + PD_ROWS]) for r0 in range(0, len(X), PD_ROWS)], axis=1)
+    F = np.concatenate([means_by_predict(gp, thetas, X[r0:r0 + PD_ROWS]) for r0 in range(0, len(X), PD_ROWS)], axis=1)
     F = F.reshape(F.shape[0], len(masks) + 2, N)
     return sobol_estimator(F[:, 0], F[:, 1], F[:, 2:])
 
@@ -218,10 +202,20 @@ class CanonicalPosterior:
         raise_if_not_pd(gp._ctx.posterior(H, want_alpha=False)["status"], gp.kernel_)
         return H
 
+    def built_H(self, gp, thetas):
+        """The H to evaluate with: ``thetas=None``: the median GP made resident, with the kernel parameters currently in ``kernel_``
+        (B = 1); a block of chain rows: one batched build, their H."""
+        if thetas is None:
+            self.make_resident(gp)
+            return gp._canonical(gp._kernel_theta_for_predict())
+        return self.build_rows(gp, thetas)
+
+    def forget(self):
+        """A new context-level warp: nothing is mirrored here (``Context.set_warp`` drops ``resident_H`` itself)."""
+
     def predict(self, gp, X, return_cov):
         """(mean, var, cov | None) of the resident posterior, with the kernel parameters currently in ``kernel_``."""
-        self.make_resident(gp)
-        out = gp._ctx.predict(gp._canonical(gp._kernel_theta_for_predict()), X, return_cov=return_cov)
+        out = gp._ctx.predict(self.built_H(gp, None), X, return_cov=return_cov)
         return out if return_cov else (*out, None)
 
     def rows_predict(self, gp, thetas, X, noise_zero, return_cov=False):
@@ -278,16 +272,12 @@ class CanonicalPosterior:
     def predict_grad(self, gp, X, want_dvar=True):
         """(mean (m,), var (m,), dmean (m, d), dvar (m, d) | None) of the resident posterior at the rows of X, with the kernel
         parameters currently in ``kernel_``."""
-        self.make_resident(gp)
-        mean, var, dmean, dvar = gp._ctx.predict_grad(gp._canonical(gp._kernel_theta_for_predict()), X, want_dvar=want_dvar)
+        mean, var, dmean, dvar = gp._ctx.predict_grad(self.built_H(gp, None), X, want_dvar=want_dvar)
         return mean[0], var[0], dmean[0], (dvar[0] if want_dvar else None)
 
     def minimize(self, gp, kappa, X0, lo, hi, gtol=1e-5, max_iter=200):
         """Minima of mean + kappa std (y units) of the resident posterior over the box from every start, in one launch."""
-        self.make_resident(gp)
-        y_mean, y_std = float(np.ravel(gp.y_train_mean_)[0]), float(np.ravel(gp.y_train_std_)[0])
-        return gp._ctx.minimize_starts(0, gp._canonical(gp._kernel_theta_for_predict()), y_mean, y_std, kappa, X0, lo, hi,
-                                       gtol=gtol, max_iter=max_iter)
+        return gp._ctx.minimize_starts(0, self.built_H(gp, None), *gp._y_scale(), kappa, X0, lo, hi, gtol=gtol, max_iter=max_iter)
 
     def partial_dependence(self, gp, thetas, Xs, grids, panels):
         """(per panel a (B, G1) or (B, G1, G2) array in normalised-target units, "device" | "host").  ``thetas=None``: the resident
@@ -297,12 +287,7 @@ class CanonicalPosterior:
         if gp._X_train_.shape[1] > 32 or (thetas is not None and gp.warp_inputs):
             why = "more than 32 dimensions" if gp._X_train_.shape[1] > 32 else "hyper-posterior rows with input warping"
             return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why), "host"
-        if thetas is None:
-            self.make_resident(gp)
-            H = gp._canonical(gp._kernel_theta_for_predict())
-        else:
-            H = self.build_rows(gp, thetas)
-        return gp._ctx.partial_dependence(H, Xs, grids, panels), "device"
+        return gp._ctx.partial_dependence(self.built_H(gp, thetas), Xs, grids, panels), "device"
 
     def sensitivity(self, gp, thetas, A, Bm, masks):
         """((f0 (B,), V (B,), closed (B, T), total (B, T)) in normalised-target units, "device" | "host").  ``thetas=None``: the
@@ -312,12 +297,7 @@ class CanonicalPosterior:
         if gp._X_train_.shape[1] > SENS_DMAX or (thetas is not None and gp.warp_inputs):
             why = "more than 32 dimensions" if gp._X_train_.shape[1] > SENS_DMAX else "hyper-posterior rows with input warping"
             return sensitivity_by_predict(gp, thetas, A, Bm, masks, why), "host"
-        if thetas is None:
-            self.make_resident(gp)
-            H = gp._canonical(gp._kernel_theta_for_predict())
-        else:
-            H = self.build_rows(gp, thetas)
-        return gp._ctx.sobol_indices(H, A, Bm, masks), "device"
+        return gp._ctx.sobol_indices(self.built_H(gp, thetas), A, Bm, masks), "device"
 
     gradient_cov_path = "auto"  # "host": always numpy on the downloaded inverse (tests compare the two paths)
 
@@ -338,11 +318,10 @@ class CanonicalPosterior:
             return (dmean if want[0] else None, cov if want[1] else None, csum), "host"
         call = lambda H: gp._ctx.grad_cov(H, X, want_dmean=want[0], want_cov=want[1], want_csum=want[2])  # noqa: E731
         if thetas is None:
-            self.make_resident(gp)
-            return call(gp._canonical(gp._kernel_theta_for_predict())), "device"
+            return call(self.built_H(gp, None)), "device"
         thetas = np.atleast_2d(thetas)
         step = max(1, int(gp._ctx.max_batch))  # (the batched build holds max_batch rows: one build and one call per block)
-        parts = [call(self.build_rows(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]
+        parts = [call(self.built_H(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]
         return tuple(np.concatenate([p[i] for p in parts]) if want[i] else None for i in range(3)), "device"
 
     def cross_validate(self, gp, thetas, folds, warps=None):
@@ -375,7 +354,11 @@ class GramPosterior:
     canonical = False
 
     def __init__(self):
-        self._resident = None  # theta whose posterior the device holds (every posterior_gram overwrites it)
+        self._resident = None  # theta whose posterior the device holds under the CURRENT warp (every posterior_gram overwrites it)
+
+    def forget(self):
+        """A new context-level warp: the host Gram matrices depend on it, so what the device holds is nobody's posterior now."""
+        self._resident = None
 
     def _posterior_gram(self, gp, K, theta=None, **want):
         self._resident = None

@@ -407,15 +407,11 @@ def _host_rows(gp, rows, X, points, noise_of, value, n_samples):
         return row_values(None, gp._post_theta, 0)
     total = np.zeros(m)
     n_theta = len(gp.kernel_.theta)
-    saved = (gp._post_theta, gp.alpha_)
-    try:
-        if gp.warp_inputs:
-            with gp._row_warps() as install:
-                vals = [row_values(install(r), r[:n_theta], b) for b, r in enumerate(rows)]
-        else:
-            vals = [row_values(r[None, :], r, b) for b, r in enumerate(rows)]
-    finally:
-        gp._post_theta, gp.alpha_ = saved
+    if gp.warp_inputs:
+        with gp._row_warps() as install:
+            vals = [row_values(install(r), r[:n_theta], b) for b, r in enumerate(rows)]
+    else:
+        vals = [row_values(r[None, :], r, b) for b, r in enumerate(rows)]
     for v in vals:
         if np.all(np.isfinite(v)):
             total += v / n_samples
@@ -426,7 +422,7 @@ def _kg_host(gp, rows, X, A, n_samples, why):
     """The host path: the lines of every candidate from the joint moments of [A; chunk] (``_host_rows``; the observation's noise
     is not floored), ``knowledge_gradient_values``; written only where ``s > 0``.  Returns (m,) in y units."""
     _tell_once("knowledge_gradient", why)
-    y_std = float(np.ravel(gp.y_train_std_)[0])
+    y_std = gp._y_scale()[1]
     base = gp._fantasy_base_alpha()
 
     def value(out, b, noise, mean_p, var_p, mean_c, v, cov):
@@ -478,7 +474,7 @@ class KnowledgeGradient(FullGPAcquisition):
         if why is not None:
             vals = _kg_host(gp, rows, X, A, max(int(n_gp_samples), 1), why)
             return (vals, "host") if return_path else vals
-        y_std = float(np.ravel(gp.y_train_std_)[0])
+        y_std = gp._y_scale()[1]
         if rows is None:
             gp._post.make_resident(gp)
             H = gp._canonical(gp._post_theta)
@@ -599,7 +595,7 @@ class JointEntropySearch(FullGPAcquisition):
         if n_gp_samples > 0:
             rows = gp.chain_[rng.choice(len(gp.chain_), replace=False, size=int(n_gp_samples))]
         B = 1 if rows is None else len(rows)
-        y_mean, y_std = float(np.ravel(gp.y_train_mean_)[0]), float(np.ravel(gp.y_train_std_)[0])
+        y_mean, y_std = gp._y_scale()
         if optimum_samples is None:
             thetas = np.asarray(gp._post_theta, dtype=np.float64)[None, :] if rows is None else rows
             with gp._sample_paths_rows(thetas, int(n_optima), n_features, rng) as paths:

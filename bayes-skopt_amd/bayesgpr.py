@@ -130,9 +130,8 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         rebuilt from the stored training data the first time something needs it."""
         if self._ctx_obj is None and self._needs_rebuild:
             self._needs_rebuild = False
-            saved = (self._post_theta, self.alpha_, self._L, self._K_inv)
-            self._ensure_context()
-            self._post_theta, self.alpha_, self._L, self._K_inv = saved
+            with self._keeping_posterior():
+                self._ensure_context()
         return self._ctx_obj
 
     @_ctx.setter
@@ -197,9 +196,16 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         """Make the device context see the training inputs (and later query points) through the current
         warpers -- the role of ``rewarp()`` in the reference (``bask/bayesgpr.py:284-295``)."""
         if self._ctx is not None:
-            self._ctx.set_warp(self._warp_vector())
-            self._post_theta = None
+            self._post_theta = None  # (first: a set_warp that raises leaves no posterior claimed under a warp it was not built with)
             self._L = self._K_inv = None
+            self._backend.forget()
+            self._ctx.set_warp(self._warp_vector())
+
+    def _scratch_context(self):
+        """A device context of its own on the training set, as large as the estimator's: what runs there leaves the estimator's
+        context and its resident posteriors as they are."""
+        return _lib.Context(self._X_train_, self.y_train_, self._alpha_diag(), form=self._plan.form,
+                            stationary=self._plan.stationary, max_batch=self._ctx.max_batch, device=self.device)
 
     def _canonical(self, theta):
         return self._plan.canonical(theta, self._X_train_.shape[1])
@@ -261,6 +267,27 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         self.alpha_ = self._post.posterior(self, theta)
         self._post_theta = np.array(theta, copy=True)
         self._L = self._K_inv = None
+
+    @contextmanager
+    def _keeping_posterior(self, undo=None):
+        """The one keeper of the median GP's bookkeeping: what the block does may forget it (a rebuilt
+        context, another row's warp) although the median GP has not changed; on exit, however the block is left, ``undo()`` runs
+        and then ``_post_theta`` / ``alpha_`` / ``L_`` / ``K_inv_`` are back.  An ``undo`` that raises leaves them forgotten."""
+        saved = (self._post_theta, self.alpha_, self._L, self._K_inv)
+        try:
+            yield
+        finally:
+            if undo is not None:
+                undo()
+            self._post_theta, self.alpha_, self._L, self._K_inv = saved
+
+    def _require_posterior(self, what="predict"):
+        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
+            raise RuntimeError(what + " before fit is not supported on the MI355X path")
+
+    def _y_scale(self):
+        """(mean, std) of the y normalisation as two floats."""
+        return float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
 
     def _fetch_factor(self, which):
         if self._post_theta is None:
@@ -641,8 +668,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             raise NotImplementedError("Not implemented for n_samples > 1")
         if self.warp_inputs:
             validate_zeroone(X)  # the device warps the query points with the context-level warp
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         mean, var, cov = self._post.predict(self, X, return_cov)
         y_mean = self.y_train_std_ * mean[0] + self.y_train_mean_
         if return_cov:
@@ -685,8 +711,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         if self.warp_inputs:
             validate_zeroone(X)
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         if not (self._post.canonical and self._post.device_gradients(self)):
             rows = [self.predict(x[None, :], return_std=return_std, return_mean_grad=True, return_std_grad=return_std) for x in X]
             if return_std:
@@ -714,8 +739,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         ``warp_inputs`` is applied to samples and grids on the device).  Generic kernel trees, more dimensions, and chain rows
         under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" | "host"."""
         Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         d = self._X_train_.shape[1]
         grids = [np.asarray(g, dtype=np.float64).reshape(-1) for g in grids]
         if Xs.shape[1] != d or len(grids) != d:
@@ -753,8 +777,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         rows under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" |
         "host"."""
         A, Bm = np.atleast_2d(np.asarray(A, dtype=np.float64)), np.atleast_2d(np.asarray(Bm, dtype=np.float64))
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         d = self._X_train_.shape[1]
         if A.shape[1] != d or Bm.shape != A.shape or A.shape[0] < 1:
             raise ValueError(f"A and Bm must both be (N, {d}) with N >= 1, got {A.shape} and {Bm.shape}")
@@ -763,7 +786,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             validate_zeroone(Bm)
         masks = sobol_masks([(k,) for k in range(d)] if terms is None else terms, d)
         (f0, V, closed, total), path = self._post.sensitivity(self, thetas, A, Bm, masks)
-        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        y_mean, y_std = self._y_scale()
         out = (y_std * f0 + y_mean, y_std**2 * V, y_std**2 * closed, y_std**2 * total)
         if thetas is None:
             out = tuple(v[0] for v in out)
@@ -771,8 +794,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
 
     def _gradient_cov(self, X, thetas, want):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         d = self._X_train_.shape[1]
         if X.shape[1] != d or X.shape[0] < 1:
             raise ValueError(f"the points must be (m, {d}) with m >= 1, got {X.shape}")
@@ -788,7 +810,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         said once on stderr.  Matern 1/2 is not differentiable: ValueError.  Generic kernel trees and ``warp_inputs=True``:
         NotImplementedError.  ``return_path``: also "device" | "host"."""
         (dmean, cov, _), path = self._gradient_cov(X, thetas, (True, True, False))
-        y_std = float(np.ravel(self.y_train_std_)[0])
+        y_std = self._y_scale()[1]
         out = (y_std * dmean, y_std**2 * cov)
         if thetas is None:
             out = tuple(v[0] for v in out)
@@ -800,7 +822,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         (d, d) in y units squared per unit of transformed coordinate squared, or (B, d, d) for a block of B chain rows.  On the
         device path only the two sums come back.  Paths and refusals as ``gradient_posterior``."""
         (_, _, csum), path = self._gradient_cov(Xs, thetas, (False, False, True))
-        y_std = float(np.ravel(self.y_train_std_)[0])
+        y_std = self._y_scale()[1]
         out = (y_std**2 * csum[:, 0], y_std**2 * csum[:, 1])
         if thetas is None:
             out = tuple(v[0] for v in out)
@@ -827,8 +849,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         ``fold_lpd`` (K,; log density of the whole fold, correlations included), ``elpd = sum(fold_lpd)`` and the effective
         number of rows ``ess`` (K,) behind every fold's weights.  A fold whose block of the inverse is not numerically positive
         definite raises ``LinAlgError``."""
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         if weights not in ("is", "equal"):
             raise ValueError(f"weights must be 'is' or 'equal', got {weights!r}")
         n = self._X_train_.shape[0]
@@ -848,16 +869,12 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             elif post.canonical:
                 out = post.cross_validate(self, rows[:, :n_theta], folds, warps=np.ascontiguousarray(rows[:, n_theta:]))
             else:  # a generic kernel tree sees a row's warp through the estimator's warpers: one row after the other
-                saved = (self._post_theta, self.alpha_)
-                try:
-                    with self._row_warps() as install:
-                        parts = [post.cross_validate(self, install(r), folds) for r in rows]
-                finally:
-                    self._post_theta, self.alpha_ = saved
+                with self._row_warps() as install:
+                    parts = [post.cross_validate(self, install(r), folds) for r in rows]
                 out = tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
         mean, var, lpd, status = out
         raise_if_not_pd(status.ravel(), self.kernel_)
-        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        y_mean, y_std = self._y_scale()
         sizes = np.array([len(f) for f in folds], dtype=np.float64)
         row_mean, row_var = mean * y_std + y_mean, var * y_std**2
         row_lpd = lpd - sizes[None, :] * np.log(y_std)
@@ -870,7 +887,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
     def _row_warps(self):
         """Yields ``install(row)``, which gives the estimator chain row ``row``'s own input warp (its own training inputs)
         and returns the row's kernel parameters as a (1, p) block; the current warpers are back on exit, however it is left
-        (``bask/acquisition.py:142-145``)."""
+        (``bask/acquisition.py:142-145``), and behind them the median GP's posterior (``_keeping_posterior``)."""
         n_theta, d = len(self.kernel_.theta), self._X_train_.shape[1]
         backup = (np.copy(self.warp_alphas_), np.copy(self.warp_betas_))
 
@@ -879,11 +896,22 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             self.rewarp()
             return row[None, :n_theta]
 
-        try:
-            yield install
-        finally:
+        def put_back():
             self.create_warpers(*backup)
             self.rewarp()
+
+        with self._keeping_posterior(put_back):
+            yield install
+
+    def _warped_rows_moments(self, rows, X, noise_zero):
+        """Normalised (mean, var), each (B, m), of the GPs of chain ``rows`` at ``X``, one row's warp after the other: one build +
+        predict per row (``_row_warps``)."""
+        mean, var = np.empty((len(rows), X.shape[0])), np.empty((len(rows), X.shape[0]))
+        with self._row_warps() as install:
+            for i, row in enumerate(rows):
+                m, v, _ = self._post.rows_predict(self, install(row), X, noise_zero)
+                mean[i], var[i] = m[0], v[0]
+        return mean, var
 
     _warp_rows_path = "auto"  # "loop": hyper-posterior rows under input warping one at a time (tests compare the two)
 
@@ -905,11 +933,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                                                  warps=np.ascontiguousarray(rows[:, n_theta:]))
         elif self.warp_inputs:
             validate_zeroone(X)
-            mean, var = np.empty((len(rows), X.shape[0])), np.empty((len(rows), X.shape[0]))
-            with self._row_warps() as install:
-                for i, row in enumerate(rows):
-                    m, v, _ = self._post.rows_predict(self, install(row), X, noise_zero)
-                    mean[i], var[i] = m[0], v[0]
+            mean, var = self._warped_rows_moments(rows, X, noise_zero)
         else:
             mean, var = self._post.hyper_predict(self, rows, X, noise_zero)
         return self.y_train_std_ * mean + self.y_train_mean_, np.sqrt(var * self.y_train_std_**2)
@@ -937,8 +961,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         if self.warp_inputs:
             validate_zeroone(X)
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("predict before fit is not supported on the MI355X path")
+        self._require_posterior()
         if thetas is None:
             chain = np.asarray(self.chain_)
             rng = check_random_state(random_state)
@@ -946,7 +969,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         else:
             rows = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
         probs = np.asarray(quantiles if quantiles is not None else [], dtype=np.float64).ravel()
-        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
+        y_mean, y_std = self._y_scale()
         post, ctx = self._post, self._ctx
         if post.canonical and len(rows) <= ctx.max_batch and self._warp_rows_path == "auto":
             if self.warp_inputs:
@@ -978,8 +1001,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         ``evaluate_acquisitions`` (``bask/acquisition.py:112-139``) -- only (len(kinds), m) numbers come back."""
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         H = self._post.build_rows(self, thetas)
-        y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
-        return self._ctx.acq(noise_off(H) if noise_zero else H, X, y_mean, y_std, kinds, params, n_samples)
+        return self._ctx.acq(noise_off(H) if noise_zero else H, X, *self._y_scale(), kinds, params, n_samples)
 
     def _pvrs(self, X, thompson_points, has_alpha_vec):
         """Device side of PVRS / VarianceReduction (``bask/acquisition.py:287-300,328-338``)."""
@@ -1004,7 +1026,8 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         if not 1 <= q <= X.shape[0]:
             raise ValueError(f"a batch of {q} points from {X.shape[0]} candidates")
-        lie_n = None if lie is None else (float(lie) - float(np.ravel(self.y_train_mean_)[0])) / float(np.ravel(self.y_train_std_)[0])
+        y_mean, y_std = self._y_scale()
+        lie_n = None if lie is None else (float(lie) - y_mean) / y_std
         spec = A._device_acq_spec(acq, acq_kwargs) if isinstance(acq, A.UncertaintyAcquisition) else None
         fast = (path != "fallback" and spec is not None and A.DEVICE_ACQUISITIONS and not self.warp_inputs
                 and self._post.canonical and X.shape[1] <= 32)
@@ -1026,16 +1049,14 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         import time
 
         H = self._canonical(np.atleast_2d(rows))
-        ctx = _lib.Context(self._X_train_, self.y_train_, self._alpha_diag(), form=self._plan.form,
-                           stationary=self._plan.stationary, max_batch=self._ctx.max_batch, device=self.device)
+        ctx = self._scratch_context()
         info = {"step_ms": []}
         try:
             raise_if_not_pd(ctx.posterior(H, want_alpha=False)["status"], self.kernel_)
             Hk = noise_off(H)
             noise = self._fantasy_base_alpha() + np.exp(H[:, -1])
-            y_mean, y_std = float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0])
             t0 = time.perf_counter()
-            ctx.fantasy_begin(Hk, noise, X, y_mean, y_std, [spec[0]], [spec[1]], n_samples, max(q - 1, 1))
+            ctx.fantasy_begin(Hk, noise, X, *self._y_scale(), [spec[0]], [spec[1]], n_samples, max(q - 1, 1))
             info["begin_ms"] = (time.perf_counter() - t0) * 1e3
             picks, values = [int(first)], []
             for _ in range(q - 1):
@@ -1067,7 +1088,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         scratch.kernel_ = copy.deepcopy(self.kernel_)
         full = isinstance(acq, A.FullGPAcquisition)
         own = full and type(acq) not in (A.PVRS, A.VarianceReduction)  # a whole-GP acquisition evaluated as itself
-        X0, y0 = self._X_train_, self.y_train_
+        X0, y0, (y_mean, y_std) = self._X_train_, self.y_train_, self._y_scale()
         alpha0 = np.asarray(self.alpha, dtype=np.float64) if np.iterable(self.alpha) else None
         picks, values, info = [int(first)], [], {"step_ms": []}
         try:
@@ -1084,7 +1105,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                 t0 = time.perf_counter()
                 scratch._X_train_ = np.vstack([X0, X[picks]])
                 if own and lie_n is None:  # the median GP's own means at the chosen points, normalised
-                    lies = (mus0[0, picks] - np.ravel(self.y_train_mean_)[0]) / np.ravel(self.y_train_std_)[0]
+                    lies = (mus0[0, picks] - y_mean) / y_std
                 else:  # (PVRS / VR and the variances do not read y)
                     lies = np.full(j, 0.0 if lie_n is None else lie_n)
                 scratch.y_train_ = np.concatenate([y0, lies])
@@ -1214,8 +1235,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         why = None if getattr(self, "_X_train_", None) is None else self._pathwise_obstacle()
         if why is not None:
             raise ValueError("sample_paths does not support %s" % why)
-        if self._post_theta is None or getattr(self, "_X_train_", None) is None:
-            raise RuntimeError("sample_paths before fit is not supported on the MI355X path")
+        self._require_posterior("sample_paths")
         n_paths, F = int(n_paths), int(n_features)
         if n_paths < 1 or not 1 <= F <= 65536:
             raise ValueError("sample_paths needs n_paths >= 1 and 1 <= n_features <= 65536")
@@ -1248,15 +1268,14 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         n, d = self._X_train_.shape
         omega, phase, w, eps = draw_path_variates(rng, n_paths, F, d, n, self._plan.stationary)
         uniq, inverse = np.unique(H, axis=0, return_inverse=True)  # repeated chain rows share one posterior build
-        ctx = _lib.Context(self._X_train_, self.y_train_, self._alpha_diag(), form=self._plan.form,
-                           stationary=self._plan.stationary, max_batch=self._ctx.max_batch, device=self.device)
+        ctx = self._scratch_context()
         try:
             raise_if_not_pd(ctx.posterior(uniq, want_alpha=False)["status"], self.kernel_)
             ctx.paths_begin(np.asarray(inverse, dtype=np.int32).ravel(), noise_off(H), H[:, -1], omega, phase, w, eps)
         except BaseException:
             ctx.close()
             raise
-        return PosteriorPaths(ctx, float(np.ravel(self.y_train_mean_)[0]), float(np.ravel(self.y_train_std_)[0]), n_paths, d)
+        return PosteriorPaths(ctx, *self._y_scale(), n_paths, d)
 
     def _draw_rows_reference(self, rows, X, rng, noise):
         """The reference's per-sample loop (``bask/bayesgpr.py:679-706``) with the device doing what the theta setter

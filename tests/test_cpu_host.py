@@ -382,6 +382,72 @@ def test_bayesgpr_host_semantics_without_device(bask):
         _eval_priors(vec[:1], Theta)
 
 
+def test_the_keeper_of_the_median_posterior_without_a_device(bask):
+    """DESIGN.md section 28 on a stub context: ``_row_warps`` (through ``_keeping_posterior``) puts the warpers and then the median
+    GP's bookkeeping back on a normal exit and on an exception; a restoring ``set_warp`` that raises leaves the estimator without a
+    posterior; every ``_install_warp`` makes the generic backend forget what it believed resident."""
+    from bayes_skopt_amd._posterior import GramPosterior
+
+    class Ctx:
+        def __init__(self, fail_at):
+            self.seen, self.fail_at = [], fail_at
+
+        def set_warp(self, w):
+            self.seen.append(np.array(w))
+            if len(self.seen) == self.fail_at:
+                raise RuntimeError("set_warp failed")
+
+    own = (np.array([0.1, -0.2]), np.array([0.3, 0.05]))
+    row = np.array([0.0, -1.0, -1.2, 0.4, 0.5, -0.6, -0.7])  # three kernel parameters, then the row's 2 + 2 warp parameters
+
+    def estimator(fail_at=None):
+        gp = bask.BayesGPR(kernel=bask.construct_default_kernel([0, 1]), warp_inputs=True)
+        gp.kernel_ = gp.kernel
+        gp._X_train_ = np.random.RandomState(0).uniform(size=(6, 2))
+        gp.create_warpers(*own)
+        gp._ctx_obj, gp._backend = Ctx(fail_at), GramPosterior()
+        kept = (np.arange(3.0), np.ones(6), np.eye(6), 2.0 * np.eye(6))
+        gp._post_theta, gp.alpha_, gp._L, gp._K_inv = kept
+        gp._backend._resident = np.arange(3.0)
+        return gp, kept
+
+    def walk(gp, fail=False):
+        with gp._row_warps() as install:
+            assert np.array_equal(install(row), row[None, :3])
+            assert gp._post_theta is None and gp._L is None and gp._K_inv is None and gp._backend._resident is None
+            assert np.array_equal(gp.warp_alphas_, row[3:5]) and np.array_equal(gp.warp_betas_, row[5:])
+            gp._backend._resident = np.arange(3.0)  # (what a build under the row's warp leaves behind)
+            if fail:
+                raise KeyError("inside the block")
+
+    def is_back(gp, kept):
+        now = (gp._post_theta, gp.alpha_, gp._L, gp._K_inv)
+        return all(a is b for a, b in zip(now, kept))
+
+    for fail in (False, True):
+        gp, kept = estimator()
+        if fail:
+            with pytest.raises(KeyError):
+                walk(gp, fail=True)
+        else:
+            walk(gp)
+        assert is_back(gp, kept) and gp._backend._resident is None
+        assert np.array_equal(gp.warp_alphas_, own[0]) and np.array_equal(gp.warp_betas_, own[1])
+        assert len(gp._ctx_obj.seen) == 2  # the row's warp, then the estimator's own
+        assert np.array_equal(gp._ctx_obj.seen[0], row[3:]) and np.array_equal(gp._ctx_obj.seen[1], np.concatenate(own))
+    gp, kept = estimator(fail_at=2)  # putting the warp back fails: no posterior is claimed
+    with pytest.raises(RuntimeError, match="set_warp failed"):
+        walk(gp)
+    assert gp._post_theta is None and gp._L is None and gp._K_inv is None and gp._backend._resident is None
+    with pytest.raises(RuntimeError, match="predict before fit is not supported on the MI355X path"):
+        gp.predict(np.full((1, 2), 0.5))
+    gp, kept = estimator()  # the keeper alone, as the `_ctx` property uses it around a rebuilt context
+    with gp._keeping_posterior():
+        gp._install_warp()
+        assert gp._post_theta is None and gp._backend._resident is None
+    assert is_back(gp, kept)
+
+
 def test_hdi_unimodal_is_narrowest_interval_and_multimodal_splits():
     """utils.hdi restates arviz.hdi (bask/optimizer.py:684): the unimodal estimator is the narrowest interval
     holding hdi_prob of the sorted sample (checked against brute force), the multimodal one returns one interval

@@ -324,8 +324,9 @@ def test_predict_hyper_samples_takes_the_batched_path_with_the_loops_bits(bask, 
     finally:
         restore()
         del gp._warp_rows_path
-        gp.theta = gp.theta  # (the loop leaves the estimator without a posterior, as it always has: build the median GP's again)
+    after_loop = gp.predict(Xq, return_std=True)  # (the loop keeps the median GP's posterior: DESIGN.md section 28)
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])
+    assert np.array_equal(before[0], after_loop[0]) and np.array_equal(before[1], after_loop[1])
     assert mus.shape == (len(rows), len(Xq)) and np.all(np.isfinite(mus)) and np.all(stds > 0)
     assert np.array_equal(mus, mus_l) and np.array_equal(stds, stds_l)
     assert np.array_equal(gp.warp_alphas_, warpers[0]) and np.array_equal(gp.warp_betas_, warpers[1])
@@ -335,15 +336,17 @@ def test_acquisitions_keep_their_bits(bask, warped_gp):
     gp = warped_gp
     Xq = np.random.RandomState(33).uniform(size=(25, 2))
     acqs = [bask.acquisition.ExpectedImprovement(), bask.acquisition.LCB()]
+    before = gp.predict(Xq, return_std=True)
     vals = bask.acquisition.evaluate_acquisitions(Xq, gp, acqs, n_samples=6, random_state=0)
     gp._warp_rows_path = "loop"
     try:
         vals_l = bask.acquisition.evaluate_acquisitions(Xq, gp, acqs, n_samples=6, random_state=0)
     finally:
         del gp._warp_rows_path
-        gp.theta = gp.theta  # (see above)
+    after_loop = gp.predict(Xq, return_std=True)
     assert vals.shape == (2, 25) and np.all(np.isfinite(vals))
     assert np.array_equal(vals, vals_l)
+    assert np.array_equal(before[0], after_loop[0]) and np.array_equal(before[1], after_loop[1])
 
 
 def test_optimizer_proposes_the_same_points_on_both_paths(bask, monkeypatch):
@@ -367,14 +370,20 @@ def test_optimizer_proposes_the_same_points_on_both_paths(bask, monkeypatch):
     assert np.array_equal(asked, asked_l) and np.array_equal(vals, vals_l)
 
 
-def test_a_generic_kernel_tree_keeps_the_loop(bask):
+@pytest.fixture(scope="module")
+def generic_gp(bask):
     from sklearn.gaussian_process import kernels as sk
 
     X, y = _data(30, 1, 34)
     kernel = sk.Matern(length_scale=0.4, nu=2.5) + sk.Matern(length_scale=1.5, nu=1.5)
     gp = bask.BayesGPR(kernel=kernel, random_state=2, warp_inputs=True)
     gp.fit(X, y, n_desired_samples=20, n_burnin=2, n_walkers_per_thread=10, progress=False)
-    assert gp._generic and not gp._post.canonical
+    assert gp._generic and not gp._post.canonical and gp.chain_.shape == (20, 3 + 2)
+    return gp
+
+
+def test_a_generic_kernel_tree_keeps_the_loop(generic_gp):
+    gp = generic_gp
     rows = gp.chain_[:3]
     calls, restore = _count_set_warp(gp)
     try:
@@ -383,3 +392,80 @@ def test_a_generic_kernel_tree_keeps_the_loop(bask):
         restore()
     assert len(calls) == len(rows) + 1
     assert mus.shape == (3, 7) and np.all(np.isfinite(mus)) and np.all(stds > 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the median GP's posterior survives every walk over chain rows under their own warps
+# ------------------------------------------------------------------------------------------------------------------------------
+def _median_state(gp, Xq):
+    assert gp._post_theta is not None
+    return {"post_theta": gp._post_theta.copy(), "alpha_": gp.alpha_.copy(), "warp_alphas_": gp.warp_alphas_.copy(),
+            "warp_betas_": gp.warp_betas_.copy(), **dict(zip(("mean", "std"), gp.predict(Xq, return_std=True)))}
+
+
+def _assert_median_state(gp, Xq, before):
+    after = _median_state(gp, Xq)
+    for k in before:
+        assert np.array_equal(before[k], after[k]), k
+
+
+def _on_the_loop(gp, call):
+    gp._warp_rows_path = "loop"
+    try:
+        return call()
+    finally:
+        del gp._warp_rows_path
+
+
+def _acqs(bask, gp, Xq):
+    acqs = [bask.acquisition.ExpectedImprovement(), bask.acquisition.LCB()]
+    return bask.acquisition.evaluate_acquisitions(Xq, gp, acqs, n_samples=6, random_state=0)
+
+
+_GRID = np.linspace(0.1, 0.9, 4)
+SURVIVES = {  # name: (fixture, the call on (bask, gp, Xq))
+    "canonical-predict_hyper_samples-loop": ("warped_gp", lambda bask, gp, Xq: _on_the_loop(
+        gp, lambda: gp._predict_hyper_samples(gp.chain_, Xq))),
+    "canonical-evaluate_acquisitions-loop": ("warped_gp", lambda bask, gp, Xq: _on_the_loop(gp, lambda: _acqs(bask, gp, Xq))),
+    "canonical-partial_dependence": ("warped_gp", lambda bask, gp, Xq: gp.partial_dependence(
+        Xq[:5], [_GRID] * 2, thetas=gp.chain_[:3])),
+    "canonical-sensitivity": ("warped_gp", lambda bask, gp, Xq: gp.sensitivity(Xq[:8], Xq[8:16], thetas=gp.chain_[:3])),
+    "canonical-sample_y-reference": ("warped_gp", lambda bask, gp, Xq: gp.sample_y(
+        Xq, sample_mean=False, n_samples=3, random_state=0, mvn="reference")),
+    "canonical-sample_y-cholesky": ("warped_gp", lambda bask, gp, Xq: gp.sample_y(
+        Xq, sample_mean=False, n_samples=3, random_state=0, mvn="cholesky")),
+    "canonical-kg-host": ("warped_gp", lambda bask, gp, Xq: bask.acquisition.KnowledgeGradient()(
+        Xq, gp, n_reference=5, n_gp_samples=3, random_state=0, return_path=True)),
+    "generic-predict_hyper_samples": ("generic_gp", lambda bask, gp, Xq: gp._predict_hyper_samples(gp.chain_, Xq)),
+    "generic-cross_validate": ("generic_gp", lambda bask, gp, Xq: gp.cross_validate(thetas=gp.chain_, n_folds=3, random_state=0)),
+    "generic-partial_dependence": ("generic_gp", lambda bask, gp, Xq: gp.partial_dependence(Xq[:5], [_GRID], thetas=gp.chain_)),
+    "generic-evaluate_acquisitions": ("generic_gp", _acqs),
+}
+
+
+@pytest.mark.parametrize("case", list(SURVIVES))
+def test_the_median_posterior_survives(bask, request, case):
+    fixture, call = SURVIVES[case]
+    gp = request.getfixturevalue(fixture)
+    Xq = np.random.RandomState(35).uniform(0.02, 0.98, size=(16, gp._X_train_.shape[1]))
+    before = _median_state(gp, Xq)
+    calls, restore = _count_set_warp(gp)
+    try:
+        out = call(bask, gp, Xq)  # (raises nothing)
+    finally:
+        restore()
+    assert len(calls) >= 2  # the case did walk rows under their own warps: at least one row's, then the estimator's own again
+    assert case != "canonical-kg-host" or out[1] == "host"
+    _assert_median_state(gp, Xq, before)
+
+
+def test_an_exception_inside_the_row_walk_leaves_the_estimator_as_it_was(warped_gp):
+    gp = warped_gp
+    Xq = np.random.RandomState(36).uniform(size=(9, 2))
+    before = _median_state(gp, Xq)
+    with pytest.raises(ZeroDivisionError):
+        with gp._row_warps() as install:
+            install(gp.chain_[0])
+            assert gp._post_theta is None and not np.array_equal(gp.warp_alphas_, before["warp_alphas_"])
+            1 / 0
+    _assert_median_state(gp, Xq, before)
