@@ -129,6 +129,7 @@ SIGNATURES = {
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
+    "bgp_shapley": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "bgp_knowledge_gradient": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_joint_entropy": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp]),
@@ -825,6 +826,25 @@ class Context:
         _check(self._lib.bgp_sobol_indices(self._h, B, _p(H), A.shape[0], _p(A), _p(Bm), T, masks.ctypes.data_as(up), _p(f0), _p(V),
                                            _p(closed), _p(total)), "bgp_sobol_indices")
         return f0, V, closed, total
+
+    # ---- Shapley attribution of the surrogate mean (bgp_shapley.hip)
+    def shapley(self, H_kernel, Xp, Z, interactions=False):
+        """``bgp_shapley``: the Shapley values of the mean of the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2)) at the
+        points ``Xp`` (P, d) against the background rows ``Z`` (N, d; one row: baseline Shapley), all 2^d coalitions enumerated.
+        Returns ``(phi (B, P, d), base (B,), value (B, P), inter (B, P, d, d) | None)`` in normalised-target units: ``phi`` sums
+        over the dimensions to ``value - base``; ``inter`` is the Shapley interaction index (symmetric, zero diagonal), computed
+        with ``interactions``.  Needs d <= 16."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xp, Z = _c(np.atleast_2d(Xp)), _c(np.atleast_2d(Z))
+        if Xp.shape[1] != self.d or Z.shape[1] != self.d:
+            raise ValueError(f"points and background rows must have {self.d} columns, got {Xp.shape} and {Z.shape}")
+        P, d = Xp.shape[0], self.d
+        phi, base, value = np.empty((B, P, d)), np.empty(B), np.empty((B, P))
+        inter = np.empty((B, P, d, d)) if interactions else None
+        _check(self._lib.bgp_shapley(self._h, B, _p(H), P, _p(Xp), Z.shape[0], _p(Z), _p(phi), _p(base), _p(value),
+                                     _p(inter) if interactions else C.cast(None, _dp)), "bgp_shapley")
+        return phi, base, value, inter
 
     # ---- posterior covariance of the gradient and the active-subspace sums (bgp_gcov.hip; DESIGN.md section 22)
     def grad_cov(self, H_kernel, Xq, want_dmean=True, want_cov=True, want_csum=False):

@@ -146,6 +146,112 @@ def sensitivity_by_predict(gp, thetas, A, Bm, masks, why):
     return sobol_estimator(F[:, 0], F[:, 1], F[:, 2:])
 
 
+_shap_told = []
+SHAP_DMAX = 16             # dimensions of the device call: all 2^d coalitions are enumerated (bgp_shapley.hip)
+SHAP_PARTMAX = 1 << 26     # doubles of chunk partials per device call, B P 2^d ceil(n N / 1024) (bgp_shapley.hip)
+SHAP_EXACT_ROWS = 1 << 22  # synthesised rows per point up to which the host route enumerates the coalitions
+
+
+def _shap_tell_once(why):
+    """One line on stderr, once per process: Shapley values computed through ``predict`` on synthesised rows."""
+    if not _shap_told:
+        _shap_told.append(True)
+        print("[bayes_skopt_amd] shapley: through predict on synthesised rows (%s)" % why, file=sys.stderr, flush=True)
+
+
+def shapley_from_values(v, d, interactions=False):
+    """The Shapley values and interaction indices of a set function: ``v`` (..., 2^d) holds the value of coalition S at index S
+    (bit k set: dimension k is in).  Returns ``(phi (..., d), inter (..., d, d) | None)`` -- the identities of DESIGN.md section 29,
+    every difference weighted by |S|! (d - |S| - 1)! / d!, or by |S|! (d - |S| - 2)! / (d - 1)! for a pair; ``inter`` is symmetric
+    with a zero diagonal."""
+    from math import factorial as fac
+
+    v = np.asarray(v)
+    S = np.arange(1 << d)
+    size = np.zeros(1 << d, dtype=np.int64)
+    for k in range(d):
+        size += (S >> k) & 1
+    w1 = np.array([fac(s) * fac(d - s - 1) for s in range(d)], dtype=v.dtype) / v.dtype.type(fac(d))  # (exact integers: one rounding)
+    w2 = np.array([fac(s) * fac(d - s - 2) for s in range(d - 1)] + [0], dtype=v.dtype) / v.dtype.type(fac(max(d - 1, 0)))
+    phi = np.zeros(v.shape[:-1] + (d,), dtype=v.dtype)
+    inter = np.zeros(v.shape[:-1] + (d, d), dtype=v.dtype) if interactions else None
+    for k in range(d):
+        out = S[((S >> k) & 1) == 0]
+        phi[..., k] = ((v[..., out | (1 << k)] - v[..., out]) * w1[size[out]]).sum(axis=-1)
+        for l in range(k + 1, d) if interactions else ():
+            o2 = out[((out >> l) & 1) == 0]
+            kb, lb = 1 << k, 1 << l
+            inter[..., k, l] = (((v[..., o2 | kb | lb] - v[..., o2 | kb]) - (v[..., o2 | lb] - v[..., o2])) * w2[size[o2]]).sum(axis=-1)
+            inter[..., l, k] = inter[..., k, l]
+    return phi, inter
+
+
+def coalition_picks(d):
+    """Every coalition of ``d`` dimensions as a boolean (2^d, d) array: row S picks dimension k when bit k of S is set."""
+    return ((np.arange(1 << d)[:, None] >> np.arange(d)[None, :]) & 1).astype(bool)
+
+
+def coalition_rows(x, Z, pick):
+    """The synthesised rows of the coalitions ``pick`` (m, d), coalition-major (m N, d): ``Z`` with the picked columns from ``x``."""
+    return np.where(pick[:, None, :], x[None, None, :], Z[None, :, :]).reshape(-1, Z.shape[1])
+
+
+def coalition_means(gp, thetas, x, Z, pick):
+    """v (B, m): for every row of the boolean ``pick`` (m, d) the mean over the background rows ``Z`` (N, d) of the latent mean at
+    ``Z`` with the picked columns taken from the point ``x`` -- through ``predict``, at most ``PD_ROWS`` rows per call."""
+    N, d = Z.shape
+    step, out = max(1, PD_ROWS // N), []
+    for m0 in range(0, len(pick), step):
+        rows = coalition_rows(x, Z, pick[m0:m0 + step])
+        F = np.concatenate([means_by_predict(gp, thetas, rows[r0:r0 + PD_ROWS]) for r0 in range(0, len(rows), PD_ROWS)], axis=1)
+        out.append(F.reshape(F.shape[0], -1, N).mean(axis=2))
+    return np.concatenate(out, axis=1)
+
+
+def shapley_by_predict(gp, thetas, Xp, Z, why, interactions=False, n_permutations=None, rng=None):
+    """The fallback of ``shapley``: coalition rows synthesised on the host, their means through ``predict`` (``coalition_means``),
+    the weights in numpy.  Up to ``SHAP_EXACT_ROWS`` rows per point (2^d N) every coalition is enumerated
+    (``shapley_from_values``).  Beyond that the values are a permutation-sampling estimate: ``n_permutations`` orders of the
+    dimensions drawn from the generator ``rng`` -- both must be given --, the columns switched from the background to the point one
+    after the other and every step credited to its dimension; no interaction index then.  Returns ``(phi (B, P, d), base (B,),
+    value (B, P), inter (B, P, d, d) | None, se (B, P, d) | None)`` in normalised-target units; ``se``: the standard error of the
+    estimate, None for the enumeration."""
+    _shap_tell_once(why)
+    Xp, Z = np.atleast_2d(np.asarray(Xp, dtype=np.float64)), np.atleast_2d(np.asarray(Z, dtype=np.float64))
+    (P, d), N = Xp.shape, Z.shape[0]
+    exact = d < 40 and (N << d) <= SHAP_EXACT_ROWS
+    if not exact and (n_permutations is None or int(n_permutations) < 2 or rng is None):
+        raise ValueError(f"2^{d} coalitions on {N} background rows are not enumerated on the host: the permutation estimate needs "
+                         "n_permutations >= 2 and a random generator")
+    phi, base, value, inter, se = [], None, [], [], []
+    for x in Xp:
+        if exact:
+            v = coalition_means(gp, thetas, x, Z, coalition_picks(d))
+            ph, it = shapley_from_values(v, d, interactions)
+            inter.append(it)
+            first, last = v[:, 0], v[:, -1]
+        else:
+            R = int(n_permutations)
+            orders = np.stack([rng.permutation(d) for _ in range(R)])
+            pick = np.zeros((R, d + 1, d), dtype=bool)
+            for r in range(R):
+                for i in range(d):
+                    pick[r, i + 1] = pick[r, i]
+                    pick[r, i + 1, orders[r, i]] = True
+            v = coalition_means(gp, thetas, x, Z, pick.reshape(-1, d)).reshape(-1, R, d + 1)
+            steps = np.empty((v.shape[0], R, d))
+            for r in range(R):
+                steps[:, r, orders[r]] = np.diff(v[:, r], axis=1)
+            ph = steps.mean(axis=1)
+            se.append(steps.std(axis=1, ddof=1) / np.sqrt(R))
+            first, last = v[:, 0, 0], v[:, 0, -1]
+        phi.append(ph)
+        value.append(last)
+        base = first if base is None else base
+    return (np.stack(phi, axis=1), base, np.stack(value, axis=1), np.stack(inter, axis=1) if exact and interactions else None,
+            None if exact else np.stack(se, axis=1))
+
+
 class PendingLml:
     """A block's LML between ``lml_begin`` and ``lml_finish``; ``submitted``: the device is already working on it."""
 
@@ -299,6 +405,28 @@ class CanonicalPosterior:
             return sensitivity_by_predict(gp, thetas, A, Bm, masks, why), "host"
         return gp._ctx.sobol_indices(self.built_H(gp, thetas), A, Bm, masks), "device"
 
+    def shapley(self, gp, thetas, Xp, Z, interactions=False, n_permutations=None, rng=None):
+        """((phi (B, P, d), base (B,), value (B, P), inter (B, P, d, d) | None, se | None) in normalised-target units, "device" |
+        "host").  ``thetas=None``: the resident median GP (B = 1); a block of chain rows: one batched build, then ONE device call
+        over all of them (``bgp_shapley``; a call whose chunk partials would pass the entry's scratch bound
+        goes point block by point block: a point's bits do not depend on what shares its call).  More than 16 dimensions, chain
+        rows under ``warp_inputs`` (every row has its own training inputs), and a single point whose partials pass that bound (at
+        d = 16 and n = 974: more than 1 077 background rows) go through ``predict`` (``shapley_by_predict``)."""
+        n, d = gp._X_train_.shape
+        B = 1 if thetas is None else len(np.atleast_2d(thetas))
+        per_point = B * (1 << min(d, 62)) * -(-n * len(Z) // 1024)
+        if d > SHAP_DMAX or (thetas is not None and gp.warp_inputs) or per_point > SHAP_PARTMAX:
+            why = ("more than 16 dimensions" if d > SHAP_DMAX else
+                   "hyper-posterior rows with input warping" if thetas is not None and gp.warp_inputs else
+                   "one point's chunk partials pass the device call's scratch bound: fewer background rows or chain rows fit")
+            return shapley_by_predict(gp, thetas, Xp, Z, why, interactions, n_permutations, rng), "host"
+        H = self.built_H(gp, thetas)
+        step = max(1, min(SHAP_PARTMAX // per_point, 65535 // len(H)))
+        parts = [gp._ctx.shapley(H, Xp[lo:lo + step], Z, interactions) for lo in range(0, len(Xp), step)]
+        phi, value = (np.concatenate([q[i] for q in parts], axis=1) for i in (0, 2))
+        inter = np.concatenate([q[3] for q in parts], axis=1) if interactions else None
+        return (phi, parts[0][1], value, inter, None), "device"
+
     gradient_cov_path = "auto"  # "host": always numpy on the downloaded inverse (tests compare the two paths)
 
     def gradient_cov(self, gp, thetas, X, want):
@@ -440,6 +568,9 @@ class GramPosterior:
 
     def sensitivity(self, gp, thetas, A, Bm, masks):
         return sensitivity_by_predict(gp, thetas, A, Bm, masks, "generic kernel tree"), "host"
+
+    def shapley(self, gp, thetas, Xp, Z, interactions=False, n_permutations=None, rng=None):
+        return shapley_by_predict(gp, thetas, Xp, Z, "generic kernel tree", interactions, n_permutations, rng), "host"
 
     def gradient_cov(self, gp, thetas, X, want):
         raise NotImplementedError("the gradient covariance needs a canonical kernel: a generic kernel tree has no closed-form "

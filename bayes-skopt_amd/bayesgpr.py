@@ -792,6 +792,40 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out = tuple(v[0] for v in out)
         return (*out, path) if return_path else out
 
+    def shapley_values(self, X, background, thetas=None, interactions=False, n_permutations=None, random_state=None):
+        """Shapley attribution of the predictive mean at the rows of ``X`` (P, d; transformed space) against ``background`` (N, d;
+        one row: a baseline point): how much of ``mean(x) - average of the mean over the background`` every dimension accounts
+        for, averaged over all orders in which the coordinates can be switched from a background row to x.  Returns a dict in y
+        units: ``"phi"`` (P, d), which sums over the dimensions to ``"value" - "base"``; ``"value"`` (P,), the mean at the
+        points; ``"base"``, the average of the mean over the background; ``"interaction"`` (P, d, d) with ``interactions``: the
+        Shapley interaction index (symmetric, zero diagonal: what two dimensions add only together), else None; ``"phi_se"``:
+        None, or the standard error of a sampled ``phi``; ``"path"``.  For a block of B chain rows ``thetas`` every array has a
+        leading axis B.  Canonical kernels in up to 16 dimensions: all 2^d coalitions in ONE device call (``bgp_shapley``,
+        DESIGN.md section 29; the context-level warp of ``warp_inputs`` is applied to points and background on the device),
+        path "device".  Generic kernel trees, more dimensions, and chain rows under ``warp_inputs``: ``predict`` on synthesised
+        rows, said once on stderr, path "host" -- every coalition while 2^d N <= 2^22, otherwise the estimate from
+        ``n_permutations`` random orders drawn with ``random_state`` (both are then required), without interactions."""
+        from sklearn.utils import check_random_state
+
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        Z = np.atleast_2d(np.asarray(background, dtype=np.float64))
+        self._require_posterior()
+        d = self._X_train_.shape[1]
+        if X.shape[1] != d or Z.shape[1] != d or X.shape[0] < 1 or Z.shape[0] < 1:
+            raise ValueError(f"points and background must be (P, {d}) and (N, {d}) with P, N >= 1, got {X.shape} and {Z.shape}")
+        if self.warp_inputs:
+            validate_zeroone(X)
+            validate_zeroone(Z)
+        rng = None if random_state is None else check_random_state(random_state)
+        (phi, base, value, inter, se), path = self._post.shapley(self, thetas, X, Z, bool(interactions), n_permutations, rng)
+        y_mean, y_std = self._y_scale()
+        out = {"phi": y_std * phi, "base": y_std * base + y_mean, "value": y_std * value + y_mean,
+               "interaction": None if inter is None else y_std * inter, "phi_se": None if se is None else y_std * se}
+        if thetas is None:
+            out = {k: (None if v is None else v[0]) for k, v in out.items()}
+        out["path"] = path
+        return out
+
     def _gradient_cov(self, X, thetas, want):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))
         self._require_posterior()

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
@@ -319,6 +319,14 @@ class Optimizer:
         """Which dimensions matter and which interact: first-order, total and pair-interaction Sobol' indices of the current
         surrogate (``utils.sensitivity_indices`` on the current result, same keyword arguments)."""
         return sensitivity_indices(self._result(), **kw)
+
+    def shapley_values(self, x=None, baseline=None, n_samples=256, n_gp_samples=0, interactions=False, random_state=None, **kw):
+        """Why the surrogate predicts what it does at ``x`` (default: the current expected optimum) against ``baseline`` (one point,
+        for example the default configuration; default: the average over ``n_samples`` points of the space): the Shapley
+        attribution of the difference to the dimensions, and with ``interactions`` what pairs contribute only together
+        (``utils.shapley_values`` on the current result; the optimizer's own random state is not consumed)."""
+        return shapley_values(self._result(), x=x, baseline=baseline, n_samples=n_samples, n_gp_samples=n_gp_samples,
+                              interactions=interactions, random_state=random_state, **kw)
 
     def cross_validate(self, **kw):
         """Does the surrogate predict the observations it has not seen?  Held-out predictives of the training points, fold by fold,

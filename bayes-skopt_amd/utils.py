@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "active_subspace", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -340,6 +340,56 @@ def sensitivity_indices(res, dims=None, pairs=None, n_samples=4096, n_gp_samples
     out["total"] = {k: float(Tt[at[k]]) for k in dims}
     out["interaction"] = {pr: float(inter[i]) for i, pr in enumerate(pairs)}
     out["mean"], out["variance"] = float(mean), float(var)
+    return out
+
+
+def shapley_values(res, x=None, baseline=None, n_samples=256, n_gp_samples=0, interactions=False, random_state=None,
+                   n_permutations=None):
+    """Why is the surrogate's prediction at ``x`` better or worse than at the baseline, dimension by dimension: the Shapley
+    attribution of the mean of ``res.models[-1]`` at ``x`` (original space; default: the current expected optimum,
+    ``expected_optimum(res, random_state=random_state)``) against ``baseline`` -- one point of the original space, for example the
+    default configuration -- or, with ``baseline=None``, against the average over ``space.rvs_transformed(n_samples, random_state)``
+    (Integer and Categorical dimensions keep their snapped values; a dimension is one column).  Returns a dict in y units:
+    ``"phi"`` {name: value}, which add up to ``"value" - "base"``: the share of that difference every dimension accounts for, with
+    its sign (where a Sobol' index says how much variance a dimension explains on average over the space); ``"value"``, the mean at
+    x; ``"base"``, the mean at the baseline (or its average over the samples); ``"interaction"`` {(name_a, name_b): index}, a < b,
+    with ``interactions`` (what the two dimensions contribute only together), else None; ``"names"``, ``"x"``; and ``"path"``:
+    "device" when all 2^d coalitions came from ONE device call (``bgp_shapley``; d <= 16), "host" when they
+    came through ``predict`` on synthesised rows -- every coalition while 2^d N <= 2^22, otherwise an estimate from
+    ``n_permutations`` (default 256) random orders, with ``"phi_se"`` {name: standard error} and no interactions.
+    ``n_gp_samples > 0``: the averages over that many rows drawn from ``chain_`` with ``random_state``, and under ``"band"``
+    {name: (5 %, 95 %)} the per-draw band of ``phi``; the default is the median GP, which ``res.models[-1]`` predicts with."""
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    if x is None:
+        x = expected_optimum(res, random_state=rng)[0]
+    x = list(x)
+    Xp = np.asarray(space.transform([x]), dtype=np.float64)
+    Z = space.rvs_transformed(n_samples, random_state=rng) if baseline is None else np.asarray(space.transform([list(baseline)]), dtype=np.float64)
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    got = reg.shapley_values(Xp, Z, thetas=thetas, interactions=interactions, random_state=rng,
+                             n_permutations=256 if n_permutations is None else n_permutations)
+    names = [dim.name if dim.name is not None else "X_%d" % k for k, dim in enumerate(space.dimensions)]
+    phi, inter, se = got["phi"][..., 0, :], got["interaction"], got["phi_se"]
+    base, value = got["base"], got["value"][..., 0]
+    out = {"path": got["path"], "names": names, "x": x}
+    if thetas is not None:
+        out["band"] = {nm: tuple(np.percentile(phi[:, k], [5.0, 95.0])) for k, nm in enumerate(names)}
+        phi, base, value = phi.mean(axis=0), base.mean(axis=0), value.mean(axis=0)
+        inter = None if inter is None else inter.mean(axis=0)
+        se = None if se is None else np.sqrt((se**2).mean(axis=0) / len(thetas))
+    out["phi"] = {nm: float(phi[k]) for k, nm in enumerate(names)}
+    out["base"], out["value"] = float(base), float(value)
+    out["interaction"] = None if inter is None else {(names[a], names[b]): float(inter[0, a, b]) for a in range(len(names))
+                                                     for b in range(a + 1, len(names))}
+    if se is not None:
+        out["phi_se"] = {nm: float(se[0, k]) for k, nm in enumerate(names)}
     return out
 
 

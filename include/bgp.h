@@ -120,7 +120,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -451,6 +451,31 @@ int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, c
  */
 int bgp_sobol_indices(bgp_ctx* ctx, int B, const double* h_kernel, int N, const double* A, const double* Bm, int T,
                       const unsigned* masks, double* f0, double* V, double* closed, double* total);
+
+/*
+ * Shapley attribution of the surrogate mean at P points against N background rows (csrc/bgp_shapley.hip), for
+ * the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read).  With the points Xp
+ * (P*d) and the background Z (N*d; N = 1: baseline Shapley against one reference point), over all 2^d coalitions S of D = {0 .. d-1}:
+ *   v_bp(S)    = (1 / N) sum_s mu_b(Z_s with the columns in S taken from Xp_p)                              (normalised-y units)
+ *   base_b     = v(empty)  (does not depend on p)                     value_bp = v(D) = mu_b(Xp_p)
+ *   phi_bpk    = sum over S in D \ {k}    |S|! (d - |S| - 1)! / d!        [v(S + k) - v(S)]                  (Shapley value)
+ *   inter_bpkl = sum over S in D \ {k, l} |S|! (d - |S| - 2)! / (d - 1)!  [(v(S + k + l) - v(S + k)) - (v(S + l) - v(S))]
+ * (the Shapley interaction index: exactly symmetric, 0 on the diagonal; inter may be NULL).  sum_k phi_bpk = value_bp - base_b up to
+ * rounding.  The squared distance of a coalition row to a training point is TL[S mod 2^dl] + TH[S >> dl], dl = ceil(d / 2): two
+ * tables of sums of squares in x / l, ascending dimension, nothing obtained by subtraction.  Every sum has a fixed order: the
+ * (s, j) pairs in chunks of 1024, chunk partials in ascending order, one division by N; the weighted differences in ascending
+ * subset index, chunks of 256 in a fixed tree, chunk partials in ascending order.  phi, inter, value of (b, p) and base of b are
+ * the same bits whatever B and P are, wherever the point stands in the list, whatever else shares the call.  If Xp_pk equals Z_sk
+ * bitwise for every s, phi_bpk and row and column k of inter are exactly 0; with N = 1 and Xp_p equal to Z_0 every phi and inter
+ * entry is exactly 0 and value equals base bit for bit.  Xp and Z go through the context-level warp as predict's queries do.
+ * phi: B*P*d;  base: B;  value: B*P;  inter: B*P*d*d, posterior-major.
+ * Needs d <= 16, 1 <= B, 1 <= P, B P <= 65535, 1 <= N <= 2^24 and at most 2^26 doubles of chunk partials,
+ * B P 2^d ceil(n N / 1024) (BGP_ERR_INVALID before anything is launched), and B resident posteriors that are not per-row warped
+ * (BGP_ERR_STATE).  A refused or failed call leaves the resident posteriors usable.
+ *   Replaces: nothing in the reference -- there the route is predict on 2^d N synthesised rows and the weights on the host.
+ */
+int bgp_shapley(bgp_ctx* ctx, int B, const double* h_kernel, int P, const double* Xp, int N, const double* Z, double* phi,
+                double* base, double* value, double* inter);
 
 /*
  * Posterior covariance of the surrogate's gradient, and the active-subspace sums (csrc/bgp_gcov.hip), for the
