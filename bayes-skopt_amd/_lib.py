@@ -128,6 +128,7 @@ SIGNATURES = {
     "bgp_minimize_starts": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_double,
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
+    "bgp_partial_dependence_var": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp, _dp, _dp]),
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_shapley": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -773,6 +774,14 @@ class Context:
         rows ``Xs`` (S, d) with the panel's coordinates replaced by grid values.  ``grids``: d 1-D arrays (1 .. 256 values each);
         ``panels``: ``(k1, -1)`` / ``(k1,)`` / ``k1`` for a curve, ``(k1, k2)`` for a map.  Returns one array per panel, (B, G1) or
         (B, G1, G2), in normalised-target units.  Needs d <= 32."""
+        H, B, Xs, gmax, ng, grid, pan, shapes, total = self._pd_args(H_kernel, Xs, grids, panels)
+        out = np.empty((B, max(total, 1)))
+        _check(self._lib.bgp_partial_dependence(self._h, B, _p(H), Xs.shape[0], _p(Xs), gmax, _p(ng), _p(grid), len(pan), _p(pan),
+                                                _p(out)), "bgp_partial_dependence")
+        return self._pd_blocks(out, shapes)
+
+    def _pd_args(self, H_kernel, Xs, grids, panels):
+        """The arguments ``bgp_partial_dependence`` and ``bgp_partial_dependence_var`` share, and the shapes of the panels' blocks."""
         H = self._H(H_kernel)
         B = H.shape[0]
         Xs = _c(np.atleast_2d(Xs))
@@ -794,15 +803,34 @@ class Context:
         shapes = [(int(ng[a]),) if b < 0 else (int(ng[a]), int(ng[b])) for a, b in pan
                   if 0 <= a < self.d and -1 <= b < self.d] if len(pan) else []
         total = int(sum(int(np.prod(s)) for s in shapes))
-        out = np.empty((B, max(total, 1)))
-        _check(self._lib.bgp_partial_dependence(self._h, B, _p(H), Xs.shape[0], _p(Xs), gmax, _p(ng), _p(grid), len(pan), _p(pan),
-                                                _p(out)), "bgp_partial_dependence")
+        return H, B, Xs, gmax, ng, grid, pan, shapes, total
+
+    @staticmethod
+    def _pd_blocks(out, shapes):
         res, o = [], 0
         for s in shapes:
             sz = int(np.prod(s))
-            res.append(out[:, o:o + sz].reshape((B,) + s).copy())
+            res.append(out[:, o:o + sz].reshape((out.shape[0],) + s).copy())
             o += sz
         return res
+
+    # ---- partial dependence with its posterior variance (bgp_pdvar.hip)
+    def partial_dependence_var(self, H_kernel, Xs, grids, panels, want_mean=True, want_var=True, want_cov=False):
+        """``bgp_partial_dependence_var``: arguments as ``partial_dependence``.  Returns ``(mean, var, cov)``, each a list or None:
+        ``mean`` and ``var`` one array per panel, (B, G1) or (B, G1, G2); ``cov`` one (B, G1, G1) array per 1-D panel, in list
+        order (the covariance of the curve's cells; 2-D panels have none).  Latent function, normalised-target units; ``var`` and
+        the diagonal of ``cov`` are clipped at 0.  Needs d <= 32 and at most 16 384 sample rows."""
+        H, B, Xs, gmax, ng, grid, pan, shapes, total = self._pd_args(H_kernel, Xs, grids, panels)
+        cshapes = [s + s for s in shapes if len(s) == 1]
+        mean = np.empty((B, max(total, 1))) if want_mean else None
+        var = np.empty((B, max(total, 1))) if want_var else None
+        cov = np.empty((B, max(sum(s[0] * s[1] for s in cshapes), 1))) if want_cov else None
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_partial_dependence_var(self._h, B, _p(H), Xs.shape[0], _p(Xs), gmax, _p(ng), _p(grid), len(pan), _p(pan),
+                                                    _p(mean) if want_mean else null, _p(var) if want_var else null,
+                                                    _p(cov) if want_cov else null), "bgp_partial_dependence_var")
+        return (self._pd_blocks(mean, shapes) if want_mean else None, self._pd_blocks(var, shapes) if want_var else None,
+                self._pd_blocks(cov, cshapes) if want_cov else None)
 
     # ---- Sobol' sensitivity of the surrogate mean (bgp_sobol.hip; DESIGN.md section 21)
     def sobol_indices(self, H_kernel, A, Bm, masks):

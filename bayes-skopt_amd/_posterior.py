@@ -85,6 +85,55 @@ def partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why):
     return out
 
 
+PDVAR_SMAX = 16384  # sample rows of the device call with a variance: its prior term is a pair sum (bgp_pdvar.hip)
+
+
+def latent_cov_by_predict(gp, thetas, X):
+    """The (B, m, m) latent covariance at ``X`` -- ``predict(return_cov=True)`` with the noise set to zero --, normalised-target
+    units; the rows of ``thetas`` as in ``means_by_predict``."""
+    if thetas is None:
+        with gp.noise_set_to_zero():
+            return gp._post.predict(gp, X, True)[2]
+    thetas = np.atleast_2d(thetas)
+    if gp.warp_inputs:
+        with gp._row_warps() as install:
+            return np.concatenate([gp._post.rows_predict(gp, install(row), X, True, return_cov=True)[2] for row in thetas])
+    return gp._post.rows_predict(gp, thetas, X, True, return_cov=True)[2]
+
+
+def partial_dependence_var_by_predict(gp, thetas, Xs, grids, panels, want_cov, why):
+    """The fallback of ``partial_dependence`` with ``return_std`` / ``return_cov``: the means as ``partial_dependence_by_predict``
+    gives them; per cell the latent covariance of its S synthesised rows, ``1^T cov 1 / S^2``; for the cells g > g' of a curve
+    (``want_cov``) the cross block of the covariance of both cells' rows.  Returns (means, variances, covariances | None)."""
+    means = partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why)
+    Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
+    S = Xs.shape[0]
+
+    def rows(axes, shape, c):
+        X = Xs.copy()
+        for (k, g), gi in zip(axes, np.unravel_index(c, shape)):
+            X[:, k] = g[gi]
+        return X
+
+    var, cov = [], ([] if want_cov else None)
+    for k1, k2 in panels:
+        axes = [(k1, np.asarray(grids[k1], dtype=np.float64))] + ([(k2, np.asarray(grids[k2], dtype=np.float64))] if k2 >= 0 else [])
+        shape = tuple(len(g) for _k, g in axes)
+        ncell = int(np.prod(shape))
+        v = np.stack([latent_cov_by_predict(gp, thetas, rows(axes, shape, c)).sum(axis=(1, 2)) for c in range(ncell)], axis=1) / S**2
+        v = np.maximum(v, 0.0)
+        var.append(v.reshape((v.shape[0],) + shape))
+        if want_cov and k2 < 0:
+            Cm = np.zeros((v.shape[0], ncell, ncell))
+            for g in range(ncell):
+                Cm[:, g, g] = v[:, g]
+                for h in range(g):
+                    both = latent_cov_by_predict(gp, thetas, np.concatenate([rows(axes, shape, g), rows(axes, shape, h)]))
+                    Cm[:, g, h] = Cm[:, h, g] = both[:, :S, S:].sum(axis=(1, 2)) / S**2
+            cov.append(Cm)
+    return means, var, cov
+
+
 _sens_told = []
 SENS_DMAX = 32  # dimensions of the device call: one bit of a 32-bit mask each (bgp_sobol.hip)
 
@@ -385,14 +434,23 @@ class CanonicalPosterior:
         """Minima of mean + kappa std (y units) of the resident posterior over the box from every start, in one launch."""
         return gp._ctx.minimize_starts(0, self.built_H(gp, None), *gp._y_scale(), kappa, X0, lo, hi, gtol=gtol, max_iter=max_iter)
 
-    def partial_dependence(self, gp, thetas, Xs, grids, panels):
+    def partial_dependence(self, gp, thetas, Xs, grids, panels, return_std=False, return_cov=False):
         """(per panel a (B, G1) or (B, G1, G2) array in normalised-target units, "device" | "host").  ``thetas=None``: the resident
         median GP (B = 1); a block of chain rows: one batched build, then ONE device call over all of them
         (``bgp_partial_dependence``).  More than 32 dimensions, and chain rows under ``warp_inputs`` (every
-        row has its own training inputs), go through ``predict``."""
+        row has its own training inputs), go through ``predict``.  With ``return_std`` / ``return_cov`` the first item is ``(means,
+        variances, covariances | None)`` of the latent function instead, from ONE ``bgp_partial_dependence_var`` call (DESIGN.md
+        section 30) or, on the host, from ``predict(return_cov=True)`` on the synthesised rows."""
+        wide = return_std or return_cov
         if gp._X_train_.shape[1] > 32 or (thetas is not None and gp.warp_inputs):
             why = "more than 32 dimensions" if gp._X_train_.shape[1] > 32 else "hyper-posterior rows with input warping"
+            if wide:
+                return partial_dependence_var_by_predict(gp, thetas, Xs, grids, panels, return_cov, why), "host"
             return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, why), "host"
+        if wide:
+            if len(Xs) > PDVAR_SMAX:  # (the device route alone: the host path has no pair sum)
+                raise ValueError(f"partial_dependence with return_std / return_cov takes at most {PDVAR_SMAX} sample rows, got {len(Xs)}")
+            return gp._ctx.partial_dependence_var(self.built_H(gp, thetas), Xs, grids, panels, want_cov=return_cov), "device"
         return gp._ctx.partial_dependence(self.built_H(gp, thetas), Xs, grids, panels), "device"
 
     def sensitivity(self, gp, thetas, A, Bm, masks):
@@ -563,7 +621,9 @@ class GramPosterior:
         """``kernel_.gradient_x`` is ``kernels.gradient_x`` (skopt's method restated for scikit-learn kernel objects)."""
         return gradient_x(gp.kernel_, x, Xt), gp.kernel_(x[None, :], Xt)[0]
 
-    def partial_dependence(self, gp, thetas, Xs, grids, panels):
+    def partial_dependence(self, gp, thetas, Xs, grids, panels, return_std=False, return_cov=False):
+        if return_std or return_cov:
+            return partial_dependence_var_by_predict(gp, thetas, Xs, grids, panels, return_cov, "generic kernel tree"), "host"
         return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, "generic kernel tree"), "host"
 
     def sensitivity(self, gp, thetas, A, Bm, masks):

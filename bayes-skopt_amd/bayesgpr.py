@@ -729,7 +729,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         grad_std[nz] = dvar[nz] / (2.0 * y_std[nz])[:, None] * self.y_train_std_**2
         return y_mean, y_std, grad_mean, grad_std
 
-    def partial_dependence(self, Xs, grids, panels=None, thetas=None, return_path=False):
+    def partial_dependence(self, Xs, grids, panels=None, thetas=None, return_path=False, return_std=False, return_cov=False):
         """Partial dependence of the predictive mean: per panel the mean averaged over the sample rows ``Xs`` (S, d; transformed
         space) with the panel's coordinates replaced by grid values -- ``grids``: one 1-D array per dimension (transformed space, at
         most 256 values), ``panels``: ``k`` / ``(k,)`` / ``(k, -1)`` for a curve, ``(k1, k2)`` for a map, None for every dimension
@@ -737,7 +737,13 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         (``thetas=None``), or (B, G1) / (B, G1, G2) for a block of B chain rows.  Canonical kernels in up to 32 dimensions: ONE
         device call for all panels and rows (``bgp_partial_dependence``; the context-level warp of
         ``warp_inputs`` is applied to samples and grids on the device).  Generic kernel trees, more dimensions, and chain rows
-        under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" | "host"."""
+        under ``warp_inputs``: ``predict`` on synthesised rows, said once on stderr.  ``return_path``: also "device" | "host".
+        ``return_std``: also, per panel and shaped like its values, the posterior standard deviation of the partial dependence of
+        the LATENT function (y units) -- how unsure the GP is about the curve, the samples held fixed; ``return_cov``: also, per
+        1-D panel in list order, the (G1, G1) covariance of its cells.  The tuple is then ``(values[, std][, cov][, path])``.
+        Both come with the values from ONE ``bgp_partial_dependence_var`` call (more than 16 384 sample rows
+        are a ValueError there: its prior term is a pair sum) or, where the values take the host route, from
+        ``predict(return_cov=True)`` with the noise set to zero (no such limit)."""
         Xs = np.atleast_2d(np.asarray(Xs, dtype=np.float64))
         self._require_posterior()
         d = self._X_train_.shape[1]
@@ -758,11 +764,22 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             pan.append(pnl)
         if not pan or Xs.shape[0] < 1 or any(not 1 <= len(g) <= 256 for g in grids):
             raise ValueError("partial_dependence needs a panel, a sample row and 1 .. 256 grid values per dimension")
-        vals, path = self._post.partial_dependence(self, thetas, Xs, grids, pan)
-        vals = [self.y_train_std_ * v + self.y_train_mean_ for v in vals]
+        if not (return_std or return_cov):
+            vals, path = self._post.partial_dependence(self, thetas, Xs, grids, pan)
+            vals = [self.y_train_std_ * v + self.y_train_mean_ for v in vals]
+            if thetas is None:
+                vals = [v[0] for v in vals]
+            return (vals, path) if return_path else vals
+        (vals, var, cov), path = self._post.partial_dependence(self, thetas, Xs, grids, pan, return_std=True, return_cov=return_cov)
+        y_mean, y_std = self._y_scale()
+        out = [[y_std * v + y_mean for v in vals]]
+        if return_std:
+            out.append([y_std * np.sqrt(v) for v in var])
+        if return_cov:
+            out.append([y_std**2 * v for v in cov])
         if thetas is None:
-            vals = [v[0] for v in vals]
-        return (vals, path) if return_path else vals
+            out = [[v[0] for v in part] for part in out]
+        return (*out, path) if return_path else tuple(out)
 
     def sensitivity(self, A, Bm, terms=None, thetas=None, return_path=False):
         """Variance-based (Sobol') sensitivity of the predictive mean by the pick-freeze design: ``A``, ``Bm`` are two independent

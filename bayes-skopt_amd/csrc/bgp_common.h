@@ -394,7 +394,7 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
@@ -436,7 +436,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
   return BGP_OK;
 }
 
-// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
+// ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
 // bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
@@ -518,7 +518,7 @@ int bgp_launch_kcross_matvec_x(bgp_ctx* ctx, int nb, const double* dH, int m, co
 int bgp_launch_warp(bgp_ctx* c, hipStream_t st, const double* dX, const double* dW, double* dout, int n, int B,
                     size_t ostride);
 int bgp_launch_cholesky(bgp_ctx* ctx, int B, int augmented);
-// bgp_post.hip: `rows` query rows to the device, through the context-level warp when one is set (predict's staging; bgp_pdep.hip, bgp_sobol.hip, bgp_shapley.hip)
+// bgp_post.hip: `rows` query rows to the device, through the context-level warp when one is set (predict's staging; bgp_pdep.hip, bgp_pdvar.hip, bgp_sobol.hip, bgp_shapley.hip)
 int post_stage_queries(bgp_ctx* c, double* dst, const double* src, int rows);
 // n <= 128: K-build + factorisation + LML of the slice [off, off+B) in ONE launch (bgp_chol.hip, potrf_kernel<1,..>)
 int bgp_launch_lml_small(bgp_ctx* ctx, int off, int B, hipStream_t st);
@@ -540,6 +540,8 @@ void bgp_launch_gemm4(hipStream_t st, int mode, const double* A, const double* B
 void bgp_launch_rowquad(hipStream_t st, const double* A, int lda, size_t sA, const double* S, int lds_, size_t sS,
                         const int* pidx, int M, int n, int nb, double* part);
 int bgp_rowquad_tile();
+// bgp_pdep.hip: out[b][r][k] = in[r][k] / l_bk for the posteriors b of H (x / l as the cross kernel forms it); grid (ceil(rows d / 256), items)
+__global__ void pdep_scale_kernel(const double* __restrict__ in, int rows, int d, const double* __restrict__ H, double* __restrict__ out);
 // bgp_post.hip: out[b][i] = sum_t part[(b tn + t) M + i], t ascending (out packed with stride M); grid (ceil(M / 256), items)
 __global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, int M, double* __restrict__ out);
 // bgp_post.hip: var[b][i] = max(0, kernel_.diag of H[b] incl. the white level - q[b][i]), i < m; grid (ceil(m / 256), items)

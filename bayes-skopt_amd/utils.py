@@ -255,7 +255,8 @@ def _pd_grid(dim, n_points):
     return np.asarray(orig, dtype=object if isinstance(dim, Categorical) else np.int64), np.asarray(dim.transform(orig), dtype=np.float64)
 
 
-def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, samples=None, n_gp_samples=0, random_state=None):
+def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, samples=None, n_gp_samples=0, random_state=None,
+                       return_std=False, return_cov=False):
     """The data of the "plot objective" figure: the partial dependence of the surrogate mean on single dimensions and on pairs,
     i.e. the mean of ``res.models[-1]`` averaged over ``n_samples`` points of the space (``space.rvs_transformed(n_samples,
     random_state)``, or the given ``samples`` in the original space) with one or two coordinates swept over a grid (``_pd_grid``:
@@ -265,7 +266,13 @@ def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, 
     device call (``bgp_partial_dependence``), "host" when they came through ``predict`` on synthesised rows.
     ``n_gp_samples > 0``: the fully Bayesian curve -- the average over that many rows drawn from ``chain_`` with
     ``random_state`` -- and under ``"band"`` {k: (5 %, 95 %)} the per-draw band of the 1-D curves; the default is the median GP,
-    which ``res.models[-1]`` predicts with."""
+    which ``res.models[-1]`` predicts with.
+    ``return_std``: also ``"std"`` {"dims": {k: std}, "pairs": {(k1, k2): std[G1, G2]}}, the posterior standard deviation of the
+    partial dependence of the latent function in y units: how unsure the GP is about the curve, with the samples held fixed
+    (``bgp_partial_dependence_var``; at most 16 384 samples).  ``return_cov``: also ``"cov"`` {k: cov[G, G]},
+    the covariance of a curve's cells.  With ``n_gp_samples > 0`` both are totals by the law of total variance over the drawn
+    rows, the mean of the rows' (co)variances plus the (co)variance of the rows' curves, and ``return_std`` adds the two parts as
+    ``"std_within"`` and ``"std_between"`` (same layout); ``"band"`` stays the per-draw band of the curves."""
     from sklearn.utils import check_random_state
 
     space = res.space
@@ -283,8 +290,30 @@ def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, 
     if n_gp_samples > 0:
         chain = np.asarray(reg.chain_)
         thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
-    vals, path = reg.partial_dependence(Xs, [g[1] for g in both], panels, thetas=thetas, return_path=True)
+    got = reg.partial_dependence(Xs, [g[1] for g in both], panels, thetas=thetas, return_path=True, **(
+        {"return_std": True, "return_cov": return_cov} if return_std or return_cov else {}))  # (the variance feeds both)
+    vals, path = got[0], got[-1]
     out = {"dims": {}, "pairs": {}, "path": path}
+
+    def layout(arrs):
+        return {"dims": dict(zip(dims, arrs)), "pairs": dict(zip(pairs, arrs[len(dims):]))}
+
+    if return_std or return_cov:
+        within = [np.square(v) for v in got[1]]  # per panel: the rows' variances (B, ...), or the median GP's
+        cov = list(got[2]) if return_cov else None
+        if thetas is not None:
+            between = [v.var(axis=0) for v in vals]
+            within = [v.mean(axis=0) for v in within]
+            if return_std:
+                out["std_within"], out["std_between"] = layout([np.sqrt(v) for v in within]), layout([np.sqrt(v) for v in between])
+            if return_cov:
+                dev = [v - v.mean(axis=0) for v in vals[:len(dims)]]
+                cov = [c.mean(axis=0) + np.einsum("bi,bj->ij", e, e) / len(e) for c, e in zip(cov, dev)]
+            within = [w + b for w, b in zip(within, between)]
+        if return_std:
+            out["std"] = layout([np.sqrt(v) for v in within])
+        if return_cov:
+            out["cov"] = dict(zip(dims, cov))
     if thetas is not None:
         out["band"] = {k: tuple(np.percentile(v, [5.0, 95.0], axis=0)) for k, v in zip(dims, vals)}
         vals = [v.mean(axis=0) for v in vals]

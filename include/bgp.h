@@ -120,7 +120,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -431,6 +431,27 @@ int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, c
                            const double* grid, int P, const int* panels, double* out);
 
 /*
+ * Partial dependence with its posterior variance (csrc/bgp_pdvar.hip): how unsure the GP itself is about a
+ * curve or a map.  Arguments up to `panels` are those of bgp_partial_dependence.  For the LATENT function (no white term; the
+ * constant of the sum form included), with z_gs = x_s[D <- g] and in normalised-y units:
+ *   kbar_b(g)_j            = sum_s k_b(z_gs, X_j)                          mean_b(g) = kbar_b(g)^T alpha_b / S
+ *   prior_b(D; g, g')      = sum_s sum_s' k_b(Qss' + T(g, g')),   Qss' = sum_{k not in D} ((x_sk - x_s'k) / l_k)^2,
+ *                                                                  T    = sum_{k in D} ((g_k - g'_k) / l_k)^2
+ *   Cov[pd_b(g), pd_b(g')] = (prior_b(D; g, g') - kbar_b(g)^T K_b^-1 kbar_b(g')) / S^2          Var: g = g', T = 0
+ * mean and var are B*total doubles in bgp_partial_dependence's layout.  cov holds, per posterior, the ng[k1]^2 row-major blocks
+ * of the 1-D panels in list order (exactly symmetric; 2-D panels contribute nothing).  Any of the three may be NULL, not all.
+ * var and the diagonal of cov are clipped at 0; the diagonal of cov is var bit for bit.  mean is held to the precision model's
+ * tolerance, not the bits of bgp_partial_dependence.  A panel's values depend on the posterior, the samples, the grids and the
+ * panel alone: not on the other panels, on B, on the chunking (BGP_PDVAR_CHUNK) or on which outputs are asked for.
+ * Needs what bgp_partial_dependence needs, S <= 16384 (the prior is a pair sum) and, with cov, ng[k1] (ng[k1] + 1) / 2 * S (S + 1) / 2
+ * <= 2^38 for every 1-D panel (BGP_ERR_INVALID before anything is launched); B resident posteriors that are not per-row warped
+ * (BGP_ERR_STATE).
+ *   Replaces: nothing in the reference -- there the route is predict(return_cov=True) on the S synthesised rows of every cell.
+ */
+int bgp_partial_dependence_var(bgp_ctx* ctx, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
+                               const double* grid, int P, const int* panels, double* mean, double* var, double* cov);
+
+/*
  * Variance-based (Sobol') sensitivity of the surrogate mean by the pick-freeze design (csrc/bgp_sobol.hip),
  * for the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read).  With two
  * sample matrices A, Bm (N*d each, row-major) and T terms, term t the set of dimensions whose bits are set in masks[t]:
@@ -637,7 +658,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
  *   256; default by n and d; read at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
- *   default by n; read at every call), BGP_ITEM_CHUNK / BGP_ROW_CHUNK (upper bounds on the posteriors per chunk of the batched posterior
+ *   default by n; read at every call), BGP_PDVAR_CHUNK (cells per chunk of bgp_partial_dependence_var, rounded up to 128; default by
+ *   n; read at every call), BGP_ITEM_CHUNK / BGP_ROW_CHUNK (upper bounds on the posteriors per chunk of the batched posterior
  *   calls and on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval and bgp_paths_minimize; default: the
  *   scratch budgets alone; read at every call; a bound can shrink a chunk, never enlarge it: see bgp_chunk_stats).
  * Runtime switch set by the PYTHON package, not read by this library: bayes-skopt_amd/_lib.py exports HIP_FORCE_DEV_KERNARG=1 (kernel
