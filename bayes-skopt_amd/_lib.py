@@ -109,6 +109,12 @@ SIGNATURES = {
     "bgp_mixture_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp,
                                      _ip]),
     "bgp_mixture_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bgp_hyper_information": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp,
+                                        _ip]),
+    "bgp_hyper_information_warped": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp,
+                                               _dp, _ip]),
+    "bgp_information_values": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp,
+                                         _ip]),
     "bgp_pvrs": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "bgp_pvrs_prepare": (C.c_int, [_vp, _dp, C.c_int, _ip]),
     "bgp_fantasy_begin": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _ip, _dp, C.c_int,
@@ -675,6 +681,41 @@ class Context:
         out = (C.c_longlong * 2)()
         _check(self._lib.bgp_mixture_stats(self._h, out), "bgp_mixture_stats")
         return int(out[0]), int(out[1])
+
+    def _information(self, m, B, n_nodes, weights, call):
+        """Rule, weights and outputs shared by ``hyper_information`` and ``information_values``; ``call(tail, w)`` issues the C call."""
+        t, om = np.polynomial.hermite.hermgauss(int(n_nodes)) if int(n_nodes) >= 1 else (np.empty(0), np.empty(0))
+        t, om = _c(t), _c(om)
+        w = None
+        if weights is not None:
+            w = _c(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (B,):
+                raise ValueError("weights: one per row expected (%d), got %d" % (B, len(w)))
+        info, ent, nu = np.empty(m), np.empty(m), np.zeros(1, dtype=np.int32)
+        call((len(t), _p(t), _p(om), _p(info), _p(ent), _p(nu)), _p(w) if w is not None else C.cast(None, _dp))
+        return {"information": info, "entropy": ent, "n_used": int(nu[0])}
+
+    def hyper_information(self, H_kernel, Xq, y_mean, y_std, n_nodes=32, weights=None, warped=False):
+        """What an observation at each row of Xq tells about which of the first B resident posteriors is the right one: the mutual
+        information (nats) and the entropy of their mixture (y units), on the device behind the batched predict
+        (bgp_hyper_information; ``warped``: bgp_hyper_information_warped).  ``n_nodes``: the Gauss-Hermite rule (1..64)."""
+        H = self._H(H_kernel)
+        Xq = _c(np.atleast_2d(Xq))
+        B, m = H.shape[0], Xq.shape[0]
+        name = "bgp_hyper_information_warped" if warped else "bgp_hyper_information"
+        fn = getattr(self._lib, name)
+        return self._information(m, B, n_nodes, weights, lambda tail, w: _check(
+            fn(self._h, B, _p(H), w, m, _p(Xq), float(y_mean), float(y_std), *tail), name))
+
+    def information_values(self, mean, var, y_mean, y_std, n_nodes=32, weights=None):
+        """The same pass on given normalised (B, m) means / variances (bgp_information_values): no resident posterior is read."""
+        mean, var = _c(np.atleast_2d(mean)), _c(np.atleast_2d(var))
+        if mean.shape != var.shape:
+            raise ValueError("mean and var differ in shape")
+        B, m = mean.shape
+        return self._information(m, B, n_nodes, weights, lambda tail, w: _check(
+            self._lib.bgp_information_values(self._h, B, m, _p(mean), _p(var), w, float(y_mean), float(y_std), *tail),
+            "bgp_information_values"))
 
     def pvrs_prepare(self, h_kernel, has_alpha_vec):
         H = self._H(h_kernel)

@@ -16,7 +16,9 @@ Mirrors ``bask/acquisition.py``: the same class hierarchy (``UncertaintyAcquisit
   observation, one device call for all candidates and hyper-posterior rows (``bgp_knowledge_gradient``, DESIGN.md section 23);
 * ``JointEntropySearch`` is not in the reference either: the expected drop of the entropy of an observation once the optimum's
   location AND value are known, on optimum samples found continuously on the device (``PosteriorPaths.minimize``), one device call
-  for all candidates and hyper-posterior rows (``bgp_joint_entropy``).
+  for all candidates and hyper-posterior rows (``bgp_joint_entropy``, DESIGN.md section 25);
+* ``HyperInformation`` is not in the reference: the mutual information between an observation and the kernel hyper-parameters
+  (BALD) over the rows a ``tell`` draws, one device call for all candidates (``bgp_hyper_information``).
 """
 import sys
 from abc import ABC, abstractmethod
@@ -41,6 +43,7 @@ __all__ = [
     "knowledge_gradient_values",
     "JointEntropySearch",
     "joint_entropy_values",
+    "HyperInformation",
 ]
 
 
@@ -127,7 +130,10 @@ def evaluate_acquisitions(X, gpr, acquisition_functions=None, n_samples=10, prog
             else:
                 if _record is not None:  # (a batch replays the acquisition itself with the same generator state)
                     _record.setdefault("replay", {})[i_acq] = random_state.get_state()
-                vals = acq(X, gpr, random_state=random_state, **kwargs)
+                if type(acq) is HyperInformation:  # (on the rows this evaluation draws, not on rows of its own)
+                    vals = acq(X, gpr, rows=gpr.chain_[trace_i], random_state=random_state, **kwargs)
+                else:
+                    vals = acq(X, gpr, random_state=random_state, **kwargs)
             if np.all(np.isfinite(vals)):
                 out[i_acq] = vals
 
@@ -627,3 +633,26 @@ class JointEntropySearch(FullGPAcquisition):
         noise = _jes_noise(gp, np.exp(H[:, -1]))
         vals = gp._ctx.joint_entropy(noise_off(H), noise, X, A, f, tau, len(H), want_rows=False)[1]
         return (vals, "device") if return_path else vals
+
+
+# ---- information about the hyper-parameters ---------------------------------------------------------------
+class HyperInformation(FullGPAcquisition):
+    """BALD for the surrogate itself (Houlsby et al. 2011; Riis et al. 2022 for fully Bayesian GPs): the mutual information, in
+    nats, between an observation at x and the kernel hyper-parameters -- where the chain's rows disagree about what will be seen,
+    in mean, length scale or noise.  An acquisition for the first part of a run ("learn the surrogate first").
+
+    ``rows`` (B, p): the hyper-posterior rows; ``evaluate_acquisitions`` hands over the ``n_samples`` rows a ``tell`` draws, and
+    without them ``n_gp_samples`` rows are drawn without replacement from ``random_state``.  Every row keeps its own white level
+    (the hyper-parameters are learnt from an observation).  ONE batched posterior build and ONE device call
+    (``BayesGPR.hyper_information``: ``bgp_hyper_information``, its warped twin under ``warp_inputs``, the rows' moments and
+    ``bgp_information_values`` for generic kernel trees).  ``n_nodes``: the Gauss-Hermite rule.  Fewer than two rows:
+    ``ValueError`` -- a single GP holds no information about its own hyper-parameters."""
+
+    def __call__(self, X, gp, *args, rows=None, n_gp_samples=0, n_nodes=32, random_state=None, **kwargs):
+        if rows is None and n_gp_samples > 0:
+            rng = check_random_state(random_state)
+            rows = gp.chain_[rng.choice(len(gp.chain_), replace=False, size=int(n_gp_samples))]
+        if rows is None or len(rows) < 2:
+            raise ValueError("the information of a single GP about its own hyper-parameters is zero: HyperInformation needs at "
+                             "least two hyper-posterior rows (tell(..., n_samples >= 2))")
+        return gp.hyper_information(X, thetas=np.asarray(rows, dtype=np.float64), n_nodes=n_nodes, within=False)["information"]

@@ -1046,6 +1046,71 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out["quantiles"] = np.empty((0, X.shape[0]))
         return (out, path) if return_path else out
 
+    def hyper_information(self, X, thetas=None, n_samples=None, weights=None, noise=True, n_nodes=32, random_state=None,
+                          within=True, return_path=False):
+        """Where an observation would settle the hyper-parameters: at the rows of ``X`` (m, d; transformed space) the mutual
+        information, in nats, between an observation y(x) and the chain row under the hyper-posterior mixture of
+        ``predict_marginal`` (BALD; Houlsby et al. 2011), ``I(x) = sum_b w_b KL(N(mu_b, sd_b^2) || mixture)``.  It is at least 0, at
+        most the entropy of the weights (``log n_used`` for equal ones), and sees rows that agree on the mean and differ in length
+        scale or noise -- ``std_between`` of ``predict_marginal`` is only its second-moment shadow.  Rows and ``weights`` as in
+        ``predict_marginal`` (``n_samples=None``: the whole chain, up to the context's ``max_batch`` rows on the one-call route).
+        ``noise=True`` (default) keeps every row's own white level: the hyper-parameters are learnt from an observation, not from
+        the latent value.  ``n_nodes``: nodes of the Gauss-Hermite rule per component (1..64; DESIGN.md section 31 tabulates
+        what the rule costs in accuracy).
+
+        Returns a dict: ``information`` (m,); ``entropy`` (m,) of the mixture in y units; ``entropy_within`` =
+        ``sum_b w_b log(2 pi e sd_b^2) / 2``, the rows' own average entropy, from the rows' moments on the host (so that
+        ``information == entropy - entropy_within`` up to rounding and the rule's error; on the one-call route it costs one more
+        batched predict, ``within=False`` leaves it out); ``n_used`` and the ``rows``.  Routes as
+        ``predict_marginal``: canonical kernels with at most ``max_batch`` rows take ONE batched build and ONE device call
+        (``bgp_hyper_information``, under ``warp_inputs`` ``bgp_hyper_information_warped``); generic kernel trees and more rows
+        take the rows' moments chunk by chunk and ``bgp_information_values`` on them, said once on stderr.  An atom (a row with
+        ``sd = 0`` at a point) gives ``entropy = -inf`` and ``information = NaN`` there."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if self.warp_inputs:
+            validate_zeroone(X)
+        self._require_posterior()
+        if thetas is None:
+            chain = np.asarray(self.chain_)
+            rows = chain
+            if n_samples is not None:
+                rows = chain[check_random_state(random_state).choice(len(chain), replace=False, size=min(int(n_samples), len(chain)))]
+        else:
+            rows = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        y_mean, y_std = self._y_scale()
+        post, ctx = self._post, self._ctx
+        if post.canonical and len(rows) <= ctx.max_batch and self._warp_rows_path == "auto":
+            if self.warp_inputs:
+                n_theta = len(self.kernel_.theta)
+                H = self._canonical(rows[:, :n_theta])
+                status = ctx.posterior(H, want_alpha=False, warps=np.ascontiguousarray(rows[:, n_theta:]))["status"]
+                raise_if_not_pd(status, self.kernel_)
+            else:
+                H = post.build_rows(self, rows)
+            Hn = H if noise else noise_off(H)
+            out = ctx.hyper_information(Hn, X, y_mean, y_std, n_nodes=n_nodes, weights=weights, warped=bool(self.warp_inputs))
+            # (entropy_within alone needs the rows' own moments on the host: one more batched predict on the same posteriors)
+            if within:
+                mean, var = ctx.predict_warped(Hn, X) if self.warp_inputs else ctx.predict(Hn, X)
+                mu, sd = y_std * mean + y_mean, np.sqrt(var * y_std**2)
+            path = "device"
+        else:
+            _information_tell_once("generic kernel tree" if not post.canonical else "more rows than the context's max_batch")
+            step = max(1, int(ctx.max_batch))
+            parts = [self._predict_hyper_samples(rows[b0:b0 + step], X, noise_zero=not noise) for b0 in range(0, len(rows), step)]
+            mu, sd = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+            out = ctx.information_values(mu, sd * sd, 0.0, 1.0, n_nodes=n_nodes, weights=weights)  # (already in y units)
+            path = "chunks"
+        if within:
+            w = np.ones(len(rows)) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+            used = (w > 0.0) & np.isfinite(mu).all(axis=1) & np.isfinite(sd).all(axis=1)
+            out["entropy_within"] = np.full(X.shape[0], np.nan)
+            if used.any():
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    out["entropy_within"] = (w[used] / w[used].sum()) @ np.log(sd[used]) + 0.5 * np.log(2.0 * np.pi * np.e)
+        out["rows"] = rows
+        return (out, path) if return_path else out
+
     def _acq_hyper_samples(self, thetas, X, kinds, params, n_samples, noise_zero=True):
         """Closed-form acquisition values averaged over a batch of hyper-posterior draws, entirely on the device:
         batched posterior build, batched predict and the acquisition / averaging pass of
@@ -1168,7 +1233,8 @@ class BayesGPR(RegressorMixin, BaseEstimator):
                     scratch.theta = scratch.theta  # the median GP's posterior on the augmented set
                     rng = np.random.RandomState()
                     rng.set_state(replay)
-                    vals = np.asarray(acq(X, scratch, random_state=rng, **acq_kwargs), dtype=np.float64)
+                    extra = {"rows": rows} if type(acq) is A.HyperInformation else {}  # (the proposal's rows, as evaluate_acquisitions)
+                    vals = np.asarray(acq(X, scratch, random_state=rng, **extra, **acq_kwargs), dtype=np.float64)
                     vals = vals if np.all(np.isfinite(vals)) else np.zeros(X.shape[0])
                 elif full:
                     vals = scratch._pvrs(X, X if thompson is None else thompson, alpha0 is not None)
@@ -1562,6 +1628,15 @@ def _pathwise_tell_once(why):
 
 
 _marginal_told = []
+_information_told = []
+
+
+def _information_tell_once(why):
+    """One line on stderr, once per process: a hyper-parameter information whose rows' moments came back to the host in chunks."""
+    if not _information_told:
+        _information_told.append(True)
+        print("[bayes_skopt_amd] hyper_information: the rows' moments chunk by chunk through predict, then the information pass on "
+              "them (%s)" % why, file=sys.stderr, flush=True)
 
 
 def _marginal_tell_once(why):

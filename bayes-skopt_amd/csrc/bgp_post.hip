@@ -381,7 +381,8 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
 // rowwarp: the resident posteriors are per-row warped -- item b reads its own training inputs (c->dXwP) and its own warped copy of
 // the queries (one upload of the m rows, ONE warp launch over the B parameter sets in c->dwarpP); no cov there.
 static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, double* mean, double* var,
-                       double* cov, const AcqPlan* ap, bool rowwarp = false, const BgpMixPlan* mp = nullptr) {
+                       double* cov, const AcqPlan* ap, bool rowwarp = false, const BgpMixPlan* mp = nullptr,
+                       const BgpInfoPlan* ip = nullptr) {
   const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
   const size_t p = d + 2, sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
   const size_t qs = rowwarp ? (size_t)m * d : 0, xs = rowwarp ? (size_t)n * d : 0;  // per-item strides of queries / training inputs
@@ -391,6 +392,7 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   double *dXq, *dXq0 = nullptr, *dH, *dKs, *dmpart, *dqB, *doutB, *dP = nullptr, *dCov = nullptr;
   AcqScratch as;
   BgpMixScratch ms;
+  BgpInfoScratch is;
   BgpScratch live(c);
   BGP_TRY(live.carve([&](BgpCarve& s) {
     dXq = s.take<double>(rowwarp ? (size_t)B * qs : (size_t)m * d);  // (every item's warped queries: all B, as dqB / doutB)
@@ -406,6 +408,7 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
     }
     if (n_acq) as.take(s, n_acq, B, mpad);
     if (mp) ms.take(s, B, mpad, mp->Q);
+    if (ip) is.take(s, B, mpad);
   }));
   if (rowwarp) {
     BGP_HIP(bgp_memcpy_async(dXq0, Xq, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -433,8 +436,13 @@ static int predict_run(bgp_ctx* c, int B, const double* h_kernel, int m, const d
   }
   if (n_acq) BGP_TRY(acq_run(c, B, m, mpad, doutB, dqB, *ap, as));
   if (mp) BGP_TRY(bgp_mix_run(c, B, m, mpad, doutB, dqB, *mp, ms));  // the hyper-posterior mixture of the B rows (bgp_mix.hip)
+  if (ip) BGP_TRY(bgp_info_run(c, B, m, mpad, doutB, dqB, *ip, is));  // what an observation tells about the rows (bgp_info.hip)
   BGP_HIP(bgp_stream_sync(c->stream));
   return BGP_OK;
+}
+
+int bgp_predict_run_info(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, const BgpInfoPlan& ip, bool rowwarp) {
+  return predict_run(c, B, h_kernel, m, Xq, nullptr, nullptr, nullptr, nullptr, rowwarp, nullptr, &ip);
 }
 
 int bgp_predict_run_mix(bgp_ctx* c, int B, const double* h_kernel, int m, const double* Xq, const BgpMixPlan& mp, bool rowwarp) {

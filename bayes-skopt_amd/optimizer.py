@@ -17,11 +17,12 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
 ACQUISITION_FUNC = {
+    "bald": acquisition.HyperInformation(),
     "ei": acquisition.ExpectedImprovement(),
     "kg": acquisition.KnowledgeGradient(),
     "jes": acquisition.JointEntropySearch(),
@@ -339,6 +340,21 @@ class Optimizer:
         mean, within / between spread, mixture quantiles, P(f <= at) and the log predictive density (``utils.predict_marginal`` on
         the current result, same keyword arguments; the optimizer's own random state is not consumed)."""
         return predict_marginal(self._result(), X, **kw)
+
+    def hyper_information(self, X=None, **kw):
+        """Where an observation would settle the kernel hyper-parameters: the mutual information (nats) between an observation at
+        points ``X`` of the original space and the hyper-posterior's rows, with the mixture's entropy
+        (``utils.hyper_information`` on the current result, same keyword arguments; the optimizer's own random state is not
+        consumed).  ``X=None``: the candidates of the last proposal, on the rows that proposal drew where it drew more than one
+        (what ``acq_func="bald"`` maximised) unless ``thetas`` / ``n_samples`` say otherwise."""
+        if X is not None:
+            return hyper_information(self._result(), X, **kw)
+        if self._last_candidates is None:
+            raise RuntimeError("No proposal yet: tell() has not fit a model and proposed a point.")
+        rows = (self._last_batch_state or {}).get("rows")
+        if rows is not None and len(rows) > 1 and "thetas" not in kw and "n_samples" not in kw:
+            kw["thetas"] = rows
+        return self.gp.hyper_information(self._last_candidates, **kw)
 
     def _optimum_vs_space_draws(self, n_space_samples, n_gp_samples, n_random_starts, use_mean_gp, seed, minimizer="scipy"):
         """Function draws (device ``sample_y``) at [expected optimum, n_space_samples random points]:

@@ -479,6 +479,17 @@ def predict_marginal(res, X, **kw):
     return res.models[-1].predict_marginal(res.space.transform(X), **kw)
 
 
+def hyper_information(res, X, **kw):
+    """What an observation at points ``X`` of the ORIGINAL space would tell about the kernel hyper-parameters of the surrogate
+    ``res.models[-1]``: the mutual information in nats, the entropy of the hyper-posterior mixture and its within-GP part
+    (``BayesGPR.hyper_information`` on ``res.space.transform(X)``, same keyword arguments; ``bgp_hyper_information``, DESIGN.md
+    section 31)."""
+    X = list(X)
+    if X and not np.iterable(X[0]):
+        X = [X]
+    return res.models[-1].hyper_information(res.space.transform(X), **kw)
+
+
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):
     """Highest density interval(s) of a 1-d sample (the quantity ``bask/optimizer.py:684`` takes from
     ``arviz.hdi``; arviz is not part of this image, so its two estimators are restated):

@@ -260,6 +260,37 @@ int bgp_mixture_values(bgp_ctx* ctx, int B, int m, const double* mean, const dou
 int bgp_mixture_stats(bgp_ctx* ctx, long long* out);
 
 /*
+ * What an observation at a point would tell about the kernel hyper-parameters (BALD): the mutual information, in nats, between
+ * y(x) and the chain row under the mixture above,
+ *   information_i = sum_b w^_b KL(N(mu_bi, sd_bi^2) || sum_c w^_c N(mu_ci, sd_ci^2))     (0 <= information <= -sum w^ log w^),
+ * and entropy_i, the entropy of the mixture (y units).  Rows, weights, USED rows, mu / sd and *n_used are bgp_predict_mixture's; so
+ * are the three entries' inputs (bgp_hyper_information: the first B resident posteriors; _warped: per-row-warped ones;
+ * bgp_information_values: caller-supplied normalised mean / var, no resident posterior).  h_kernel's white level should be the
+ * rows' own: the hyper-parameters are learnt from an observation, not from the latent value.
+ * Neither number has a closed form.  The caller passes a Gauss-Hermite rule (nodes t_q, weights omega_q, 1 <= Q <= BGP_INFO_QMAX,
+ * for the weight exp(-t^2): numpy's hermgauss), and per point, over the used rows in ascending b,
+ *   y_bq = mu_b + (sqrt(2) sd_b) t_q,   own_bq = (log w^_b - log sd_b) - t_q^2,
+ *   a_c(y) = (log w^_c - log sd_c) - ((y - mu_c) (1 / sd_c))^2 / 2 for c != b,  a_b(y_bq) = own_bq,
+ *   lse_bq = A + log sum_c exp(a_c(y_bq) - A) with A = max_c a_c(y_bq)  (c ascending),
+ *   information = max(0, sum_{b,q} w^_b ((omega_q / sqrt(pi)) ((own_bq - lse_bq) - log w^_b))),
+ *   entropy     = log(2 pi) / 2 - sum_{b,q} w^_b ((omega_q / sqrt(pi)) lse_bq).
+ * One used row: information is exactly 0.  A used row whose sd is not > 0: entropy = -inf and information = NaN at that point.
+ * n_used == 0: every output is NaN, the call returns BGP_OK.  One wave per point adds its (b, q) terms in a fixed order: a point's two
+ * numbers are the same bits whatever m is and whichever points share the call.  Q outside 1..BGP_INFO_QMAX, a NULL rule or output,
+ * a rule entry, or a weight, that is negative (weights) or not finite: BGP_ERR_INVALID.
+ */
+#define BGP_INFO_QMAX 64
+int bgp_hyper_information(bgp_ctx* ctx, int B, const double* h_kernel, const double* weights, int m, const double* Xq, double y_mean,
+                          double y_std, int Q, const double* nodes, const double* wts, double* information, double* entropy,
+                          int* n_used);
+int bgp_hyper_information_warped(bgp_ctx* ctx, int B, const double* h_kernel, const double* weights, int m, const double* Xq,
+                                 double y_mean, double y_std, int Q, const double* nodes, const double* wts, double* information,
+                                 double* entropy, int* n_used);
+int bgp_information_values(bgp_ctx* ctx, int B, int m, const double* mean, const double* var, const double* weights, double y_mean,
+                           double y_std, int Q, const double* nodes, const double* wts, double* information, double* entropy,
+                           int* n_used);
+
+/*
  * PVRS inner loop with the resident posterior built by bgp_pvrs_prepare (K without the candidate
  * row):  for every candidate i
  *   covs[i] = sum_t k_t,aug^T K_aug,i^-1 k_t,aug ,   K_aug,i = kernel([X_train; x_i])
