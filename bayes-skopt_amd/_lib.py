@@ -138,6 +138,7 @@ SIGNATURES = {
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_shapley": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "bgp_hess_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "bgp_knowledge_gradient": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_joint_entropy": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
@@ -936,6 +937,29 @@ class Context:
         _check(self._lib.bgp_grad_cov(self._h, B, _p(H), m, _p(Xq), _p(dmean) if want_dmean else null,
                                       _p(cov) if want_cov else null, _p(csum) if want_csum else null), "bgp_grad_cov")
         return dmean, cov, csum
+
+    # ---- posterior of the Hessian (bgp_hess.hip)
+    def hess_cov(self, H_kernel, Xq, want_mean=True, want_var=True, want_cov=False):
+        """``bgp_hess_cov``: for the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2)) at the rows of ``Xq`` (m, d) the Hessian of
+        the mean ``hmean`` (B, m, d, d), the posterior variance of every entry of the latent function's Hessian ``hvar`` (B, m, d,
+        d) and the covariance of its vech ``hcov`` (B, m, T, T; T = d (d + 1) / 2, order (k, l), k >= l, row-major over the lower
+        triangle; exactly symmetric, diagonal clipped at 0; ``hvar`` is that diagonal).  Normalised-target units; an output that is
+        not wanted is None and is neither downloaded nor, where nothing needs it, computed.  Needs d <= 16, m pad16(T) <= 2^22,
+        RBF or Matern 5/2 and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        Xq = _c(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"query points must have {self.d} columns, got {Xq.shape[1]}")
+        m, d = Xq.shape[0], self.d
+        T = d * (d + 1) // 2
+        hmean = np.empty((B, m, d, d)) if want_mean else None
+        hvar = np.empty((B, m, d, d)) if want_var else None
+        hcov = np.empty((B, m, T, T)) if want_cov else None
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_hess_cov(self._h, B, _p(H), m, _p(Xq), _p(hmean) if want_mean else null,
+                                      _p(hvar) if want_var else null, _p(hcov) if want_cov else null), "bgp_hess_cov")
+        return hmean, hvar, hcov
 
     # ---- knowledge-gradient acquisition (bgp_kg.hip; DESIGN.md section 23)
     def knowledge_gradient(self, H_kernel, noise, Xcand, Xref, y_std, n_samples, want_rows=True):

@@ -9,7 +9,7 @@ import sys
 import numpy as np
 from sklearn.base import clone
 
-from . import gradcov
+from . import gradcov, hesscov
 from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
 
 _PD_MESSAGE = (
@@ -510,6 +510,32 @@ class CanonicalPosterior:
         parts = [call(self.built_H(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]
         return tuple(np.concatenate([p[i] for p in parts]) if want[i] else None for i in range(3)), "device"
 
+    hessian_cov_path = "auto"  # "host": always numpy on the downloaded inverse (tests compare the two paths)
+
+    def hessian_cov(self, gp, thetas, X, want_cov=False):
+        """((hmean (B, m, d, d), hvar (B, m, d, d), hcov (B, m, T, T) | None) in normalised-target units, "device" | "host").
+        ``thetas=None``: the resident median GP (B = 1); a block of chain rows: one batched build and ONE device call per
+        ``max_batch`` rows (``bgp_hess_cov``).  More than 16 dimensions, or ``hessian_cov_path = "host"``:
+        ``hesscov.hessian_cov_host``, said once; with chain rows the host path builds every row as posterior 0 of the context to
+        download its inverse (as ``gradcov.host_rows`` does), so the median GP's posterior is no longer the resident one afterwards
+        and the next call that needs it makes it resident again (section 28).  Matern 1/2 and 3/2: ValueError; ``warp_inputs``: NotImplementedError (the chain
+        rule through the Beta pdf is not built)."""
+        hesscov.check_twice_differentiable(gp._plan.stationary)
+        if gp.warp_inputs:
+            raise NotImplementedError("the Hessian covariance is not available with warp_inputs=True: the derivative with respect "
+                                      "to the un-warped coordinates needs the chain rule through the Beta pdf")
+        d = gp._X_train_.shape[1]
+        if d > hesscov.HESS_DMAX or self.hessian_cov_path == "host":
+            hmean, hvar, hcov = hesscov.host_rows(gp, thetas, X, "more than 16 dimensions" if d > hesscov.HESS_DMAX else "forced")
+            return (hmean, hvar, hcov if want_cov else None), "host"
+        call = lambda H: gp._ctx.hess_cov(H, X, want_mean=True, want_var=True, want_cov=want_cov)  # noqa: E731
+        if thetas is None:
+            return call(self.built_H(gp, None)), "device"
+        thetas = np.atleast_2d(thetas)
+        step = max(1, int(gp._ctx.max_batch))  # (the batched build holds max_batch rows: one build and one call per block)
+        parts = [call(self.built_H(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]
+        return tuple(np.concatenate([p[i] for p in parts]) if parts[0][i] is not None else None for i in range(3)), "device"
+
     def cross_validate(self, gp, thetas, folds, warps=None):
         """(mean (B, n), var (B, n), fold_lpd (B, K), status (B, K)) of the held-out observations, normalised-target units
         (``bgp_cross_validate``).  ``thetas=None``: the resident median GP; a block of chain rows (``warps``
@@ -635,6 +661,10 @@ class GramPosterior:
     def gradient_cov(self, gp, thetas, X, want):
         raise NotImplementedError("the gradient covariance needs a canonical kernel: a generic kernel tree has no closed-form "
                                   "cross derivative")
+
+    def hessian_cov(self, gp, thetas, X, want_cov=False):
+        raise NotImplementedError("the Hessian covariance needs a canonical kernel: a generic kernel tree has no closed-form "
+                                  "second derivative")
 
     def cross_validate(self, gp, thetas, folds, warps=None):
         """As ``CanonicalPosterior.cross_validate``: the device call reads the resident inverses alone, so host kernel matrices

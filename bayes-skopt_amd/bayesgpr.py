@@ -879,6 +879,29 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out = tuple(v[0] for v in out)
         return (*out, path) if return_path else out
 
+    def hessian_posterior(self, X, thetas=None, return_cov=False, return_path=False):
+        """The posterior distribution of the Hessian of the latent function at the rows of ``X`` (m, d; transformed space):
+        ``(hess_mean (m, d, d), hess_std (m, d, d))`` in y units per unit of the transformed coordinate squared -- every entry of the
+        Hessian is normal with that mean (the Hessian of the predictive mean, exactly symmetric) and that sd, so ``hess_mean[:, k,
+        l] / hess_std[:, k, l]`` says whether a curvature is distinguishable from zero.  ``return_cov``: also ``hess_cov`` (m, T,
+        T), the covariance of vech H in the order (k, l), k >= l, row-major over the lower triangle (T = d (d + 1) / 2; exactly
+        symmetric, diagonal clipped at 0).  For the median GP (``thetas=None``), or with a leading axis B for a block of B chain
+        rows.  RBF and Matern 5/2 kernels in up to 16 dimensions: ONE device call (``bgp_hess_cov``); more
+        dimensions: numpy on the downloaded inverse, said once on stderr.  Matern 1/2 and 3/2 have no mean-square second
+        derivative: ValueError.  Generic kernel trees and ``warp_inputs=True``: NotImplementedError.  ``return_path``: also
+        "device" | "host"."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        self._require_posterior()
+        d = self._X_train_.shape[1]
+        if X.shape[1] != d or X.shape[0] < 1:
+            raise ValueError(f"the points must be (m, {d}) with m >= 1, got {X.shape}")
+        (hmean, hvar, hcov), path = self._post.hessian_cov(self, thetas, X, want_cov=bool(return_cov))
+        y_std = self._y_scale()[1]
+        out = (y_std * hmean, y_std * np.sqrt(hvar)) + ((y_std**2 * hcov,) if return_cov else ())
+        if thetas is None:
+            out = tuple(v[0] for v in out)
+        return (*out, path) if return_path else out
+
     def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
         """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the
         held-out OBSERVATIONS ``y_F`` given the remaining points -- without a refit: it follows from the resident ``K^-1`` and

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, inverse_unrounded, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
@@ -315,6 +315,14 @@ class Optimizer:
         """Which directions matter: the eigen-decomposition of the active-subspace matrix of the current surrogate
         (``utils.active_subspace`` on the current result, same keyword arguments)."""
         return active_subspace(self._result(), **kw)
+
+    def optimum_curvature(self, x=None, delta=None, n_gp_samples=0, n_draws=1000, random_state=None):
+        """How sharp is the optimum: the posterior of the surrogate's Hessian at ``x`` (default: the current expected optimum),
+        its eigen-directions, the tolerance of every parameter for a loss of ``delta`` (default: the noise sd) and the probability
+        that the point is a minimum at all (``utils.optimum_curvature`` on the current result; the optimizer's own random state
+        is not consumed)."""
+        return optimum_curvature(self._result(), x=x, delta=delta, n_gp_samples=n_gp_samples, n_draws=n_draws,
+                                 random_state=random_state)
 
     def sensitivity_indices(self, **kw):
         """Which dimensions matter and which interact: first-order, total and pair-interaction Sobol' indices of the current

@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -448,6 +448,55 @@ def active_subspace(res, n_samples=1024, samples=None, n_gp_samples=0, random_st
         thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
     C_mean, C_cov, path = reg.active_subspace(Xs, thetas=thetas, return_path=True)
     return assemble(C_mean, C_cov, path)
+
+
+def optimum_curvature(res, x=None, delta=None, n_gp_samples=0, n_draws=1000, random_state=None):
+    """How sharp is the optimum: the posterior of the Hessian of the surrogate ``res.models[-1]`` at ``x`` (original space;
+    default: the current expected optimum, ``expected_optimum(res, random_state=random_state)``), in transformed (unit-cube)
+    coordinates (``BayesGPR.hessian_posterior``, ``bgp_hess_cov``).  ``delta`` (y units; default: the median
+    GP's noise sd, "one observation's worth of noise") is the loss the tolerances are stated for.  Returns a dict: ``"x"``
+    (transformed), ``"hessian"`` and ``"hessian_std"`` (d, d; y units); ``"eigenvalues"`` ascending with ``"eigenvectors"`` as
+    columns, each signed so that its largest-magnitude component is positive -- the first is the flattest direction;
+    ``"tolerance_conditional"`` ``sqrt(2 delta / H_kk)``, how far coordinate k can move with the others held, and
+    ``"tolerance_marginal"`` ``sqrt(2 delta (H^-1)_kk)``, with the others re-optimised (NaN where H is not positive definite);
+    ``"interval"``: per dimension ``x -/+ tolerance_marginal`` clipped to the cube and mapped back endpoint by endpoint through the
+    space's inverse transform; ``"prob_minimum"``: the share of ``n_draws`` seeded draws ``vech H ~ N(mean, hess_cov)`` whose
+    smallest eigenvalue is positive -- is the point a minimum at all within the GP's own uncertainty; ``"band"``: the 5 % / 95 %
+    band of the ranked eigenvalues and of both tolerances over those draws; ``"delta"``, ``"path"``: "device" | "host".
+    ``n_gp_samples > 0``: mean and covariance per row drawn from ``chain_`` with ``random_state``, the draws dealt over the rows, so
+    that the band holds what the GPs and what the hyper-parameters are unsure about; ``"hessian"`` is then the average over the
+    rows.  Categorical dimensions have no curvature: ValueError."""
+    from sklearn.utils import check_random_state
+
+    from .hesscov import assemble_curvature
+    from .space import Categorical
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    if space.is_partly_categorical:
+        names = [k for k, dim in enumerate(space.dimensions) if isinstance(dim, Categorical)]
+        raise ValueError(f"optimum_curvature needs a space without Categorical dimensions: dimension(s) {names} have no curvature")
+    if x is None:
+        x = expected_optimum(res, random_state=rng)[0]
+    xt = np.asarray(space.transform([list(x)]), dtype=np.float64)
+    if delta is None:
+        if getattr(reg, "noise_", None) is None:
+            raise ValueError("the surrogate has no fitted noise level: pass delta (y units)")
+        delta = float(np.sqrt(reg.noise_)) * float(reg._y_scale()[1])
+    if not delta > 0.0:
+        raise ValueError(f"delta must be positive, got {delta}")
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    hmean, hstd, hcov, path = reg.hessian_posterior(xt, thetas=thetas, return_cov=True, return_path=True)
+    out = assemble_curvature(xt[0], hmean[..., 0, :, :], hstd[..., 0, :, :] ** 2, hcov[..., 0, :, :], delta, int(n_draws), rng, path)
+    open_ = np.isnan(out["tolerance_marginal"])  # (no interval where H is not positive definite)
+    half = np.where(open_, 0.0, out["tolerance_marginal"])
+    lo, hi = (space.inverse_transform(np.clip(xt + s * half, 0.0, 1.0))[0] for s in (-1.0, 1.0))
+    out["interval"] = [None if open_[k] else (lo[k], hi[k]) for k in range(space.n_dims)]
+    return out
 
 
 def cross_validate(res, n_folds=None, n_samples=0, folds=None, weights="is", random_state=None):

@@ -120,7 +120,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_hess_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -384,7 +384,7 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
  * bgp_paths_stats: out[0] = begins, out[1] = evals run on this context.
  * bgp_chunk_stats: how the context's last call to an entry point that cuts its work by a scratch budget ran -- bgp_predict_batch /
  *   _warped / _gram, bgp_acq_batch, bgp_predict_mixture, bgp_sample_y_batch, bgp_knowledge_gradient, bgp_joint_entropy, bgp_grad_cov,
- *   bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize: out[0] = chunks of posteriors, out[1] = chunks of query rows,
+ *   bgp_hess_cov, bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize: out[0] = chunks of posteriors, out[1] = chunks of query rows,
  *   candidates or starts (per chunk of posteriors); a loop the entry point does not have counts as one chunk.  Host counters only.
  *   BGP_ITEM_CHUNK / BGP_ROW_CHUNK (below) force several chunks at small shapes (tests/test_gpu_chunk_loops.py).
  * bgp_paths_minimize: minimise every open path over the box [lo, hi] (d doubles each) from its OWN S starts,
@@ -552,6 +552,29 @@ int bgp_shapley(bgp_ctx* ctx, int B, const double* h_kernel, int P, const double
 int bgp_grad_cov(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* dmean, double* cov, double* csum);
 
 /*
+ * Posterior of the surrogate's Hessian (csrc/bgp_hess.hip), for the resident posteriors 0 .. B-1 (h_kernel
+ * B*(d + 2) as in bgp_predict_batch; the white level is not read: the latent function) at the m query rows Xq (m*d, row-major).  With
+ * z_k = (x_k - X_jk) / l_k, fac(r) = S'(r) / r as in bgp_predict_grad_batch, fac2(r) = fac'(r) / r (RBF: exp(-r^2 / 2); Matern 5/2:
+ * (25 / 3) exp(-sqrt5 r)), psi = fac2(0), cf = c in the product form and 1 in the sum form (the constant and white terms add
+ * nothing), T = d (d + 1) / 2 and vech order (k, l), k >= l, row-major over the lower triangle:
+ *   h_kl(j) = cf [fac delta_kl / l_k^2 + fac2 z_k z_l / (l_k l_l)]                     row (k, l) of R(x), T x n
+ *   Hbar    = R(x) alpha                                                               hmean  B*m*d*d   Hessian of the mean
+ *   P0[(k,l),(p,q)] = cf psi (delta_kl delta_pq + delta_kp delta_lq + delta_kq delta_lp) / (l_k l_l l_p l_q)
+ *   Cov[H_kl, H_pq] = P0 - R(x) K^-1 R(x)^T                                            hcov   B*m*T*T   posterior covariance
+ *   Var[H_kl]       = its diagonal, entry (k, l) and (l, k)                            hvar   B*m*d*d
+ * in normalised-y units per unit of the (transformed) input squared; K^-1 and alpha are the resident ones.  Any output may be NULL,
+ * not all three; hmean alone skips the product.  hmean and hcov are exactly symmetric (the lower triangle is computed and mirrored),
+ * the diagonal of hcov is clipped at 0 as bgp_predict_batch clips the variance, and hvar is that diagonal bit for bit.  The product
+ * R K^-1 runs on the fp64 MFMA ring and the contraction on fp64 MFMA tiles, every sum in a fixed order: a point's outputs are the
+ * same bits whatever m and B are, whatever else shares the call, whichever outputs are asked for and however the call is chunked.
+ * Needs d <= 16, 1 <= m, m pad16(T) <= 2^22, 1 <= B <= 65535, a family with a mean-square second derivative -- Matern 3/2 and 1/2
+ * have none and are refused, never approximated -- and no context-level warp: BGP_ERR_INVALID before anything is launched; B
+ * resident posteriors: BGP_ERR_STATE.  A refused call leaves the resident posteriors as they were.
+ *   Replaces: nothing in the reference.
+ */
+int bgp_hess_cov(bgp_ctx* ctx, int B, const double* h_kernel, int m, const double* Xq, double* hmean, double* hvar, double* hcov);
+
+/*
  * Knowledge-gradient acquisition (csrc/bgp_kg.hip) of the resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as
  * in bgp_acq_batch: the white level at -inf, the latent function) at the m candidates Xcand (m*d, row-major) against the M reference
  * points Xref (M*d; not read at M = 0).  noise (B): the variance of a fantasy observation per posterior, as bgp_fantasy_begin takes
@@ -688,7 +711,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   at the head of their ticket list; default by shape), BGP_SYRK_GEN (0 / 1: on the launch schedule, every Gram block by the
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
- *   256; default by n and d; read at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
+ *   256; default by n and d; read at every call), BGP_HESS_CHUNK (query points per chunk of bgp_hess_cov; default by n and d; read
+ *   at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
  *   default by n; read at every call), BGP_PDVAR_CHUNK (cells per chunk of bgp_partial_dependence_var, rounded up to 128; default by
  *   n; read at every call), BGP_ITEM_CHUNK / BGP_ROW_CHUNK (upper bounds on the posteriors per chunk of the batched posterior
  *   calls and on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval and bgp_paths_minimize; default: the
