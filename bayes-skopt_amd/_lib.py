@@ -95,6 +95,7 @@ SIGNATURES = {
     "bgp_ctx_set_warp": (C.c_int, [_vp, _dp]),
     "bgp_beta_cdf": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "bgp_lml_grad_batch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _ip]),
+    "bgp_lml_hess_batch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "bgp_kernel_matrix": (C.c_int, [_vp, _dp, _dp]),
     "bgp_posterior_batch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
     "bgp_predict_batch": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -493,6 +494,20 @@ class Context:
         self._drop_resident()
         _check(self._lib.bgp_lml_grad_batch(self._h, B, _p(H), _p(out), _p(grad), _p(st)), "bgp_lml_grad_batch")
         return out, grad, st
+
+    def lml_hess(self, H):
+        """``bgp_lml_hess_batch``: (lml (B,), grad (B, p), hess (B, p, p), status (B,)) with respect to the canonical vectors of
+        ``H`` (B, d + 2); ``hess`` is symmetric bit for bit, ``lml`` and ``grad`` are ``lml_grad``'s.  More than 16 dimensions:
+        BgpError (``lmlhess.lml_hess_host`` is the numpy path).  Nothing stays resident."""
+        H = self._H(H)
+        B = H.shape[0]
+        out = np.empty(B)
+        grad = np.empty((B, self.p))
+        hess = np.empty((B, self.p, self.p))
+        st = np.zeros(B, dtype=np.int32)
+        self._drop_resident()
+        _check(self._lib.bgp_lml_hess_batch(self._h, B, _p(H), _p(out), _p(grad), _p(hess), _p(st)), "bgp_lml_hess_batch")
+        return out, grad, hess, st
 
     def kernel_matrix(self, h):
         H = self._H(h)

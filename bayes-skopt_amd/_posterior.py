@@ -9,7 +9,7 @@ import sys
 import numpy as np
 from sklearn.base import clone
 
-from . import gradcov, hesscov
+from . import gradcov, hesscov, lmlhess
 from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
 
 _PD_MESSAGE = (
@@ -319,6 +319,29 @@ class CanonicalPosterior:
             return lml, gp._plan.grad_to_theta(gh, gp._X_train_.shape[1])
         return gp._ctx.lml(H), None
 
+    lml_hess_path = "auto"  # "host": always numpy on the downloaded inverse (tests compare the two paths)
+
+    def lml_hess(self, gp, theta):
+        """(LML, gradient (p,), Hessian (p, p), status, "device" | "host") at ONE theta, derivatives with respect to theta.  Up to
+        16 dimensions: ``bgp_lml_hess_batch`` (nothing stays resident).  More dimensions, or
+        ``lml_hess_path = "host"``: ``lmlhess.lml_hess_host`` on the downloaded inverse, said once (the posterior at ``theta`` is
+        the resident one afterwards).  The training inputs are the context's: a context-level warp is a fixed warp."""
+        d = gp._X_train_.shape[1]
+        H = gp._canonical(theta)
+        if d <= lmlhess.LMLHESS_DMAX and self.lml_hess_path != "host":
+            lml, gh, Hc, st = gp._ctx.lml_hess(H)
+            path = "device"
+        else:
+            lmlhess._tell_once("more than 16 dimensions" if d > lmlhess.LMLHESS_DMAX else "forced")
+            res = gp._ctx.posterior(H, want_alpha=True, want_K_inv=True)
+            lml, st = res["lml"], res["status"]
+            gh, Hc = np.zeros((1, d + 2)), np.zeros((1, d + 2, d + 2))
+            if st[0] == 0:
+                Hc[0] = lmlhess.lml_hess_host(gp.X_train_, H[0], res["K_inv"][0], res["alpha"][0], gp._plan.stationary, gp._plan.form)
+                gh = gp._ctx.lml_grad(H)[1]
+            path = "host"
+        return float(lml[0]), gp._plan.grad_to_theta(gh, d)[0], gp._plan.hess_to_theta(Hc[0], d), int(st[0]), path
+
     def lml_begin(self, gp, T, W):
         """Put the block's LML batch on the device (``W``: per-row input warps) and return at once."""
         H = gp._canonical(T)
@@ -595,6 +618,19 @@ class GramPosterior:
             vals[i] = res["lml"][0]
             grads[i] = 0.5 * (np.einsum("i,ijk,j->k", a, Kg, a) - np.einsum("ij,ijk->k", Ki, Kg))
         return vals, grads
+
+    def lml_hess(self, gp, theta):
+        """As ``CanonicalPosterior.lml_hess`` for a kernel object: its gradient tensor and central differences of it on the host,
+        factorisation, alpha and K^-1 on the device (``lmlhess.lml_hess_generic``); always "host"."""
+        lmlhess._tell_once("generic kernel tree")
+        theta = np.asarray(theta, dtype=np.float64)
+        vals, grads = self.lml(gp, theta[None, :], True)
+        res = self._posterior_gram(gp, gp._gram_stack(theta), want_alpha=True, want_K_inv=True)
+        st = int(res["status"][0])
+        Hm = np.zeros((len(theta), len(theta)))
+        if st == 0:
+            Hm = lmlhess.lml_hess_generic(gp.kernel_, theta, gp.X_train_, res["K_inv"][0], res["alpha"][0])
+        return float(vals[0]), grads[0], Hm, st, "host"
 
     def lml_begin(self, gp, T, W):
         return PendingLml((T, W))  # host kernel matrices: nothing to overlap the priors with

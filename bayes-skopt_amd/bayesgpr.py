@@ -902,6 +902,49 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out = tuple(v[0] for v in out)
         return (*out, path) if return_path else out
 
+    def hyper_laplace(self, theta=None, priors=None, n_samples=0, random_state=None):
+        """The Laplace (Gaussian) approximation of the hyper-posterior ``LML(theta) + log prior(theta)`` from its curvature at the
+        mode.  ``theta=None``: the mode is found from the fitted theta by the MAP start's optimiser on
+        LML + log prior (``optimizer=None``: the fitted theta as it is); a ``theta`` that is given is used as it is.
+        ``priors`` as ``sample`` takes them (default ``guess_priors``); their derivatives are central differences on the host.
+        Returns a dict: ``mode`` (p,), ``cov`` (p, p) the inverse of the negative Hessian, ``sd``, ``corr``, ``log_evidence`` =
+        ``lml + log prior + p / 2 log 2 pi - 1/2 log det(-H)`` -- comparable between kernels on the same data --, ``lml``,
+        ``log_prior``, ``hessian`` (of the log posterior), ``negative_definite`` (False: ``cov``, ``sd``, ``corr`` and
+        ``log_evidence`` are NaN, nothing is raised), ``path`` "device" (canonical kernels in up to 16 dimensions: ONE call of
+        ``bgp_lml_hess_batch``) | "host" (more dimensions or generic kernel trees: numpy on the downloaded inverse, said once on
+        stderr), and with ``n_samples > 0`` ``samples`` (n_samples, p): seeded draws from the Gaussian clipped to the kernel's
+        bounds, accepted wherever a method takes ``thetas=`` and as ``position=`` of ``fit`` / ``sample``.  ``warp_inputs=True``:
+        NotImplementedError (the hyper-posterior there includes the 2d warp parameters, which this Hessian does not cover)."""
+        from . import lmlhess
+
+        if self.warp_inputs:
+            raise NotImplementedError("hyper_laplace is not available with warp_inputs=True: the hyper-posterior includes the 2d "
+                                      "warp parameters, which the LML Hessian does not cover")
+        self._require_posterior("hyper_laplace")
+        if priors is None:
+            priors = guess_priors(self.kernel_)
+        bounds = np.asarray(self.kernel_.bounds, dtype=np.float64)
+        if theta is None:
+            theta = np.array(self._post_theta, dtype=np.float64, copy=True)
+            if self.optimizer is not None and len(theta) > 0:
+                def obj(t):
+                    lml, grad = self.log_marginal_likelihood(t, eval_gradient=True, clone_kernel=False)
+                    lp, gp_, _ = lmlhess.prior_derivatives(priors, t)
+                    val = lml + lp
+                    return (-val, -(grad + gp_)) if np.isfinite(val) else (np.inf, np.zeros_like(t))
+
+                theta = np.asarray(self._constrained_optimization(obj, theta, bounds)[0], dtype=np.float64)
+        theta = np.asarray(theta, dtype=np.float64).ravel()
+        if theta.shape != (len(bounds),) or not np.all(np.isfinite(theta)):
+            raise ValueError(f"theta must be {len(bounds)} finite log-space hyper-parameters, got {theta}")
+        with self._keeping_posterior():
+            lml, _grad, Hm, status, path = self._post.lml_hess(self, theta)
+        lp, _gp, Hp = lmlhess.prior_derivatives(priors, theta)
+        hess = Hm + Hp if status == 0 else np.full_like(Hm, np.nan)
+        out = lmlhess.laplace(theta, lml + lp, hess, bounds, int(n_samples), check_random_state(random_state))
+        out.update(lml=lml, log_prior=lp, path=path)
+        return out
+
     def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
         """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the
         held-out OBSERVATIONS ``y_F`` given the remaining points -- without a refit: it follows from the resident ``K^-1`` and

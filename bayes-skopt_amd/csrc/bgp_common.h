@@ -395,7 +395,7 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
@@ -438,7 +438,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
 }
 
 // ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
-// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
+// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
 // path is the body's own.
@@ -545,6 +545,14 @@ int bgp_rowquad_tile();
 __global__ void pdep_scale_kernel(const double* __restrict__ in, int rows, int d, const double* __restrict__ H, double* __restrict__ out);
 // bgp_post.hip: out[b][i] = sum_t part[(b tn + t) M + i], t ascending (out packed with stride M); grid (ceil(M / 256), items)
 __global__ void rowdot_reduce_kernel(const double* __restrict__ part, int tn, int M, double* __restrict__ out);
+// bgp_post.hip, the two launches of bgp_lml_grad_batch (bgp_lmlhess.hip launches them as they are: the gradient's bits).  gpart[b][tile][k]:
+// the lower-triangular tile's share of g_k; grid 8 ceil(B / 8) tiles
+__global__ void __launch_bounds__(256) lml_grad_kernel(const double* __restrict__ X, const double* __restrict__ H,
+                                                        const double* __restrict__ Kinv, const double* __restrict__ alpha_sol,
+                                                        double* __restrict__ gpart, int n, int d, int npad, int nblk, int form,
+                                                        int stat, int B);
+// grad[b][k] = sum over the tiles, ascending; grid (B), p threads rounded up to 64
+__global__ void grad_reduce_kernel(const double* __restrict__ gpart, double* __restrict__ grad, int ntiles, int p);
 // bgp_post.hip: var[b][i] = max(0, kernel_.diag of H[b] incl. the white level - q[b][i]), i < m; grid (ceil(m / 256), items)
 __global__ void finish_var_kernel(const double* __restrict__ q, size_t sq, const double* __restrict__ H, int d, int form,
                                   int m, double* __restrict__ var, size_t so);

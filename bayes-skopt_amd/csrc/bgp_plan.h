@@ -28,7 +28,7 @@ enum BgpSwitch {
   BGP_SW_WAIT, BGP_SW_DEBUG_TIMES, BGP_SW_PS_COOLDOWN, BGP_SW_PS_TIMEOUT_MS, BGP_SW_PS_TIMEOUT_TICKS, BGP_SW_PS_PAIR, BGP_SW_PS_GEN,
   BGP_SW_PS_TRACE, BGP_SW_COMM_TIMEOUT_S,
   BGP_SW_SYRK_GEN, BGP_SW_GCOV_CHUNK, BGP_SW_KG_CHUNK, BGP_SW_JES_CHUNK, BGP_SW_ITEM_CHUNK, BGP_SW_ROW_CHUNK, BGP_SW_PDVAR_CHUNK,
-  BGP_SW_HESS_CHUNK,
+  BGP_SW_HESS_CHUNK, BGP_SW_LMLHESS_CHUNK,
   BGP_SW_COUNT
 };
 enum BgpSwitchRead { BGP_READ_CONTEXT, BGP_READ_PROCESS, BGP_READ_CALL };
@@ -60,6 +60,7 @@ static const BgpSwitchRow bgp_switches[BGP_SW_COUNT] = {
     {"BGP_ROW_CHUNK", BGP_READ_CALL, "by the scratch budget", "upper bound on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize (tests)"},
     {"BGP_PDVAR_CHUNK", BGP_READ_CALL, "by n", "cells per chunk of bgp_partial_dependence_var, rounded up to 128 (tests: a forced 128 against the default)"},
     {"BGP_HESS_CHUNK", BGP_READ_CALL, "by n and d", "query points per chunk of bgp_hess_cov (tests: a small chunk against the default)"},
+    {"BGP_LMLHESS_CHUNK", BGP_READ_CALL, "by the scratch budget", "upper bound on the matrices per chunk of bgp_lml_hess_batch (tests: a forced chunk against the default)"},
 };
 // read elsewhere: by the Python layer and bench.py, never by libbgp.so
 static const char* const bgp_switches_elsewhere[] = {"BGP_COMM_DIR", "BGP_COMM_PORT", "BGP_COMM_TCP", "BGP_COMM_JOB",

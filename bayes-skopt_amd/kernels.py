@@ -215,6 +215,27 @@ class KernelPlan:
             out[:, self.white[1]] += G[:, d + 1]
         return out
 
+    def jacobian(self, d):
+        """dh / dtheta (d + 2, p): the linear map behind ``canonical`` (``grad_to_theta`` is its transpose applied to a gradient)."""
+        J = np.zeros((d + 2, self.n_theta))
+        if self.const[0] == "free":
+            J[0, self.const[1]] = 1.0
+        if self.ell[0] == "free":
+            idx = self.ell[1]
+            if len(idx) == 1:
+                J[1 : d + 1, idx[0]] = 1.0
+            else:
+                J[np.arange(1, d + 1), idx] = 1.0
+        if self.white[0] == "free":
+            J[d + 1, self.white[1]] = 1.0
+        return J
+
+    def hess_to_theta(self, Hc, d):
+        """d2LML / dh2 (d + 2, d + 2) -> d2LML / dtheta2 (p, p): ``J^T Hc J`` (isotropic length scales sum over the replicated rows
+        and columns, fixed entries drop out; the map is linear, so no gradient term enters)."""
+        J = self.jacobian(d)
+        return J.T @ np.asarray(Hc, dtype=np.float64) @ J
+
 
 def _flatten(kernel, cls):
     if isinstance(kernel, cls):

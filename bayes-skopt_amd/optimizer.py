@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, hyper_laplace, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
@@ -323,6 +323,11 @@ class Optimizer:
         is not consumed)."""
         return optimum_curvature(self._result(), x=x, delta=delta, n_gp_samples=n_gp_samples, n_draws=n_draws,
                                  random_state=random_state)
+
+    def hyper_laplace(self, **kw):
+        """Are the hyper-parameters identified: the Laplace approximation of the current surrogate's hyper-posterior
+        (``utils.hyper_laplace`` on the current result, same keyword arguments)."""
+        return hyper_laplace(self._result(), **kw)
 
     def sensitivity_indices(self, **kw):
         """Which dimensions matter and which interact: first-order, total and pair-interaction Sobol' indices of the current

@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "hyper_laplace", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -537,6 +537,14 @@ def hyper_information(res, X, **kw):
     if X and not np.iterable(X[0]):
         X = [X]
     return res.models[-1].hyper_information(res.space.transform(X), **kw)
+
+
+def hyper_laplace(res, **kw):
+    """Are the hyper-parameters of the surrogate ``res.models[-1]`` identified, and how well does its kernel explain the data: the
+    Laplace approximation of the hyper-posterior -- mode, covariance, sd and correlations of the log-space hyper-parameters, the
+    log evidence, and seeded draws usable as ``thetas=`` (``BayesGPR.hyper_laplace``, same keyword arguments;
+    ``bgp_lml_hess_batch``)."""
+    return res.models[-1].hyper_laplace(**kw)
 
 
 def hdi(samples, hdi_prob=0.95, multimodal=False, max_modes=10, grid=512):

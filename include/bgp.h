@@ -121,7 +121,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
  *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_hess_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
- *   bgp_pvrs_prepare, bgp_lml_grad_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
+ *   bgp_pvrs_prepare, bgp_lml_grad_batch, bgp_lml_hess_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
 int bgp_ctx_set_warp(bgp_ctx* ctx, const double* warp);
@@ -148,6 +148,18 @@ int bgp_lml_batch_wait(bgp_ctx* ctx, double* lml, int* status);
  * kernels.py:1746-1766) driven by L-BFGS-B inside fit (bask/bayesgpr.py:607).
  */
 int bgp_lml_grad_batch(bgp_ctx* ctx, int B, const double* h, double* lml, double* grad, int* status);
+
+/*
+ * LML, gradient and Hessian w.r.t. the canonical vector (csrc/bgp_lmlhess.hip).  With alpha = K^-1 y,
+ * W = alpha alpha^T - K^-1, D_k = dK/dh_k and D_kl = d2K/dh_k dh_l:
+ *     H_kl = 1/2 tr(W D_kl) - (D_k alpha)^T K^-1 (D_l alpha) + 1/2 tr(K^-1 D_k K^-1 D_l)
+ * hess is B*(d+2)*(d+2), symmetric bit for bit, both triangles written; lml and grad carry bgp_lml_grad_batch's bits.  The
+ * posteriors are built from the context's inputs (a context-level warp counts as a fixed warp) and dropped afterwards, as
+ * bgp_lml_grad_batch does.  A matrix's Hessian does not depend on B, its position in the batch or the chunking
+ * (BGP_LMLHESS_CHUNK).  status[b] != 0 (failed pivot): lml[b] = -inf, zeros in grad and hess.  d > 16: BGP_ERR_INVALID, nothing
+ * launched.  The curvature at the MAP point gives the Laplace approximation of the hyper-posterior (BayesGPR.hyper_laplace).
+ */
+int bgp_lml_hess_batch(bgp_ctx* ctx, int B, const double* h, double* lml, double* grad, double* hess, int* status);
 
 /*
  * Parity helper: the jittered Gram matrix K(h) itself, n*n row-major (both triangles filled).
@@ -712,7 +724,8 @@ int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const d
  *   kernel in front / all but block column 0 in the accumulators of the first panel group's updates; default 1 where the
  *   pipelined Gram kernel would run, see bgp_lml_gen_stats), BGP_GCOV_CHUNK (query points per chunk of bgp_grad_cov, rounded up to
  *   256; default by n and d; read at every call), BGP_HESS_CHUNK (query points per chunk of bgp_hess_cov; default by n and d; read
- *   at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
+ *   at every call), BGP_LMLHESS_CHUNK (upper bound on the matrices per chunk of bgp_lml_hess_batch; default: the scratch budget
+ *   alone; read at every call), BGP_KG_CHUNK / BGP_JES_CHUNK (candidates per chunk of bgp_knowledge_gradient / bgp_joint_entropy, rounded up to 128;
  *   default by n; read at every call), BGP_PDVAR_CHUNK (cells per chunk of bgp_partial_dependence_var, rounded up to 128; default by
  *   n; read at every call), BGP_ITEM_CHUNK / BGP_ROW_CHUNK (upper bounds on the posteriors per chunk of the batched posterior
  *   calls and on the query rows / starts per chunk of bgp_predict_grad_batch, bgp_paths_eval and bgp_paths_minimize; default: the
