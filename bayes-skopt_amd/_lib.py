@@ -143,6 +143,7 @@ SIGNATURES = {
     "bgp_knowledge_gradient": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_joint_entropy": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp]),
     "bgp_cross_validate": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _ip]),
+    "bgp_influence": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip]),
     "bgp_sample_y": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, _dp]),
     "bgp_sample_y_batch": (C.c_int, [_vp, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_double, _dp, _ip]),
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
@@ -1046,6 +1047,30 @@ class Context:
         _check(self._lib.bgp_cross_validate(self._h, B, K, _p(ptr), _p(idx), _p(mean), _p(var), _p(lpd), _p(st)),
                "bgp_cross_validate")
         return mean, var, lpd, st
+
+    # ---- case-deletion influence of every observation (bgp_influence.hip)
+    def influence(self, H_kernel, noise, Xq, n_focus=0):
+        """``bgp_influence``: for the resident posteriors 0 .. B-1 (``H_kernel`` (B, d + 2), white level at -inf) and every
+        observation i, how far the latent posterior moves at the rows of ``Xq`` (m, d) when i is deleted -- hyper-parameters and
+        the y normalisation held fixed, no refit.  ``noise`` (B,): the variance of an observation per posterior.  Returns a dict of
+        (B, n) arrays ``sum_dm2``, ``sum_cook``, ``sum_kl``, ``max_abs``, ``arg_max`` (int32: the first row that attains the
+        maximum), the signed ``dmu_focus`` / ``dvar_focus`` (B, n_focus, n) of the first ``n_focus`` <= 64 rows, and ``status``
+        (B,), non-zero where a value is not finite.  Normalised-target units.  Needs d <= 32 and no context-level warp."""
+        H = self._H(H_kernel)
+        B = H.shape[0]
+        noise = _c(np.asarray(noise, dtype=np.float64).reshape(B))
+        Xq = _c(np.asarray(Xq, dtype=np.float64).reshape(-1, self.d))
+        m, n, nf = Xq.shape[0], self.n, int(n_focus)
+        out = {k: np.empty((B, n)) for k in ("sum_dm2", "sum_cook", "sum_kl", "max_abs")}
+        out["arg_max"] = np.zeros((B, n), dtype=np.int32)
+        out["dmu_focus"], out["dvar_focus"] = np.empty((B, max(nf, 0), n)), np.empty((B, max(nf, 0), n))
+        out["status"] = np.zeros(B, dtype=np.int32)
+        null = C.cast(None, _dp)
+        _check(self._lib.bgp_influence(self._h, B, _p(H), _p(noise), m, _p(Xq) if m else null, nf, _p(out["sum_dm2"]),
+                                       _p(out["sum_cook"]), _p(out["sum_kl"]), _p(out["max_abs"]), _p(out["arg_max"]),
+                                       _p(out["dmu_focus"]) if nf > 0 else null, _p(out["dvar_focus"]) if nf > 0 else null,
+                                       _p(out["status"])), "bgp_influence")
+        return out
 
     # ---- pathwise posterior function draws (bgp_paths_*; DESIGN.md section 14)
     def paths_begin(self, pidx, H_kernel, log_s2, omega, phase, w, eps):

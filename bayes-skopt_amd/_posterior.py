@@ -9,7 +9,7 @@ import sys
 import numpy as np
 from sklearn.base import clone
 
-from . import gradcov, hesscov, lmlhess
+from . import gradcov, hesscov, influence, lmlhess
 from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
 
 _PD_MESSAGE = (
@@ -579,6 +579,26 @@ class CanonicalPosterior:
             parts.append(gp._ctx.cross_validate(len(T), folds))
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
 
+    def influence(self, gp, thetas, X, n_focus):
+        """(normalised (B, ...) arrays of ``bgp_influence``, "device" | "host"): the case-deletion influence of every observation at
+        the rows of ``X``.  ``thetas=None``: the resident median GP; a block of chain rows: the batched
+        build, ``max_batch`` rows at a time, each followed by ONE device call.  An observation's variance is the scalar alpha plus
+        the row's white level, as the knowledge gradient takes it -- which is why the median GP's H is that of the posterior
+        (``_post_theta``, made resident as ``built_H`` makes it) and not ``built_H``'s own answer, the kernel as ``predict`` sees
+        it: under ``noise_set_to_zero`` that one has lost the white level the noise needs; the call gets ``noise_off(H)`` either
+        way.  ``warp_inputs`` or more than 32 dimensions: ``influence.host_rows``, said once."""
+        why = "input warping" if gp.warp_inputs else "more than 32 dimensions" if X.shape[1] > influence.INFL_DMAX else None
+        if why is not None:
+            return influence.host_rows(gp, thetas, X, n_focus, why), "host"
+        base = gp._fantasy_base_alpha()
+        call = lambda H: gp._ctx.influence(noise_off(H), base + np.exp(H[:, -1]), X, n_focus)  # noqa: E731
+        if thetas is None:
+            self.make_resident(gp)
+            return call(gp._canonical(gp._post_theta)), "device"
+        thetas = np.atleast_2d(thetas)
+        step = max(1, int(gp._ctx.max_batch))
+        return influence.concat([call(self.build_rows(gp, thetas[lo : lo + step])) for lo in range(0, len(thetas), step)]), "device"
+
     def pvrs(self, gp, X, T, has_alpha_vec):
         Hk = gp._canonical(gp._kernel_theta_for_predict())
         raise_if_not_pd(gp._ctx.pvrs_prepare(Hk, has_alpha_vec))
@@ -717,6 +737,9 @@ class GramPosterior:
             raise_if_not_pd(self._posterior_gram(gp, gp._gram_stack(T, Xt), want_alpha=False)["status"], gp.kernel_)
             parts.append(gp._ctx.cross_validate(len(T), folds))
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+    def influence(self, gp, thetas, X, n_focus):
+        return influence.host_rows(gp, thetas, X, n_focus, "generic kernel tree"), "host"
 
     def pvrs(self, gp, X, T, has_alpha_vec):
         """PVRS through the bordered-inverse identity of ``bgp_pvrs``,

@@ -945,6 +945,52 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         out.update(lml=lml, log_prior=lp, path=path)
         return out
 
+    def influence(self, X, focus=None, thetas=None, n_samples=0, weights=None, return_path=False, random_state=None):
+        """Which observations is the surrogate resting on?  For every observation i, how far the latent posterior moves at the rows
+        of ``X`` (m, d; transformed space) when i is deleted -- without a refit: a rank-1 term in the resident ``K^-1`` and
+        ``alpha`` (``bgp_influence``).  The hyper-parameters, the warps and the y normalisation stay those
+        fitted on ALL points, as ``cross_validate`` holds them.  ``cross_validate`` says how badly i is predicted by the others AT
+        i; this says how much i moves the surrogate everywhere else.
+
+        ``focus`` (f, d), f <= 64: points of special interest (the expected optimum), put in front of ``X``.  ``thetas=None`` and
+        ``n_samples=0``: the median GP; a (B, p) block of chain rows, or ``n_samples`` rows drawn from ``chain_`` with
+        ``random_state``: every row's answer, their average (``weights`` (B,), default equal) and under ``"band"`` the per-row
+        5 % / 95 % band of every quantity.
+
+        Returns a dict, per observation (n,): ``rms`` = sqrt(mean_x dmu_i(x)^2), ``max_abs`` = max_x |dmu_i(x)| and ``arg_max``,
+        the first row (of [focus; X]) that attains it, in y units; ``cook`` = mean_x dmu_i(x)^2 / v(x) and ``kl`` = mean_x
+        KL(full || deleted) of an observation at x, unitless (v = latent variance + alpha + white level; a row with v <= 0
+        contributes 0).  With focus rows (f, n): ``dmean_focus`` (mean after deletion minus before), ``dstd_focus`` (sd after
+        minus before) in y units, and ``focus_z = dmean_focus / sd(focus)``.  ``status`` is non-zero for a row with a value that
+        is not finite.  Canonical kernels in up to 32 dimensions: ONE device call per ``max_batch`` rows; generic kernel trees,
+        ``warp_inputs=True`` and more dimensions: numpy on the downloaded inverse, said once on stderr.  ``return_path``: the
+        dict carries ``"path"`` either way; also returned as a second value."""
+        from . import influence as _infl
+
+        self._require_posterior("influence")
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        d = self._X_train_.shape[1]
+        F = np.zeros((0, d)) if focus is None else np.asarray(focus, dtype=np.float64).reshape(-1, d)
+        if X.shape[1] != d or len(F) > _infl.INFL_FMAX:
+            raise ValueError(f"the rows must be (m, {d}) and the focus points at most {_infl.INFL_FMAX}, got {X.shape} and {F.shape}")
+        Q = np.ascontiguousarray(np.vstack([F, X]))
+        if self.warp_inputs:
+            validate_zeroone(Q)
+        nf = len(F)
+        if thetas is None and n_samples > 0:
+            rng = check_random_state(random_state)
+            thetas = np.asarray(self.chain_)[rng.randint(0, len(self.chain_), size=int(n_samples))]
+        y_std = self._y_scale()[1]
+        sd = None
+        if nf and thetas is None:
+            with self.noise_set_to_zero():  # (the latent sd, as the chain rows' below: dvar_focus is a latent difference)
+                sd = np.atleast_2d(self.predict(F, return_std=True)[1]) / y_std
+        elif nf:
+            sd = self._predict_hyper_samples(np.atleast_2d(thetas), F, noise_zero=True)[1] / y_std
+        raw, path = self._post.influence(self, None if thetas is None else np.atleast_2d(thetas), Q, nf)
+        out = _infl.assemble(raw, len(Q), nf, y_std, sd, weights, path)
+        return (out, path) if return_path else out
+
     def cross_validate(self, folds=None, n_folds=None, thetas=None, weights="is", random_state=None):
         """Does the surrogate predict the data it has not seen?  For every fold F of training indices, the predictive of the
         held-out OBSERVATIONS ``y_F`` given the remaining points -- without a refit: it follows from the resident ``K^-1`` and

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, hyper_laplace, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, hyper_laplace, influence, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
@@ -347,6 +347,12 @@ class Optimizer:
         without a refit (``utils.cross_validate`` on the current result, same keyword arguments; the optimizer's own random state
         is not consumed)."""
         return cross_validate(self._result(), **kw)
+
+    def influence(self, n_samples=1024, X=None, focus="optimum", n_gp_samples=0, random_state=None):
+        """Which observations is the surrogate resting on?  For every point told so far, how far the predictions over the space --
+        and at the expected optimum -- would move without it, ranked (``utils.influence`` on the current result, same keyword
+        arguments; the optimizer's own random state is not consumed)."""
+        return influence(self._result(), n_samples=n_samples, X=X, focus=focus, n_gp_samples=n_gp_samples, random_state=random_state)
 
     def predict_marginal(self, X, **kw):
         """What the surrogate predicts at points ``X`` of the original space once the kernel hyper-parameters are integrated out:

@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "hyper_laplace", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "influence", "hyper_laplace", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -515,6 +515,40 @@ def cross_validate(res, n_folds=None, n_samples=0, folds=None, weights="is", ran
         chain = np.asarray(reg.chain_)
         thetas = chain[rng.randint(0, len(chain), size=int(n_samples))]
     return reg.cross_validate(folds=folds, n_folds=n_folds, thetas=thetas, weights=weights, random_state=rng)
+
+
+def influence(res, n_samples=1024, X=None, focus="optimum", n_gp_samples=0, random_state=None):
+    """Which observations is the surrogate ``res.models[-1]`` resting on, and how far would the predictions -- and the predicted value
+    at the expected optimum -- move if one of them were wrong: the case-deletion influence of every observation of ``res.x_iters``
+    (``BayesGPR.influence``, ``bgp_influence``; no refit, hyper-parameters held fixed).  Rows: ``X`` (original
+    space), default ``n_samples`` points of ``space.rvs`` drawn with ``random_state``.  ``focus``: "optimum" (the expected optimum,
+    ``expected_optimum(res, random_state=random_state)``), points of the original space, or None.  ``n_gp_samples = 0``: the median
+    GP; more: that many rows of ``chain_``, their average and the per-row band.  Returns ``BayesGPR.influence``'s dict (y units)
+    with ``"ranking"`` (the observations by descending ``cook``), ``"x"`` / ``"y"`` of every observation in the original space and,
+    with focus points, ``"focus"`` (original space)."""
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    rows = space.rvs(n_samples=int(n_samples), random_state=rng) if X is None else [list(x) for x in X]
+    if isinstance(focus, str):
+        if focus != "optimum":
+            raise ValueError(f"focus must be 'optimum', points of the space or None, got {focus!r}")
+        focus = [list(expected_optimum(res, random_state=rng)[0])]
+    elif focus is not None:
+        focus = [list(f) for f in (focus if np.iterable(focus[0]) else [focus])]
+    thetas = None
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+    out = reg.influence(np.asarray(space.transform(rows), dtype=np.float64),
+                        focus=None if focus is None else np.asarray(space.transform(focus), dtype=np.float64), thetas=thetas)
+    out["ranking"] = np.argsort(-out["cook"], kind="stable")
+    out["x"], out["y"] = list(res.x_iters), np.asarray(res.func_vals, dtype=np.float64)
+    if focus is not None:
+        out["focus"] = focus
+    return out
 
 
 def predict_marginal(res, X, **kw):

@@ -666,6 +666,40 @@ int bgp_cross_validate(bgp_ctx* ctx, int B, int n_folds, const int* fold_ptr, co
                        double* fold_lpd, int* status);
 
 /*
+ * Case-deletion influence of every observation (csrc/bgp_influence.hip): how far the latent posterior of each
+ * of the first B resident posteriors moves at the m query rows Xq (m*d, row-major) when observation i is taken out, for all n
+ * observations, without a refit.  h_kernel B*(d + 2) as in bgp_predict_batch (white level at -inf: the latent function); noise (B):
+ * the variance s_b >= 0 of an observation per posterior, as bgp_knowledge_gradient takes it.  With P = K_b^-1 and a = alpha_b as
+ * resident (white level and alpha / noise_vector included), k_*(x) the latent cross kernel and mu, var the latent moments
+ * (bgp_predict_batch's launches and bits), in normalised units:
+ *   c_i(x)    = [k_*(x)^T P]_i
+ *   dmu_i(x)  = mu_{-i}(x) - mu(x)   = -c_i(x) a_i / P_ii
+ *   dvar_i(x) = var_{-i}(x) - var(x) = +c_i(x)^2 / P_ii                                      (>= 0)
+ *   v = var(x) + s_b,  v_i = v + dvar_i(x)
+ *   kl_i(x)   = 1/2 [v / v_i - 1 + log(v_i / v) + dmu_i(x)^2 / v_i]      KL(full || deleted), >= 0; evaluated as
+ *               1/2 [log1p(t) - t / (1 + t) + (dmu_i(x)^2 / v) / (1 + t)],  t = dvar_i(x) / v
+ * The hyper-parameters, the warps and the normalisation of y are held fixed under the deletion, as bgp_cross_validate holds them.
+ * Outputs, each B*n, over the m rows in ascending order:
+ *   sum_dm2 = sum_x dmu_i(x)^2      sum_cook = sum_x dmu_i(x)^2 / v(x)      sum_kl = sum_x kl_i(x)
+ *   max_abs = max_x |dmu_i(x)|      arg_max  = the first row that attains it
+ * A row with v(x) <= 0 contributes exactly 0 to sum_cook and sum_kl.  The first n_focus rows (focus points, e.g. the expected
+ * optimum) are also written out signed: dmu_focus, dvar_focus B*n_focus*n (may be NULL at n_focus = 0).  status (B): non-zero where
+ * one of the three sums or the maximum of that posterior is not finite (the focus entries are not inspected themselves: a dmu that
+ * is not finite makes sum_dm2 so).
+ * V = K_* P runs on the fp64 MFMA ring and is never stored: the epilogue reduces over the query rows inside the accumulators, per
+ * strip of 128 rows, and one thread per (posterior, observation) adds the strips in ascending order.  No floating-point atomics:
+ * every output is the same bits whatever B is, whatever shares the call and however it is chunked (BGP_ITEM_CHUNK, BGP_ROW_CHUNK).
+ * Needs d <= 32, 1 <= m <= 2^24, 1 <= B <= 65535, 0 <= n_focus <= min(m, 64), every noise[b] finite and >= 0 and no context-level
+ * warp: BGP_ERR_INVALID before anything is launched; B resident posteriors that are not per-row warped and no pending batch:
+ * BGP_ERR_STATE.  A refused call changes nothing; a successful one leaves the resident posteriors as they were.
+ *   Replaces: nothing in the reference -- there the route is a refit without the point (bask/bayesgpr.py:200-217, 622-635) per
+ *   observation.
+ */
+int bgp_influence(bgp_ctx* ctx, int B, const double* h_kernel, const double* noise, int m, const double* Xq, int n_focus,
+                  double* sum_dm2, double* sum_cook, double* sum_kl, double* max_abs, int* arg_max, double* dmu_focus,
+                  double* dvar_focus, int* status);
+
+/*
  * Draw f ~ N(mean, cov) at m points for resident posterior b using standard normals supplied by
  * the host (z: n_draws*m), via a Cholesky factor of cov (+jitter) instead of numpy's SVD.
  * Replaces: sklearn sample_y (sklearn/_gpr.py:522-526) reached from BayesGPR.sample_y
