@@ -136,6 +136,8 @@ SIGNATURES = {
                                       C.c_int, _dp, _dp, _dp, _ip, _ip, _ip]),
     "bgp_partial_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp]),
     "bgp_partial_dependence_var": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, _ip, _dp, _dp, _dp]),
+    "bgp_profile_dependence": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.c_int, _ip, _dp, C.c_int,
+                                         _ip, C.c_double, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _ip, C.POINTER(C.c_longlong)]),
     "bgp_sobol_indices": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_uint), _dp, _dp, _dp, _dp]),
     "bgp_shapley": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "bgp_grad_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -868,7 +870,7 @@ class Context:
         res, o = [], 0
         for s in shapes:
             sz = int(np.prod(s))
-            res.append(out[:, o:o + sz].reshape((out.shape[0],) + s).copy())
+            res.append(out[:, o:o + sz].reshape((out.shape[0],) + s + out.shape[2:]).copy())  # (trailing axes: per-cell vectors)
             o += sz
         return res
 
@@ -889,6 +891,37 @@ class Context:
                                                     _p(cov) if want_cov else null), "bgp_partial_dependence_var")
         return (self._pd_blocks(mean, shapes) if want_mean else None, self._pd_blocks(var, shapes) if want_var else None,
                 self._pd_blocks(cov, cshapes) if want_cov else None)
+
+    # ---- profile curves and maps of the surrogate mean (bgp_profile.hip)
+    def profile_dependence(self, H_kernel, y_mean, y_std, X0, lo, hi, grids, panels, gtol=1e-5, max_iter=200, per_chain=False):
+        """``bgp_profile_dependence``: per panel and cell the lowest mean of the resident posteriors 0 .. B-1 (``H_kernel`` (B, d +
+        2)) over the box [lo, hi] with the panel's coordinates held at the grid values, searched by one chain per row of ``X0``
+        (S, d) that walks along the panel's last dimension from cell to cell.  ``grids`` and ``panels`` as in
+        ``partial_dependence``.  Returns a dict of per-panel lists shaped like ``partial_dependence``'s arrays -- ``val`` (B, G1[,
+        G2]) in normalised-target units, ``x`` (..., d), ``best_chain``, ``n_converged`` -- and ``evals`` (B,).  ``per_chain``: also
+        ``chain_val``, ``chain_status`` (..., S) and ``chain_x`` (..., S, d).  ``gtol`` is in y units.  Needs d <= 32 and no
+        context-level warp."""
+        H, B, X0, gmax, ng, grid, pan, shapes, total = self._pd_args(H_kernel, X0, grids, panels)
+        S, d, T = X0.shape[0], self.d, max(total, 1)
+        lo = _c(np.broadcast_to(np.asarray(lo, dtype=np.float64), (d,)))
+        hi = _c(np.broadcast_to(np.asarray(hi, dtype=np.float64), (d,)))
+        val, x = np.empty((B, T)), np.empty((B, T, d))
+        best, nconv = np.zeros((B, T), dtype=np.int32), np.zeros((B, T), dtype=np.int32)
+        cv = np.empty((B, T, S)) if per_chain else None
+        cx = np.empty((B, T, S, d)) if per_chain else None
+        cs = np.zeros((B, T, S), dtype=np.int32) if per_chain else None
+        evals = (C.c_longlong * B)()
+        nd, ni = C.cast(None, _dp), C.cast(None, _ip)
+        _check(self._lib.bgp_profile_dependence(self._h, B, _p(H), float(y_mean), float(y_std), S, _p(X0), _p(lo), _p(hi), gmax, _p(ng),
+                                                _p(grid), len(pan), _p(pan), float(gtol), int(max_iter), _p(val), _p(x), _p(best),
+                                                _p(nconv), _p(cv) if per_chain else nd, _p(cx) if per_chain else nd,
+                                                _p(cs) if per_chain else ni, evals), "bgp_profile_dependence")
+        out = {"val": self._pd_blocks(val, shapes), "x": self._pd_blocks(x, shapes), "best_chain": self._pd_blocks(best, shapes),
+               "n_converged": self._pd_blocks(nconv, shapes), "evals": np.array(list(evals), dtype=np.int64)}
+        if per_chain:
+            out.update(chain_val=self._pd_blocks(cv, shapes), chain_x=self._pd_blocks(cx, shapes),
+                       chain_status=self._pd_blocks(cs, shapes))
+        return out
 
     # ---- Sobol' sensitivity of the surrogate mean (bgp_sobol.hip; DESIGN.md section 21)
     def sobol_indices(self, H_kernel, A, Bm, masks):

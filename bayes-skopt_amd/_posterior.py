@@ -11,6 +11,7 @@ from sklearn.base import clone
 
 from . import gradcov, hesscov, influence, lmlhess
 from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
+from .profile import profile_by_predict
 
 _PD_MESSAGE = (
     "The kernel, %s, is not returning a positive definite matrix. Try gradually increasing the "
@@ -476,6 +477,20 @@ class CanonicalPosterior:
             return gp._ctx.partial_dependence_var(self.built_H(gp, thetas), Xs, grids, panels, want_cov=return_cov), "device"
         return gp._ctx.partial_dependence(self.built_H(gp, thetas), Xs, grids, panels), "device"
 
+    def profile_dependence(self, gp, thetas, X0, lo, hi, grids, panels, gtol=1e-5, max_iter=200, per_chain=False):
+        """(dict of per-panel lists in normalised-target units with a leading posterior axis, "device" | "host"): the profile of
+        the mean -- panel coordinates held, every other coordinate re-optimised in the box.  ``thetas=None``: the resident median GP
+        (B = 1); a block of chain rows: one batched build, then ONE device call over all panels, chains and rows
+        (``bgp_profile_dependence``).  ``warp_inputs`` and more than 32 dimensions take
+        ``profile.profile_by_predict`` (the median GP alone)."""
+        if not self.device_gradients(gp):
+            if thetas is not None:
+                raise ValueError("profile_dependence of hyper-posterior rows needs the device path (no input warping, d <= 32)")
+            why = "input warping" if gp.warp_inputs else "more than 32 dimensions"
+            return profile_by_predict(gp, X0, lo, hi, grids, panels, gtol, max_iter, why), "host"
+        return gp._ctx.profile_dependence(self.built_H(gp, thetas), *gp._y_scale(), X0, lo, hi, grids, panels, gtol=gtol,
+                                          max_iter=max_iter, per_chain=per_chain), "device"
+
     def sensitivity(self, gp, thetas, A, Bm, masks):
         """((f0 (B,), V (B,), closed (B, T), total (B, T)) in normalised-target units, "device" | "host").  ``thetas=None``: the
         resident median GP (B = 1); a block of chain rows: one batched build, then ONE device call over all of them
@@ -707,6 +722,11 @@ class GramPosterior:
         if return_std or return_cov:
             return partial_dependence_var_by_predict(gp, thetas, Xs, grids, panels, return_cov, "generic kernel tree"), "host"
         return partial_dependence_by_predict(gp, thetas, Xs, grids, panels, "generic kernel tree"), "host"
+
+    def profile_dependence(self, gp, thetas, X0, lo, hi, grids, panels, gtol=1e-5, max_iter=200, per_chain=False):
+        if thetas is not None:
+            raise ValueError("profile_dependence of hyper-posterior rows needs a canonical kernel")
+        return profile_by_predict(gp, X0, lo, hi, grids, panels, gtol, max_iter, "generic kernel tree"), "host"
 
     def sensitivity(self, gp, thetas, A, Bm, masks):
         return sensitivity_by_predict(gp, thetas, A, Bm, masks, "generic kernel tree"), "host"

@@ -781,6 +781,49 @@ class BayesGPR(RegressorMixin, BaseEstimator):
             out = [[v[0] for v in part] for part in out]
         return (*out, path) if return_path else tuple(out)
 
+    def profile_dependence(self, grids, panels=None, X0=None, bounds=(0.0, 1.0), thetas=None, return_path=False, gtol=1e-5,
+                           max_iter=200, per_chain=False):
+        """Profile of the predictive mean: per panel and cell the lowest mean over the box with the panel's coordinates held at
+        the grid values and every other coordinate re-optimised -- "how good can it get if this parameter is g" (DESIGN.md section
+        35).  ``grids`` and ``panels`` as in ``partial_dependence`` (transformed space); ``X0`` (S, d): the starts of the S search
+        chains (default: the best observed input); ``bounds``: ``(lo, hi)``, scalars or one value per dimension.  Returns a dict
+        of per-panel lists: ``"val"`` (G1,) / (G1, G2) in y units, ``"x"`` (..., d) the minimisers, ``"best_chain"``,
+        ``"n_converged"`` (chains that met ``gtol``, y units), and with ``per_chain`` ``"chain_val"`` / ``"chain_status"`` (...,
+        S) and ``"chain_x"``; a leading axis of B for a block of B chain rows ``thetas``.  Canonical kernels in up to 32
+        dimensions without ``warp_inputs``: ONE device call (``bgp_profile_dependence``); otherwise scipy's L-BFGS-B on
+        ``predict(return_mean_grad=True)`` in the same order (``profile.profile_values``; the median GP alone), said once on
+        stderr.  ``return_path``: ``(dict, "device" | "host")``."""
+        self._require_posterior()
+        d = self._X_train_.shape[1]
+        grids = [np.asarray(g, dtype=np.float64).reshape(-1) for g in grids]
+        if X0 is None:
+            X0 = self._X_train_[int(np.argmin(np.ravel(self.y_train_)))]
+        X0 = np.atleast_2d(np.asarray(X0, dtype=np.float64))
+        if X0.shape[1] != d or len(grids) != d:
+            raise ValueError(f"starts need {d} columns and one grid per dimension is needed")
+        lo, hi = (np.broadcast_to(np.asarray(v, dtype=np.float64), (d,)) for v in bounds)
+        if panels is None:
+            panels = [(k, -1) for k in range(d)] + [(a, b) for a in range(d) for b in range(a + 1, d)]
+        pan = []
+        for pnl in panels:
+            pnl = tuple(int(v) for v in np.atleast_1d(pnl))
+            pnl = (pnl[0], pnl[1] if len(pnl) > 1 else -1)
+            if not (0 <= pnl[0] < d and -1 <= pnl[1] < d and pnl[0] != pnl[1]):
+                raise ValueError(f"panel {pnl} is not a dimension or a pair of two different dimensions of {d}")
+            if any(np.any(grids[k] < lo[k]) or np.any(grids[k] > hi[k]) for k in pnl if k >= 0):
+                raise ValueError(f"panel {pnl} has grid values outside the bounds")
+            pan.append(pnl)
+        if not pan or np.any(lo > hi) or any(not 1 <= len(g) <= 256 for g in grids):
+            raise ValueError("profile_dependence needs a panel, lo <= hi and 1 .. 256 grid values per dimension")
+        got, path = self._post.profile_dependence(self, thetas, X0, lo, hi, grids, pan, gtol=gtol, max_iter=max_iter,
+                                                  per_chain=per_chain)
+        y_mean, y_std = self._y_scale()
+        out = {k: ([y_std * v + y_mean for v in vs] if k in ("val", "chain_val") else vs) for k, vs in got.items()
+               if per_chain or not k.startswith("chain_")}
+        if thetas is None:
+            out = {k: ([v[0] for v in vs] if isinstance(vs, list) else vs) for k, vs in out.items()}
+        return (out, path) if return_path else out
+
     def sensitivity(self, A, Bm, terms=None, thetas=None, return_path=False):
         """Variance-based (Sobol') sensitivity of the predictive mean by the pick-freeze design: ``A``, ``Bm`` are two independent
         sample matrices (N, d; transformed space), ``terms`` a list of dimensions or tuples of dimensions (default: every single

@@ -17,7 +17,7 @@ from .acquisition import evaluate_acquisitions
 from .bayesgpr import BayesGPR
 from .init import r2_sequence, sb_sequence
 from .space import create_result, is_2Dlistlike, is_listlike, normalize_dimensions
-from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, hyper_laplace, influence, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, sensitivity_indices, shapley_values
+from .utils import active_subspace, construct_default_kernel, cross_validate, expected_minimum, expected_optimum, hdi, hyper_information, hyper_laplace, influence, inverse_unrounded, optimum_curvature, partial_dependence, predict_marginal, profile_dependence, sensitivity_indices, shapley_values
 
 __all__ = ["Optimizer"]
 
@@ -310,6 +310,11 @@ class Optimizer:
         """What the surrogate looks like right now: 1-D curves and 2-D maps of its partial dependence
         (``utils.partial_dependence`` on the current result, same keyword arguments)."""
         return partial_dependence(self._result(), **kw)
+
+    def profile_dependence(self, **kw):
+        """How good can it get if a parameter is held: 1-D curves and 2-D maps of the surrogate mean with every other parameter
+        re-optimised (``utils.profile_dependence`` on the current result, same keyword arguments)."""
+        return profile_dependence(self._result(), **kw)
 
     def active_subspace(self, **kw):
         """Which directions matter: the eigen-decomposition of the active-subspace matrix of the current surrogate

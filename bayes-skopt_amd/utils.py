@@ -10,7 +10,7 @@ from .init import r2_sequence  # noqa: F401  (re-exported like bask/utils.py:8-9
 from .kernels import ConstantKernel, Matern
 from .priors import halfnorm_logpdf_logspace, make_roundflat
 
-__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "influence", "hyper_laplace", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
+__all__ = ["expected_minimum", "expected_optimum", "partial_dependence", "profile_dependence", "sensitivity_indices", "shapley_values", "active_subspace", "optimum_curvature", "cross_validate", "influence", "hyper_laplace", "hdi", "geometric_median", "guess_priors", "construct_default_kernel", "validate_zeroone", "r2_sequence",
            "get_progress_bar"]
 
 
@@ -317,6 +317,74 @@ def partial_dependence(res, dims=None, pairs="all", n_samples=250, n_points=40, 
     if thetas is not None:
         out["band"] = {k: tuple(np.percentile(v, [5.0, 95.0], axis=0)) for k, v in zip(dims, vals)}
         vals = [v.mean(axis=0) for v in vals]
+    for k, v in zip(dims, vals):
+        out["dims"][k] = (both[k][0], v)
+    for (a, b), v in zip(pairs, vals[len(dims):]):
+        out["pairs"][(a, b)] = (both[a][0], both[b][0], v)
+    return out
+
+
+def profile_dependence(res, dims=None, pairs="all", n_points=40, n_starts=4, n_gp_samples=0, return_std=False, random_state=None):
+    """Profile curves and maps of the surrogate mean: for every grid value of a dimension (or a pair) the best the mean of
+    ``res.models[-1]`` can be when that parameter is held and every other one is re-tuned inside the space.
+    Unlike the partial dependence a narrow valley is not averaged away, and the minimum of a curve IS the expected optimum.
+    ``dims``, ``pairs``, ``n_points`` as in ``partial_dependence`` (grids from ``_pd_grid``; integer dimensions are swept over their
+    integers and relaxed where they are free); a space with categorical dimensions is a ValueError, as in ``expected_optimum``.
+    Every cell is searched by ``n_starts`` chains that walk along the grid from cell to cell: they start at ``res.x`` and at the
+    ``n_starts - 1`` distinct observed points of lowest y (deterministic; ``space.rvs`` with ``random_state`` only where there are
+    fewer observations).  Returns a dict: ``"dims"`` {k: (grid, values)}, ``"pairs"`` {(k1, k2): (grid1, grid2, values[G1,
+    G2])}, values in y units; ``"argmin"`` with the same keys, the minimisers in the original space, un-rounded (..., d);
+    ``"converged"`` with the same keys, the share of chains that met the tolerance; ``"path"``: "device" when everything came
+    from ONE device call (``bgp_profile_dependence``), "host" for the scipy loop (input warping, generic kernel trees, more than
+    32 dimensions).  ``n_gp_samples > 0``: the mean over that many rows drawn from ``chain_`` with ``random_state`` and ``"band"``
+    {key: (5 %, 95 %)}, from a second device call over the drawn rows; ``"argmin"`` and ``"converged"`` stay those of the median
+    GP, which ``res.models[-1]`` predicts with.  The drawn rows need the device path: on the host path (``"path" ==
+    "host"``) ``n_gp_samples > 0`` is a ValueError.  ``return_std``: also ``"std"`` with the same keys, the predictive std of the
+    median GP at every argmin, from one batched ``predict``."""
+    from sklearn.utils import check_random_state
+
+    space = res.space
+    if space.is_partly_categorical:
+        raise ValueError("profile_dependence does not support any categorical values")
+    reg = res.models[-1]
+    rng = check_random_state(random_state)
+    d = space.n_dims
+    dims = list(range(d)) if dims is None else [int(k) for k in dims]
+    if pairs == "all":
+        pairs = [(a, b) for i, a in enumerate(dims) for b in dims[i + 1:]]
+    pairs = [] if pairs is None else [(int(a), int(b)) for a, b in pairs]
+    keys = dims + pairs
+    panels = [(k, -1) for k in dims] + pairs
+    both = [_pd_grid(dim, n_points) for dim in space.dimensions]
+    starts, seen = [list(res.x)], {tuple(res.x)}
+    for i in np.argsort(np.asarray(res.func_vals), kind="stable"):
+        if len(starts) >= n_starts:
+            break
+        if tuple(res.x_iters[i]) not in seen:
+            seen.add(tuple(res.x_iters[i]))
+            starts.append(list(res.x_iters[i]))
+    if len(starts) < n_starts:
+        starts.extend(space.rvs(n_starts - len(starts), random_state=rng))
+    X0 = space.transform(starts)
+    grids = [g[1] for g in both]
+    got, path = reg.profile_dependence(grids, panels, X0=X0, return_path=True)
+    vals = got["val"]
+    out = {"dims": {}, "pairs": {}, "path": path,
+           "argmin": {k: np.apply_along_axis(lambda xt: np.array(inverse_unrounded(space, xt)), -1, x) for k, x in zip(keys, got["x"])},
+           "converged": {k: nc / float(len(starts)) for k, nc in zip(keys, got["n_converged"])}}
+    if n_gp_samples > 0:
+        chain = np.asarray(reg.chain_)
+        thetas = chain[rng.randint(0, len(chain), size=int(n_gp_samples))]
+        rows = reg.profile_dependence(grids, panels, X0=X0, thetas=thetas)["val"]
+        out["band"] = {k: tuple(np.percentile(v, [5.0, 95.0], axis=0)) for k, v in zip(keys, rows)}
+        vals = [v.mean(axis=0) for v in rows]
+    if return_std:
+        pts = np.concatenate([x.reshape(-1, d) for x in got["x"]])
+        sd = np.asarray(reg.predict(pts, return_std=True)[1], dtype=np.float64)
+        out["std"], o = {}, 0
+        for k, v in zip(keys, got["val"]):
+            out["std"][k] = sd[o:o + v.size].reshape(v.shape)
+            o += v.size
     for k, v in zip(dims, vals):
         out["dims"][k] = (both[k][0], v)
     for (a, b), v in zip(pairs, vals[len(dims):]):

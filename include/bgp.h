@@ -120,7 +120,7 @@ int bgp_lml_batch(bgp_ctx* ctx, int B, const double* h, double* lml, int* status
  *   the kernel): every entry point that would combine resident posteriors
  *   with the context's shared (warped or un-warped) training inputs -- bgp_predict_batch, bgp_acq_batch, bgp_sample_y,
  *   bgp_sample_y_batch, bgp_pvrs, bgp_fantasy_begin, bgp_predict_grad_batch, bgp_minimize_starts, bgp_paths_begin,
- *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_hess_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
+ *   bgp_partial_dependence, bgp_partial_dependence_var, bgp_profile_dependence, bgp_sobol_indices, bgp_shapley, bgp_grad_cov, bgp_hess_cov, bgp_knowledge_gradient, bgp_joint_entropy, bgp_predict_mixture -- returns BGP_ERR_STATE and launches nothing.  Any posterior build (bgp_posterior_batch*,
  *   bgp_pvrs_prepare, bgp_lml_grad_batch, bgp_lml_hess_batch), bgp_ctx_set_warp and bgp_ctx_update_data end that state.
  */
 int bgp_lml_batch_warped(bgp_ctx* ctx, int B, const double* h, const double* warp, double* lml, int* status);
@@ -396,7 +396,7 @@ int bgp_minimize_starts(bgp_ctx* ctx, int b, const double* h_kernel, double y_me
  * bgp_paths_stats: out[0] = begins, out[1] = evals run on this context.
  * bgp_chunk_stats: how the context's last call to an entry point that cuts its work by a scratch budget ran -- bgp_predict_batch /
  *   _warped / _gram, bgp_acq_batch, bgp_predict_mixture, bgp_sample_y_batch, bgp_knowledge_gradient, bgp_joint_entropy, bgp_grad_cov,
- *   bgp_hess_cov, bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize: out[0] = chunks of posteriors, out[1] = chunks of query rows,
+ *   bgp_hess_cov, bgp_predict_grad_batch, bgp_paths_eval, bgp_paths_minimize, bgp_profile_dependence (chunks of lines): out[0] = chunks of posteriors, out[1] = chunks of query rows,
  *   candidates or starts (per chunk of posteriors); a loop the entry point does not have counts as one chunk.  Host counters only.
  *   BGP_ITEM_CHUNK / BGP_ROW_CHUNK (below) force several chunks at small shapes (tests/test_gpu_chunk_loops.py).
  * bgp_paths_minimize: minimise every open path over the box [lo, hi] (d doubles each) from its OWN S starts,
@@ -493,6 +493,38 @@ int bgp_partial_dependence(bgp_ctx* ctx, int B, const double* h_kernel, int S, c
  */
 int bgp_partial_dependence_var(bgp_ctx* ctx, int B, const double* h_kernel, int S, const double* Xs, int gmax, const int* ng,
                                const double* grid, int P, const int* panels, double* mean, double* var, double* cov);
+
+/*
+ * Profile curves and maps of the surrogate mean (csrc/bgp_profile.hip): the best the mean can be with one or
+ * two coordinates held at a grid value and every other coordinate re-optimised inside the box [lo, hi] (d doubles each), for the
+ * resident posteriors 0 .. B-1 (h_kernel B*(d + 2) as in bgp_predict_batch; the white level is not read).  Normalised-y units, as
+ * bgp_minimize_starts returns them:
+ *   prof_b(D, g) = min over x in [lo, hi] with x_D = g of mean_b(x)        xarg_b(D, g) = the minimiser found
+ * Grids and panels are exactly those of bgp_partial_dependence (gmax*d grid, ng[k], panels (k1, -1) or (k1, k2), k1's index slow,
+ * a panel's block at the sum of the earlier panels' sizes); no warp is applied.  A LINE is the set of cells swept along the last
+ * panel dimension (a 1-D panel: one line; a 2-D panel: ng[k1] lines with x[k1] fixed).  ONE launch per chunk of lines, one workgroup
+ * per (line, chain s, posterior b).  Chain s starts from X0[s] (S*d) clipped into the box, the panel coordinates overwritten; its
+ * anchor is the cell whose grid value is nearest the clipped start's swept coordinate (ties, and a NaN there, go to the lower
+ * index).  The chain minimises at the anchor, walks forward to the last cell, restarts from the anchor's end point and walks back to
+ * cell 0; every cell starts from the previous cell's end point with the swept coordinate set to the cell's grid value and runs the
+ * projected BFGS of bgp_minimize_starts (kappa = 0, gtol in y units, at most max_iter iterations of at most 30 trial points) in the
+ * box with lo = hi = g in the panel dimensions.  The (chain, cell) result is bit for bit what bgp_minimize_starts returns (X_out,
+ * mean_out, status) from that start in that box.  max_iter = 0 is a pure evaluation of every chain's points.
+ * Outputs: val B*total, xarg B*total*d, best_chain and n_converged B*total -- the lowest value over the chains in ascending chain
+ * order (a tie keeps the lower chain; a non-finite value never wins against a finite one; a chain that ended with status 1 or 2
+ * still contributes: its value is the mean at a feasible point), that chain's point, and the chains with status 0.  chain_val,
+ * chain_status (B*total*S, chain fastest) and chain_x (B*total*S*d): every chain's result; each may be NULL.  evals (B): the
+ * evaluations of the mean spent on posterior b.  A cell's results do not depend on the chunking (BGP_ROW_CHUNK bounds the lines
+ * per chunk; counted in bgp_chunk_stats), on which panels, posteriors or chains share the call, nor on the panel's place in the list.
+ * Needs d <= 32 and no context-level warp, 1 <= B, S <= 65535, P >= 1, max_iter >= 0, gtol >= 0, 1 <= ng[k] <= gmax <= 256, panel
+ * indices in [0, d) with k1 != k2, lo <= hi, every grid value of a panel dimension inside [lo, hi], at most 2^24 cells
+ * (BGP_ERR_INVALID before anything is launched) and B resident posteriors that are not per-row warped (BGP_ERR_STATE).
+ *   Replaces: nothing in the reference; today's route is one bgp_minimize_starts call per cell.
+ */
+int bgp_profile_dependence(bgp_ctx* ctx, int B, const double* h_kernel, double y_mean, double y_std, int S, const double* X0,
+                           const double* lo, const double* hi, int gmax, const int* ng, const double* grid, int P,
+                           const int* panels, double gtol, int max_iter, double* val, double* xarg, int* best_chain,
+                           int* n_converged, double* chain_val, double* chain_x, int* chain_status, long long* evals);
 
 /*
  * Variance-based (Sobol') sensitivity of the surrogate mean by the pick-freeze design (csrc/bgp_sobol.hip),
