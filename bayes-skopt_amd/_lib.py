@@ -151,6 +151,11 @@ SIGNATURES = {
     "bgp_lml_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _ip]),
     "bgp_posterior_batch_gram": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "bgp_predict_batch_gram": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # (the kernel program of every _tree call: n_ops, ops, n_imm, imm, P)
+    "bgp_tree_gram": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "bgp_lml_batch_tree": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _ip]),
+    "bgp_posterior_batch_tree": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "bgp_predict_batch_tree": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "bgp_comm_abort": (C.c_int, [_vp]),
     "bgp_mcmc_begin": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp]),
     "bgp_mcmc_begin_ex": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip, _dp, _dp, _dp]),
@@ -588,6 +593,74 @@ class Context:
                                                 _p(mean), _p(var), _p(cov) if cov is not None else nul),
                "bgp_predict_batch_gram")
         return (mean, var, cov) if cov is not None else (mean, var)
+
+    # ---- generic kernel expression trees compiled for the device (kernels.compile_tree; bgp_tree.hip): a program and (B, P)
+    # log-space parameter rows in, the kernel arithmetic and everything behind it on the device
+    def _tree_head(self, program, params):
+        """(B, params, the C arguments ``n_ops, ops, n_imm, imm, P, B, params``) of a ``_tree`` call."""
+        params = _c(np.atleast_2d(params))
+        if params.shape[1] != program.P:
+            raise ValueError(f"parameter rows must have {program.P} entries, got {params.shape[1]}")
+        B = params.shape[0]
+        imm = program.imm if program.imm.size else np.zeros(1)
+        return B, params, (int(program.ops.size), _p(program.ops), int(program.imm.size), _p(imm), int(program.P), B, _p(params))
+
+    def tree_gram(self, program, params, Xq=None):
+        """The kernel matrices themselves: (B, n, n) ``kernel_(X_train)`` (no alpha), or (B, m, n) ``kernel_(Xq, X_train)`` with
+        the query rows seen through the context-level warp."""
+        B, params, head = self._tree_head(program, params)
+        if Xq is None:
+            m, xq, out = 0, C.cast(None, _dp), np.empty((B, self.n, self.n))
+        else:
+            Xq = _c(np.atleast_2d(Xq))
+            if Xq.shape[1] != self.d:
+                raise ValueError(f"query rows must have {self.d} columns, got {Xq.shape[1]}")
+            m, xq, out = Xq.shape[0], _p(Xq), np.empty((B, Xq.shape[0], self.n))
+        _check(self._lib.bgp_tree_gram(self._h, *head, m, xq, _p(out)), "bgp_tree_gram")
+        return out
+
+    def lml_tree(self, program, params, warp=None, use_alpha=True, return_status=False):
+        """``lml_gram`` with the matrices built on the device.  ``warp`` (B, 2d): every row with its own input warp."""
+        B, params, head = self._tree_head(program, params)
+        w = C.cast(None, _dp)
+        if warp is not None:
+            warp = _c(np.atleast_2d(warp))
+            if warp.shape != (B, 2 * self.d):
+                raise ValueError(f"warp rows must be ({B}, {2 * self.d}), got {warp.shape}")
+            w = _p(warp)
+        lml = np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        _check(self._lib.bgp_lml_batch_tree(self._h, *head, w, int(bool(use_alpha)), _p(lml), _p(st)), "bgp_lml_batch_tree")
+        return (lml, st) if return_status else lml
+
+    def posterior_tree(self, program, params, use_alpha=True, want_L=False, want_alpha=True, want_K_inv=False):
+        """``posterior_gram`` with the matrices built on the device; the posteriors stay resident."""
+        B, params, head = self._tree_head(program, params)
+        n, nul = self.n, C.cast(None, _dp)
+        L = np.empty((B, n, n)) if want_L else None
+        a = np.empty((B, n)) if want_alpha else None
+        Ki = np.empty((B, n, n)) if want_K_inv else None
+        lml = np.empty(B)
+        st = np.zeros(B, dtype=np.int32)
+        self._drop_resident()
+        _check(self._lib.bgp_posterior_batch_tree(self._h, *head, int(bool(use_alpha)), _p(L) if want_L else nul,
+                                                  _p(a) if want_alpha else nul, _p(Ki) if want_K_inv else nul, _p(lml), _p(st)),
+               "bgp_posterior_batch_tree")
+        return {"L": L, "alpha": a, "K_inv": Ki, "lml": lml, "status": st}
+
+    def predict_tree(self, program, params, Xq, return_cov=False):
+        """``predict_gram`` for the B resident posteriors with the cross covariances, the prior variances and (``return_cov``)
+        ``kernel_(Xq)`` built on the device from ``params`` as given."""
+        B, params, head = self._tree_head(program, params)
+        Xq = _c(np.atleast_2d(Xq))
+        if Xq.shape[1] != self.d:
+            raise ValueError(f"query rows must have {self.d} columns, got {Xq.shape[1]}")
+        m = Xq.shape[0]
+        mean, var = np.empty((B, m)), np.empty((B, m))
+        cov = np.empty((B, m, m)) if return_cov else None
+        _check(self._lib.bgp_predict_batch_tree(self._h, *head, m, _p(Xq), _p(mean), _p(var),
+                                                _p(cov) if return_cov else C.cast(None, _dp)), "bgp_predict_batch_tree")
+        return (mean, var, cov) if return_cov else (mean, var)
 
     def has_pending(self):
         """A batch handed to ``lml_submit`` has not been collected yet."""

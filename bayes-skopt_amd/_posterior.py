@@ -10,7 +10,7 @@ import numpy as np
 from sklearn.base import clone
 
 from . import gradcov, hesscov, influence, lmlhess
-from .kernels import WhiteKernel, gradient_x, param_for_white_kernel_in_sum
+from .kernels import WhiteKernel, compile_tree, gradient_x, param_for_white_kernel_in_sum
 from .profile import profile_by_predict
 
 _PD_MESSAGE = (
@@ -636,6 +636,18 @@ class GramPosterior:
         self._resident = None if theta is None else np.array(theta, copy=True)
         return res
 
+    def _build(self, gp, thetas, theta=None, **want):
+        """The batched posterior build of the rows ``thetas``: by the kernel program on the device where the estimator has one
+        (``BayesGPR._tree_program``; ``bgp_posterior_batch_tree``), else from host-evaluated matrices.  ``theta``: the row that is
+        the resident posterior afterwards."""
+        prog = gp._tree_program()
+        if prog is None:
+            return self._posterior_gram(gp, gp._gram_stack(thetas), theta, **want)
+        self._resident = None
+        res = gp._ctx.posterior_tree(prog, prog.params(thetas), **want)
+        self._resident = None if theta is None else np.array(theta, copy=True)
+        return res
+
     def lml(self, gp, T, eval_gradient):
         """``sklearn/_gpr.py:579-647``: ``K, K_gradient = kernel(X, eval_gradient=True)`` on the host; factorisation, alpha,
         K^-1 and the LML on the device; the contraction ``1/2 sum_ij (alpha_i alpha_j - K^-1_ij) dK_ij/dtheta_k`` of the
@@ -674,35 +686,43 @@ class GramPosterior:
         return gp._gram_lml(*pending.args)
 
     def posterior(self, gp, theta):
-        res = self._posterior_gram(gp, gp._gram_stack(theta), theta, want_alpha=True)
+        res = self._build(gp, theta, theta, want_alpha=True)
         raise_if_not_pd(res["status"], gp.kernel_)
         return res["alpha"][0]
 
     def factor(self, gp, which):
-        res = self._posterior_gram(gp, gp._gram_stack(gp._post_theta), gp._post_theta, want_L=(which == "L"),
-                                   want_alpha=False, want_K_inv=(which == "K_inv"))
+        res = self._build(gp, gp._post_theta, gp._post_theta, want_L=(which == "L"), want_alpha=False,
+                          want_K_inv=(which == "K_inv"))
         return res[which][0]
 
     def make_resident(self, gp):
         if self._resident is None or not np.array_equal(self._resident, gp._post_theta):
-            self._posterior_gram(gp, gp._gram_stack(gp._post_theta), gp._post_theta, want_alpha=False)
+            self._build(gp, gp._post_theta, gp._post_theta, want_alpha=False)
 
     def predict(self, gp, X, return_cov):
         return self.rows_predict(gp, None, X, noise_zero=False, return_cov=return_cov)
 
     def rows_predict(self, gp, thetas, X, noise_zero, return_cov=False):
         """The kernel object on the host (training matrix, cross covariances, prior variances), the rest on the device.
-        ``thetas=None``: the resident posterior with ``kernel_`` as it is."""
-        Xw = gp.warp(X) if gp.warp_inputs else X  # BayesGPR.predict warps the query points (bask/bayesgpr.py:630-632)
-        Xt = gp.X_train_
+        ``thetas=None``: the resident posterior with ``kernel_`` as it is.  With a kernel program (``BayesGPR._tree_program``) the
+        three kernel matrices are the device's too (``bgp_predict_batch_tree``), which warps the query rows itself."""
+        prog = gp._tree_program()
         if thetas is None:
             self.make_resident(gp)
             kernels = [gp.kernel_]
         else:
             thetas = np.atleast_2d(thetas)
-            res = self._posterior_gram(gp, gp._gram_stack(thetas, Xt), want_alpha=False)
-            raise_if_not_pd(res["status"], gp.kernel_)
-            kernels = [gp._kernel_at(t) for t in thetas]
+            raise_if_not_pd(self._build(gp, thetas, want_alpha=False)["status"], gp.kernel_)
+            kernels = None if prog is not None else [gp._kernel_at(t) for t in thetas]
+        if prog is not None:
+            if thetas is None:
+                thetas = gp._kernel_theta_for_predict()
+                if len(thetas) != prog.n_theta:  # (noise_set_to_zero has put a free WhiteKernel in a fixed one's place)
+                    prog = compile_tree(gp.kernel_, gp._X_train_.shape[1])
+            out = gp._ctx.predict_tree(prog, prog.params(thetas, noise_zero=noise_zero), X, return_cov=return_cov)
+            return out[0], out[1], (out[2] if return_cov else None)
+        Xw = gp.warp(X) if gp.warp_inputs else X  # BayesGPR.predict warps the query points (bask/bayesgpr.py:630-632)
+        Xt = gp.X_train_
         if noise_zero:
             kernels = [_with_white_zeroed(k) for k in kernels]
         Ks = np.stack([k(Xw, Xt) for k in kernels])
@@ -750,11 +770,10 @@ class GramPosterior:
             self.make_resident(gp)
             return gp._ctx.cross_validate(1, folds)
         thetas = np.atleast_2d(thetas)
-        Xt = gp.X_train_
         parts, step = [], max(1, int(gp._ctx.max_batch))
         for lo in range(0, len(thetas), step):
             T = thetas[lo : lo + step]
-            raise_if_not_pd(self._posterior_gram(gp, gp._gram_stack(T, Xt), want_alpha=False)["status"], gp.kernel_)
+            raise_if_not_pd(self._build(gp, T, want_alpha=False)["status"], gp.kernel_)
             parts.append(gp._ctx.cross_validate(len(T), folds))
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
 
@@ -766,7 +785,9 @@ class GramPosterior:
         ``covs_i = sum_t [k_t^T K^-1 k_t + (k(x_t, x_i) - k_i^T K^-1 k_t)^2 / (kappa_i - k_i^T K^-1 k_i)]``, every term read off
         ONE device predictive covariance ``C = K_** - K_* K^-1 K_*^T`` over [Thompson points; candidates] per candidate chunk:
         ``C_ti``, ``C_ii`` and ``k_t^T K^-1 k_t = kappa_t - C_tt``.  K carries alpha only when it is a vector (reference quirk,
-        ``bask/acquisition.py:332-333``); the kernel matrices come from the host-evaluated ``kernel_``."""
+        ``bask/acquisition.py:332-333``).  All of its kernel matrices come from the host-evaluated ``kernel_``, under every
+        ``tree_path``: it reads ``kernel_(Q)`` of the query rows as a matrix, which no device entry returns, and host and device
+        matrices are not mixed in one computation."""
         k = gp.kernel_
         Xt = gp.X_train_
         res = self._posterior_gram(gp, k(Xt)[None], use_alpha=bool(has_alpha_vec), want_alpha=False)

@@ -153,7 +153,7 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         """(Re)create / update the device context for the current training set."""
         X, y = self._X_train_, self.y_train_
         alpha_diag = self._alpha_diag()
-        plan = analyse_kernel(self.kernel_)
+        plan = analyse_kernel(self.kernel_, d=X.shape[1])
         want_batch = int(self.max_batch or batch_hint or getattr(self, "_batch_wish", None) or 64)
         ctx = self._ctx_obj
         if (ctx is None or ctx.d != X.shape[1] or ctx.form != plan.form or ctx.stationary != plan.stationary
@@ -225,9 +225,22 @@ class BayesGPR(RegressorMixin, BaseEstimator):
         X = self.X_train_ if X is None else X
         return np.stack([self._kernel_at(t)(X) for t in np.atleast_2d(Thetas)])
 
+    tree_path = "auto"  # "host": the kernel object on the host even where the tree has a device program (tests compare the two)
+
+    def _tree_program(self):
+        """The kernel program every kernel matrix of a generic tree comes from (``kernels.compile_tree``),
+        or None: the tree has none, or ``tree_path = "host"``."""
+        if self.tree_path not in ("auto", "host"):
+            raise ValueError("tree_path must be 'auto' or 'host', got %r" % (self.tree_path,))
+        return self._plan.program if self._generic and self.tree_path == "auto" else None
+
     def _gram_lml(self, Thetas, Ws=None):
-        """LML of every row (host kernel matrices, device factorisation).  ``Ws``: per-row input warps (B, 2d)."""
+        """LML of every row of a generic tree, device factorisation.  ``Ws``: per-row input warps (B, 2d).  With a kernel program
+        one ``bgp_lml_batch_tree`` call on a (B, P) parameter block; else the kernel object on the host, one matrix per row."""
         Thetas = np.atleast_2d(Thetas)
+        prog = self._tree_program()
+        if prog is not None:
+            return self._ctx.lml_tree(prog, prog.params(Thetas), warp=Ws)
         if Ws is None:
             K = self._gram_stack(Thetas)
         else:  # every walker sees the training inputs through its own Beta-CDF warp (bask/bayesgpr.py:353-365)
@@ -1993,6 +2006,9 @@ def _resident_run(gp, n_walkers, n_dim, priors, warp_priors, comm):
     if not getattr(gp, "resident_sampler", True):
         return None, None  # (asked for: not a fallback)
     if not gp._post.canonical:
+        if gp._tree_program() is not None:
+            return None, ("the kernel tree has no canonical device form: its matrices come from a kernel program on the device, "
+                          "one call per half-step")
         return None, "the kernel tree has no canonical device form: its matrices are evaluated on the host"
     if n_walkers % 2:
         return None, "an odd number of walkers: the two halves of a step differ in size"

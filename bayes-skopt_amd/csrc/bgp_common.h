@@ -195,6 +195,7 @@ struct bgp_ctx {
   BgpDev<char> dscratch;
   int scratch_live = 0;        // pointers carved out of dscratch are in use: a second carve would free them (BgpScratch)
   BgpDev<double> drowpart;     // column-tile partials of the predictive-variance row dots
+  BgpDev<double> dtreep;       // B x P log-space parameter rows of a kernel-program call (bgp_tree.hip), grown on demand
   // asynchronous LML batch (bgp_lml_batch_submit / _wait): pinned result buffers and the pending batch size
   BgpPinned<double> hstage;  // pinned staging of the training set (bgp_ctx_update_data)
   BgpPinned<double> hh;      // pinned copy of the submitted hyper-parameter block
@@ -395,7 +396,7 @@ static inline void bgp_ps_clear_inflight(bgp_ctx* c) {
 int bgp_ps_ensure_flags(bgp_ctx* ctx, int B);
 
 // ONE guard for the entry points that read or replace the resident posteriors (bgp_post.hip, bgp_fantasy.hip, bgp_predgrad.hip,
-// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
+// bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip, bgp_tree.hip).  An entry point calls it FIRST, with its name and the kind of posteriors it reads; one
 // that counts them calls it again with the count where its "not resident" answer stands today, behind its argument and capability
 // checks (BGP_ERR_INVALID goes before BGP_ERR_STATE there).  Always: the context is there and no submitted batch is pending -- the
 // workspace belongs to a batch submitted with bgp_lml_batch_submit until bgp_lml_batch_wait has collected it; that much is every
@@ -438,7 +439,7 @@ static inline int bgp_guard(const bgp_ctx* c, const char* who, BgpPostKind kind 
 }
 
 // ONE exit path for every entry point that touches the device with scratch (bgp_post.hip, bgp_paths.hip, bgp_paths_select.hip, bgp_pdep.hip, bgp_pdvar.hip, bgp_cv.hip, bgp_sobol.hip, bgp_shapley.hip, bgp_gcov.hip, bgp_cond.hip, bgp_kg.hip, bgp_jes.hip,
-// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
+// bgp_predgrad.hip, bgp_fantasy.hip, bgp_warp.hip, bgp_mix.hip, bgp_info.hip, bgp_hess.hip, bgp_lmlhess.hip, bgp_tree.hip; their stages return from the middle, with BGP_HIP or a plain return): the body
 // runs on the context's device, and a failed call waits for what it enqueued -- its kernels run over scratch that the next call may
 // carve again --, clears the sticky HIP error, and none of its downloads is unpacked into the caller's arrays later.  The success
 // path is the body's own.
@@ -487,11 +488,20 @@ int bgp_grow_workspace(bgp_ctx* ctx, size_t doubles);
 // stays resident beside K^-1 (the draws read it; the LML gradient does not)
 // warp != nullptr (B x 2d, host): item b is built from c->dX through its own warp instead of c->dXeff; the warped inputs and the
 // warp parameters of all B items stay resident in c->dXwP / c->dwarpP (bgp_posterior_batch_warped)
+// tree != nullptr: the B kernel matrices are built on the device by a kernel program (bgp_tree.hip) from the parameter rows
+// tree->params (host, B x P); h and Kgram are not read
+struct BgpTreeProg;
+struct BgpTreeCall {
+  const BgpTreeProg* prog;
+  const double* params;
+};
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
                         double* lml, int* status, const double* Kgram = nullptr, bool want_Linv = true,
-                        const double* warp = nullptr);
+                        const double* warp = nullptr, const BgpTreeCall* tree = nullptr);
 // host kernel matrices -> working matrices (bgp_gram.hip)
 int bgp_gram_load(bgp_ctx* c, int nb, const double* K, int augmented, int use_alpha);
+// ... what follows the matrices' arrival there: identity padding, the alpha_diag add, the right-hand side
+int bgp_gram_fixup(bgp_ctx* c, int nb, int augmented, int use_alpha);
 
 // ---- kernels launched across translation units ----
 // K-build: lower-triangular tiles of the jittered Gram matrix of walker b into dK[b] (npad x npad).

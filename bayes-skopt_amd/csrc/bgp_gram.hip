@@ -3,8 +3,9 @@
 // builds priors by recursion over arbitrary Sum / Product trees) -- and the device does everything that follows: diagonal
 // add, factorisation, solves, log-likelihood, inverse, predictive products.  Used by bayes-skopt_amd/bayesgpr.py for the trees
 // kernels.py cannot map to the canonical device form (two stationary terms, products of stationaries, general Matern nu,
-// RationalQuadratic, ExpSineSquared, DotProduct, ...).  No kernel arithmetic of such a tree exists on the device, and none of
-// the factorisation exists on the host: there is still no CPU fallback.
+// RationalQuadratic, ExpSineSquared, DotProduct, ...).  The entry points of this file take the matrices from the host; where
+// kernels.compile_tree covers the tree, bgp_tree.hip evaluates it on the device instead (bgp_*_tree).  None of the factorisation
+// exists on the host: there is still no CPU fallback.
 #include "bgp_common.h"
 
 // Rows of the working matrix that the upload did not write, the diagonal term and the working right-hand side:
@@ -35,6 +36,12 @@ int bgp_gram_load(bgp_ctx* c, int nb, const double* K, int augmented, int use_al
   for (int b = 0; b < nb; b++)
     BGP_HIP(bgp_memcpy2d_async(c->dK + (size_t)b * ld * ld, ld * sizeof(double), K + (size_t)b * n * n, (size_t)n * sizeof(double),
                                (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, c->stream));
+  return bgp_gram_fixup(c, nb, augmented, use_alpha);
+}
+
+int bgp_gram_fixup(bgp_ctx* c, int nb, int augmented, int use_alpha) {
+  const int n = c->n, npad = c->npad;
+  const size_t ld = augmented ? 2 * (size_t)npad : (size_t)npad;
   hipLaunchKernelGGL(gram_fixup_kernel, dim3(std::max(1, std::min(64, npad / 64)), nb), dim3(256), 0, c->stream, c->dK, c->dalpha,
                      c->dy, c->dyw, n, npad, (int)ld, ld * ld, use_alpha);
   BGP_HIP(hipGetLastError());

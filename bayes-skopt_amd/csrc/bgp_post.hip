@@ -16,6 +16,7 @@
 #include "bgp_common.h"
 #include "bgp_device.h"
 #include "bgp_gemm.h"
+#include "bgp_tree.h"
 
 // ------------------------------------------------------------------------------------------
 // small helpers
@@ -187,13 +188,20 @@ static int ensure_resident(bgp_ctx* c, int B, bool want_Linv, bool rowwarp) {
 }
 
 int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv,
-                        double* lml, int* status, const double* Kgram, bool want_Linv, const double* warp) {
+                        double* lml, int* status, const double* Kgram, bool want_Linv, const double* warp,
+                        const BgpTreeCall* tree) {
   const int npad = c->npad, n = c->n;
   const size_t p = c->d + 2, nd = (size_t)n * c->d, w2 = 2 * (size_t)c->d;
   const size_t ld = 2 * (size_t)npad;
   c->post.drop();  // (whatever was resident is gone before the buffers are touched; commit() below when the build is through)
   int rc = ensure_resident(c, B, want_Linv, warp != nullptr);
   if (rc) return rc;
+  if (tree) {  // the parameter rows of all B items, once
+    const size_t P = tree->prog->P;
+    rc = c->dtreep.ensure((size_t)B * P);
+    if (rc) return rc;
+    BGP_HIP(bgp_memcpy_async(c->dtreep, tree->params, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
   if (warp) {
     // every item's own Beta-CDF warp of the un-warped training inputs, all B in one launch; they stay resident for the predict
     BGP_HIP(bgp_memcpy_async(c->dwarpP, warp, (size_t)B * w2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -210,7 +218,7 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
   chunk = std::min(chunk, c->max_batch);
   for (int off = 0; off < B; off += chunk) {
     const int nb = std::min(chunk, B - off);
-    if (!Kgram)
+    if (!Kgram && !tree)
       BGP_HIP(bgp_memcpy_async(c->dh, h + (size_t)off * p, nb * p * sizeof(double), hipMemcpyHostToDevice, c->stream));
     BGP_HIP(hipMemsetAsync(c->dstatus, 0, nb * sizeof(int), c->stream));
     // zero the bottom halves ([I | 0] rows), then K into the top-left, identity, rhs
@@ -218,9 +226,15 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
       BGP_HIP(hipMemsetAsync(c->dK + (size_t)b * ld * ld + (size_t)npad * ld, 0, (size_t)npad * ld * sizeof(double),
                              c->stream));
     // (no kernel of the augmented factorisation reads c->dXeff: bgp_launch_cholesky generates nothing there)
-    rc = Kgram  ? bgp_gram_load(c, nb, Kgram + (size_t)off * n * n, 1, use_alpha)
-         : warp ? bgp_launch_kbuild_x(c, 0, nb, c->stream, 0, 1, use_alpha, c->dXwP + (size_t)off * nd, nd)
-                : bgp_launch_kbuild(c, nb, 0, 1, use_alpha);
+    if (tree) {  // the kernel program fills the top-left n x n of every augmented matrix (bgp_tree.hip)
+      rc = bgp_launch_tree(c->stream, *tree->prog, nb, c->dtreep + (size_t)off * tree->prog->P, c->d, c->dXeff, 0, n, c->dXeff, 0, n, 1,
+                           c->dK, (int)ld, ld * ld, n, n);
+      if (!rc) rc = bgp_gram_fixup(c, nb, 1, use_alpha);
+    } else {
+      rc = Kgram  ? bgp_gram_load(c, nb, Kgram + (size_t)off * n * n, 1, use_alpha)
+           : warp ? bgp_launch_kbuild_x(c, 0, nb, c->stream, 0, 1, use_alpha, c->dXwP + (size_t)off * nd, nd)
+                  : bgp_launch_kbuild(c, nb, 0, 1, use_alpha);
+    }
     if (rc) return rc;
     hipLaunchKernelGGL(aug_init_kernel, dim3((npad + 255) / 256, nb), dim3(256), 0, c->stream, c->dK, c->dyw, npad, nb);
     rc = bgp_launch_cholesky(c, nb, 1);
@@ -260,8 +274,8 @@ int bgp_posterior_build(bgp_ctx* c, int B, const double* h, int use_alpha, doubl
 
 // ... as an entry point runs it
 static int post_build(bgp_ctx* c, int B, const double* h, int use_alpha, double* L, double* alpha, double* K_inv, double* lml,
-                      int* status, const double* Kgram = nullptr, const double* warp = nullptr) {
-  return post_call(c, [&] { return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram, true, warp); });
+                      int* status, const double* Kgram = nullptr, const double* warp = nullptr, const BgpTreeCall* tree = nullptr) {
+  return post_call(c, [&] { return bgp_posterior_build(c, B, h, use_alpha, L, alpha, K_inv, lml, status, Kgram, true, warp, tree); });
 }
 
 extern "C" int bgp_posterior_batch(bgp_ctx* c, int B, const double* h, double* L, double* alpha, double* K_inv,
@@ -298,6 +312,22 @@ extern "C" int bgp_posterior_batch_gram(bgp_ctx* c, int B, const double* K, int 
     return BGP_ERR_INVALID;
   }
   return post_build(c, B, nullptr, use_alpha, L, alpha, K_inv, lml, status, K);
+}
+
+// ... and with the matrices built on the device by a kernel program (bgp_tree.hip): B rows of P log-space parameters in, the same
+// outputs, the same resident posteriors.
+extern "C" int bgp_posterior_batch_tree(bgp_ctx* c, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B,
+                                        const double* params, int use_alpha, double* L, double* alpha, double* K_inv, double* lml,
+                                        int* status) {
+  BGP_TRY(bgp_guard(c, "bgp_posterior_batch_tree"));
+  if (!params || B <= 0) {
+    bgp_set_error("bgp_posterior_batch_tree: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  BgpTreeProg pg;
+  BGP_TRY(bgp_tree_check("bgp_posterior_batch_tree", c->d, n_ops, ops, n_imm, imm, P, &pg));
+  const BgpTreeCall tree{&pg, params};
+  return post_build(c, B, nullptr, use_alpha, L, alpha, K_inv, lml, status, nullptr, nullptr, &tree);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -349,6 +379,8 @@ struct PostKss {
   const double *dH = nullptr, *dXq = nullptr;  // generated for the device hyper-vectors dH (nb x (d + 2)); white level: exp on the device,
   const double* hk = nullptr;                  // ... or, for ONE item, std::exp of this host copy (bgp_sample_y: not the same bits)
   const double* host = nullptr;                // uploaded: nb host matrices of m x m with their diagonal, zero padded here
+  const BgpTreeProg* prog = nullptr;           // generated by a kernel program in self mode on dXq (its WhiteKernel counts on the
+  const double* dparams = nullptr;             // ... diagonal) from the nb device parameter rows dparams; zero padded here
 };
 // The predictive covariance of nb items: P = K_* K^-1 (item b's K^-1 is Kinv[pidxB ? pidxB[b] : b]), K_** into dC, then
 // dC -= P K_*^T -- or, with ``factor``, Kinv holds L^-1 instead: P = K_* L^-T, dC -= P P^T.  The product with the explicit
@@ -365,6 +397,9 @@ static int post_cov(bgp_ctx* c, int nb, int m, const double* dKs, const double* 
   if (kss.host) {
     BGP_HIP(hipMemsetAsync(dC, 0, (size_t)nb * sC * sizeof(double), c->stream));
     for (int b = 0; b < nb; b++) BGP_HIP(rows_up(c, dC + (size_t)b * sC, kss.host + (size_t)b * m * m, m, mpad, m));
+  } else if (kss.prog) {
+    BGP_HIP(hipMemsetAsync(dC, 0, (size_t)nb * sC * sizeof(double), c->stream));
+    BGP_TRY(bgp_launch_tree(c->stream, *kss.prog, nb, kss.dparams, d, kss.dXq, 0, m, kss.dXq, 0, m, 1, dC, mpad, sC, m, m));
   } else {
     BGP_TRY(bgp_launch_kcross_batch(c, nb, kss.dH, m, kss.dXq, m, kss.dXq, dC, mpad, sC));
     if (kss.hk)
@@ -532,6 +567,67 @@ extern "C" int bgp_predict_batch_gram(bgp_ctx* c, int B, int m, const double* Ks
       BGP_HIP(hipGetLastError());
       BGP_HIP(rows_down(c, var + (size_t)off * m, dq, m, mpad, nb));
       BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the staged host slices' arena and the scratch)
+    }
+    return BGP_OK;
+  });
+}
+
+// bgp_predict_batch_gram with K_* = kernel_(Xq, X_train), kernel_.diag(Xq) and (cov != NULL only) kernel_(Xq) built on the device
+// by a kernel program from B rows of P log-space parameters, used as given (the caller zeroes the white level for the latent
+// function).  The query rows go through the context-level warp as bgp_predict_batch sends them; the products are the same kernels.
+extern "C" int bgp_predict_batch_tree(bgp_ctx* c, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B,
+                                      const double* params, int m, const double* Xq, double* mean, double* var, double* cov) {
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_tree"));
+  if (!params || !Xq || !mean || !var || m <= 0 || B <= 0) {
+    bgp_set_error("bgp_predict_batch_tree: bad argument");
+    return BGP_ERR_INVALID;
+  }
+  BgpTreeProg pg;
+  BGP_TRY(bgp_tree_check("bgp_predict_batch_tree", c->d, n_ops, ops, n_imm, imm, P, &pg));
+  BGP_TRY(bgp_guard(c, "bgp_predict_batch_tree", BGP_POST_ANY, B));
+  return post_call(c, [&]() -> int {
+    const int npad = c->npad, n = c->n, d = c->d, mpad = pad128(m);
+    const size_t sKs = (size_t)mpad * npad, sCv = (size_t)mpad * mpad;
+    const int chunk = post_chunk(B, sKs + 3 * (size_t)mpad + (cov ? sKs + sCv : 0), (size_t)1 << 29, true);
+    double *dXq, *dPar, *dKs, *dq, *dout, *dkss, *dP = nullptr, *dCov = nullptr;
+    BgpScratch live(c);
+    BGP_TRY(live.carve([&](BgpCarve& s) {
+      dXq = s.take<double>((size_t)m * d);
+      dPar = s.take<double>((size_t)B * P);
+      dKs = s.take<double>((size_t)chunk * sKs);
+      dq = s.take<double>((size_t)chunk * mpad);
+      dout = s.take<double>((size_t)chunk * mpad);
+      dkss = s.take<double>((size_t)chunk * mpad);
+      if (cov) {
+        dP = s.take<double>((size_t)chunk * sKs);
+        dCov = s.take<double>((size_t)chunk * sCv);
+      }
+    }));
+    BGP_TRY(post_stage_queries(c, dXq, Xq, m));
+    BGP_HIP(bgp_memcpy_async(dPar, params, (size_t)B * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->chunk_last[0] = 0, c->chunk_last[1] = 1;
+    for (int off = 0; off < B; off += chunk) {
+      const int nb = std::min(chunk, B - off);
+      c->chunk_last[0]++;
+      const double* Kinv = c->dKinv + (size_t)off * npad * npad;
+      const double* al = c->dalpha_sol + (size_t)off * npad;
+      const double* par = dPar + (size_t)off * P;
+      // K_* with its zero padding (rows m .. mpad, columns n .. npad), and the prior variances
+      BGP_TRY(bgp_launch_tree(c->stream, pg, nb, par, d, dXq, 0, m, c->dXeff, 0, n, 0, dKs, npad, sKs, mpad, npad));
+      BGP_TRY(bgp_launch_tree_diag(c->stream, pg, nb, par, d, dXq, 0, m, dkss, (size_t)mpad));
+      hipLaunchKernelGGL(matvec_rows_kernel, dim3((m + 3) / 4, nb), dim3(256), 0, c->stream, dKs, npad, sKs, al, (size_t)npad,
+                         (const int*)nullptr, npad, m, dout, (size_t)mpad);
+      BGP_HIP(rows_down(c, mean + (size_t)off * m, dout, m, mpad, nb));
+      BGP_TRY(launch_rowquad(c, dKs, npad, sKs, Kinv, npad, (size_t)npad * npad, nullptr, mpad, npad, nb, dq));
+      if (cov) {
+        PostKss src;
+        src.dXq = dXq, src.prog = &pg, src.dparams = par;
+        BGP_TRY(post_cov(c, nb, m, dKs, Kinv, nullptr, dP, src, 2, dCov, cov + (size_t)off * m * m));
+      }
+      hipLaunchKernelGGL(finish_var_gram_kernel, dim3((m + 255) / 256, nb), dim3(256), 0, c->stream, dq, dkss, (size_t)mpad, m, dq);
+      BGP_HIP(hipGetLastError());
+      BGP_HIP(rows_down(c, var + (size_t)off * m, dq, m, mpad, nb));
+      BGP_HIP(bgp_stream_sync(c->stream));  // (the next chunk reuses the scratch)
     }
     return BGP_OK;
   });

@@ -19,7 +19,9 @@ RationalQuadratic, ExpSineSquared, DotProduct, ... -- the reference accepts any 
 gets a ``GramPlan``: the host evaluates ``kernel_(X)`` with the kernel object, exactly as the reference does
 (``sklearn/_gpr.py:582``), and the device does the factorisation, the solves, the log-likelihood, the inverse and
 the predictive products (``bgp_lml_batch_gram`` / ``bgp_posterior_batch_gram`` / ``bgp_predict_batch_gram``).
-There is still no CPU path for the factorisation.
+There is still no CPU path for the factorisation.  Where ``compile_tree`` covers such a tree (everything but Matern with a
+general nu and trees beyond the program's limits), the kernel arithmetic runs on the device too: the ``GramPlan`` carries a
+``TreeProgram`` and the ``bgp_*_tree`` entry points take a ``(B, P)`` block of log-space parameters (``csrc/bgp_tree.hip``).
 """
 import numpy as np
 from sklearn.gaussian_process.kernels import (  # noqa: F401  (re-exported: the bask kernel vocabulary)
@@ -33,7 +35,7 @@ from sklearn.gaussian_process.kernels import (  # noqa: F401  (re-exported: the 
 )
 
 __all__ = ["RBF", "ConstantKernel", "Matern", "WhiteKernel", "Sum", "Product", "KernelPlan", "GramPlan", "analyse_kernel",
-           "param_for_white_kernel_in_sum", "gradient_x"]
+           "param_for_white_kernel_in_sum", "gradient_x", "compile_tree"]
 
 
 def gradient_x(kernel, x, X_train):
@@ -133,17 +135,140 @@ def _stationary_name(k):
     return None
 
 
+TREE_STACK, TREE_MAXMET, TREE_MAXINS, TREE_MAXIMM, TREE_MAXP, TREE_MAXD = 8, 4, 32, 8, 256, 32  # csrc/bgp_tree.h
+TM_ISO, TM_ARD, TM_EUCL, TM_DOT = range(4)
+(TO_CONST, TO_WHITE, TO_RBF, TO_M12, TO_M32, TO_M52, TO_RQ, TO_ESS, TO_DOT, TO_ADD, TO_MUL, TO_POW) = range(12)
+
+
+class TreeProgram:
+    """A kernel expression tree compiled for the device (``csrc/bgp_tree.hip``): ``ops`` (int32: the metric
+    table and the postfix instructions, ``include/bgp.h``), ``imm`` (the exponents of ``Exponentiation``), ``P`` parameter slots and
+    ``depth``, the deepest the value stack gets.  ``params`` maps theta to the slots."""
+
+    def __init__(self, ops, imm, theta_index, fixed, white_slots, n_theta, depth):
+        self.ops = np.ascontiguousarray(ops, dtype=np.int32)
+        self.imm = np.ascontiguousarray(imm, dtype=np.float64)
+        self._theta_index = np.asarray(theta_index, dtype=np.int64)  # per slot: where in theta, or -1 for a fixed value
+        self._fixed = np.asarray(fixed, dtype=np.float64)            # per slot: the fixed log value
+        self._white_slots = list(white_slots)  # slots of the WhiteKernel that param_for_white_kernel_in_sum finds
+        self.P, self.n_theta, self.depth = len(self._fixed), n_theta, depth
+
+    def params(self, thetas, noise_zero=False):
+        """(B, p) or (p,) theta -> (B, P) log-space parameter rows: free entries gathered from theta, fixed ones filled in.
+        ``noise_zero``: the white level ``noise_set_to_zero`` drops is -inf (``_posterior._with_white_zeroed``, vectorised)."""
+        T = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        if T.shape[1] != self.n_theta:
+            raise ValueError(f"theta has {T.shape[1]} entries, kernel has {self.n_theta} free hyper-parameters")
+        out = np.empty((T.shape[0], self.P))
+        free = self._theta_index >= 0
+        out[:, free] = T[:, self._theta_index[free]]
+        out[:, ~free] = self._fixed[~free]
+        if noise_zero:
+            out[:, self._white_slots] = -np.inf
+        return out
+
+
+def compile_tree(kernel, d):
+    """``kernel`` as a ``TreeProgram`` for inputs of ``d`` columns, or None when a node has no device form (Matern with a general
+    nu, a kernel class the device does not know), d > 32, the tree needs a deeper stack than ``TREE_STACK`` or more metrics,
+    instructions, immediates or slots than the device program holds.  Leaves that read the same length-scale entries of theta (or
+    the same fixed values) share one scaled squared distance of the metric table."""
+    from sklearn.gaussian_process.kernels import DotProduct, Exponentiation, ExpSineSquared, RationalQuadratic
+
+    if not 1 <= d <= TREE_MAXD:
+        return None
+    theta_index, fixed, metrics, met_keys, ins, imm, slots_of = [], [], [], {}, [], [], {}
+    cursor = [0]
+
+    def alloc(leaf):
+        """name -> first slot of every hyper-parameter of a leaf, in theta order (``Kernel.theta``: the non-fixed ones in
+        ``hyperparameters`` order)."""
+        out = {}
+        for hp in leaf.hyperparameters:
+            with np.errstate(divide="ignore"):
+                val = np.log(np.atleast_1d(np.asarray(getattr(leaf, hp.name), dtype=np.float64)))
+            out[hp.name] = (len(fixed), len(val))
+            for v in val:
+                theta_index.append(-1 if hp.fixed else cursor[0])
+                fixed.append(v)
+                cursor[0] += 0 if hp.fixed else 1
+        slots_of[id(leaf)] = out
+        return out
+
+    def metric(kind, slot=0, width=0):
+        idx = tuple(theta_index[slot : slot + width])
+        key = (kind, idx if all(i >= 0 for i in idx) else tuple(fixed[slot : slot + width]))
+        if key not in met_keys:
+            met_keys[key] = len(metrics)
+            metrics.append((kind, slot))
+        return met_keys[key]
+
+    def emit(k):
+        """Append the postfix code of ``k``; returns the stack depth it needs."""
+        if isinstance(k, (Sum, Product)):
+            d1 = emit(k.k1)
+            d2 = emit(k.k2)
+            ins.append((TO_ADD if isinstance(k, Sum) else TO_MUL, 0, 0, 0))
+            return max(d1, 1 + d2)
+        if isinstance(k, Exponentiation):
+            d1 = emit(k.kernel)
+            imm.append(float(k.exponent))
+            ins.append((TO_POW, len(imm) - 1, 0, 0))
+            return d1
+        if not isinstance(k, (ConstantKernel, WhiteKernel, RBF, RationalQuadratic, ExpSineSquared, DotProduct)):
+            raise NotImplementedError(type(k).__name__)
+        s = alloc(k)
+        if isinstance(k, ConstantKernel):
+            ins.append((TO_CONST, s["constant_value"][0], 0, 0))
+        elif isinstance(k, WhiteKernel):
+            ins.append((TO_WHITE, s["noise_level"][0], 0, 0))
+        elif isinstance(k, DotProduct):
+            ins.append((TO_DOT, metric(TM_DOT), s["sigma_0"][0], 0))
+        elif isinstance(k, ExpSineSquared):
+            ins.append((TO_ESS, metric(TM_EUCL), s["length_scale"][0], s["periodicity"][0]))
+        else:
+            slot, width = s["length_scale"]
+            if width not in (1, d):
+                raise NotImplementedError(f"anisotropic length scale has {width} entries but X has {d} columns")
+            m = metric(TM_ARD if width > 1 else TM_ISO, slot, width)
+            if isinstance(k, RationalQuadratic):
+                ins.append((TO_RQ, m, s["alpha"][0], 0))
+            else:
+                name = _stationary_name(k)  # (raises for a general nu)
+                ins.append(({"rbf": TO_RBF, "matern12": TO_M12, "matern32": TO_M32, "matern52": TO_M52}[name], m, 0, 0))
+        return 1
+
+    try:
+        depth = emit(kernel)
+    except NotImplementedError:
+        return None
+    if (depth > TREE_STACK or len(metrics) > TREE_MAXMET or len(ins) > TREE_MAXINS or len(imm) > TREE_MAXIMM
+            or len(fixed) > TREE_MAXP):
+        return None
+    white = kernel if isinstance(kernel, WhiteKernel) else None
+    present, name = param_for_white_kernel_in_sum(kernel)
+    if present:
+        white = kernel
+        for part in name.split("__"):
+            white = getattr(white, part)
+    white_slots = [slots_of[id(white)]["noise_level"][0]] if white is not None else []
+    ops = [len(metrics), len(ins)] + [v for mt in metrics for v in mt] + [v for i in ins for v in i]
+    return TreeProgram(ops, imm, theta_index, fixed, white_slots, cursor[0], depth)
+
+
 class GramPlan:
-    """A kernel expression tree without a canonical device form: its matrices are evaluated on the host with the
-    scikit-learn kernel object (what the reference does for every kernel, ``sklearn/_gpr.py:582``) and handed to
-    the device, which does everything behind them.  ``why`` keeps the reason the canonical analysis gave."""
+    """A kernel expression tree without a canonical device form.  With a ``program`` (``compile_tree``) the device evaluates the
+    tree itself (``bgp_tree.hip``); without one its matrices are evaluated on the host with the scikit-learn kernel object (what
+    the reference does for every kernel, ``sklearn/_gpr.py:582``) and handed to the device.  Either way the device does everything
+    behind the matrices.  ``why`` keeps the reason the canonical analysis gave."""
 
     generic = True
     form, stationary = "product", "matern52"  # (what the device context is created with; its Gram build is never used)
 
-    def __init__(self, n_theta, why):
+    def __init__(self, n_theta, why, program=None):
         self.n_theta = n_theta
         self.why = why
+        self.program = program
 
     def canonical(self, theta, d):
         raise NotImplementedError("this kernel has no canonical device form (%s): its matrices come from the host" % self.why)
@@ -254,11 +379,11 @@ def _leaves_in_theta_order(kernel, start=0):
     return [(kernel, start, n_free)], start + n_free
 
 
-def analyse_kernel(kernel, strict=False):
+def analyse_kernel(kernel, strict=False, d=None):
     """Analyse a kernel expression tree: a ``KernelPlan`` for the canonical forms (device Gram build), a ``GramPlan``
-    (host-evaluated kernel matrices, device arithmetic) for every other tree scikit-learn can evaluate
-    (``bask/bayesgpr.py:148-159`` accepts any kernel).  ``strict=True`` raises ``NotImplementedError`` instead of
-    returning a ``GramPlan``."""
+    for every other tree scikit-learn can evaluate (``bask/bayesgpr.py:148-159`` accepts any kernel) -- with the input
+    dimension ``d`` given, its ``program`` is the tree compiled for the device where ``compile_tree`` covers it.
+    ``strict=True`` raises ``NotImplementedError`` instead of returning a ``GramPlan``."""
     if not isinstance(kernel, Kernel):
         raise TypeError(f"expected a scikit-learn kernel object, got {type(kernel)}")
     try:
@@ -267,7 +392,7 @@ def analyse_kernel(kernel, strict=False):
         if strict:
             raise
         with np.errstate(divide="ignore"):
-            return GramPlan(len(kernel.theta), str(exc))
+            return GramPlan(len(kernel.theta), str(exc), None if d is None else compile_tree(kernel, int(d)))
 
 
 def _analyse_canonical(kernel):

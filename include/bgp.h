@@ -773,6 +773,41 @@ int bgp_posterior_batch_gram(bgp_ctx* ctx, int B, const double* K, int use_alpha
 int bgp_predict_batch_gram(bgp_ctx* ctx, int B, int m, const double* Ks, const double* kss, const double* Kss, double* mean,
                            double* var, double* cov);
 
+/*
+ * Generic kernel expression trees evaluated ON THE DEVICE.  The host compiles the tree once into a kernel
+ * program and passes it in every call -- a few dozen ints, no registration -- with B rows of P log-space parameters; a tile kernel
+ * evaluates the tree for every pair of points and everything behind the matrices is what the _gram calls run.  Trees the compiler
+ * does not cover keep the _gram calls.
+ *   ops     n_ops int32 words: [n_met, n_ins, n_met x (kind, slot), n_ins x (code, a, b, c)]
+ *             metric kinds: 0 sum ((x-y)/l)^2 with l = exp(params[slot]); 1 the same with l_k = exp(params[slot + k]);
+ *               2 sum (x-y)^2; 3 sum x y.  At most 4 metrics: leaves that read the same length-scale slots share one.
+ *             instruction codes, postfix over a value stack of depth 8 (at most 32 instructions):
+ *               0 Constant(slot)  1 White(slot)  2 RBF(metric)  3 / 4 / 5 Matern 1/2, 3/2, 5/2 (metric)  6 RationalQuadratic(metric,
+ *               slot of alpha)  7 ExpSineSquared(metric of kind 2, slot of length_scale, slot of periodicity)  8 DotProduct(metric of
+ *               kind 3, slot of sigma_0)  9 Sum  10 Product  11 Exponentiation(index into imm)
+ *   imm     n_imm doubles (at most 8): the exponents of Exponentiation
+ *   params  B * P doubles, log space; -inf is legal (a zeroed white level).  P <= 256.
+ * BGP_ERR_INVALID, before anything is launched, for d > 32, a stack that passes depth 8 or underflows, an unknown op or metric and a
+ * slot index >= P.  WhiteKernel counts on i == j of kernel_(X) and nothing in kernel_(Xq, X).  Item b's bits are those of a call
+ * with that item alone, and the matrices of kernel_(X) are exactly symmetric.
+ *   bgp_tree_gram             the matrices themselves: Xq == NULL: out B*n*n = kernel_(X_train) (no alpha); else out B*m*n =
+ *                             kernel_(Xq, X_train), the query rows warped as bgp_predict_batch warps them
+ *   bgp_lml_batch_tree        as bgp_lml_batch_gram.  warp != NULL (B * 2d, the layout of bgp_lml_batch_warped): item b is built
+ *                             from its own Beta-CDF warp of the un-warped training inputs
+ *   bgp_posterior_batch_tree  as bgp_posterior_batch_gram; the posteriors stay resident
+ *   bgp_predict_batch_tree    as bgp_predict_batch_gram for the B resident posteriors, with kernel_(Xq, X_train), kernel_.diag(Xq)
+ *                             and (cov != NULL only) kernel_(Xq) built on the device from params as given: the caller passes the
+ *                             block with the white level at -inf when it wants the latent function
+ */
+int bgp_tree_gram(bgp_ctx* ctx, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B, const double* params, int m,
+                  const double* Xq, double* out);
+int bgp_lml_batch_tree(bgp_ctx* ctx, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B, const double* params,
+                       const double* warp, int use_alpha, double* lml, int* status);
+int bgp_posterior_batch_tree(bgp_ctx* ctx, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B,
+                             const double* params, int use_alpha, double* L, double* alpha, double* K_inv, double* lml, int* status);
+int bgp_predict_batch_tree(bgp_ctx* ctx, int n_ops, const int* ops, int n_imm, const double* imm, int P, int B, const double* params,
+                           int m, const double* Xq, double* mean, double* var, double* cov);
+
 /* Number of walker groups (HIP streams) an LML batch of the launch schedule is split over; results are bit-identical for
  * every count.  Default: ONE group.  With k > 1 groups a batch of at least 64 matrices (or, after this call, of at least 16) is
  * factorised as k slices side by side, one group's kernels filling the tails of another's launches.  Two groups were the
